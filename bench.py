@@ -16,9 +16,18 @@ replica of the 299-cell workload with a rank-specific seed; there is no data-pat
 The per-cell results are gathered once after timing (the reference's parfor output assembly),
 and the elapsed time is the max over ranks.
 
-Beside `value` (kernel mode, K = 256) the line carries the K in {1, 64, 256, 1024} sweep, the
-drop-in's per-call latency, the metric's 200k-step end-to-end fit (BASELINE config 2), configs
-3/4/5, and the CPU baseline at all host threads and at one core.
+A plain run does only what `value` (kernel mode, K = 256) needs: set-up, warm-up, the timed steps,
+the output dump if asked for, the result line. With --full the line also carries the K in
+{1, 64, 256, 1024} sweep, the drop-in's per-call latency, the metric's 200k-step end-to-end fit
+(BASELINE config 2), configs 3/4/5, and the CPU baseline at all host threads and at one core
+(SURVEY §8(d)); the --no-* and --*-steps options select among those legs.
+
+--dump-outputs DIR writes what the last timed launch returned to its caller: DIR/ss.npy (float64),
+the SS of every row of that launch's proposal batch, and DIR/in_bounds.npy (float32), 1 on the rows
+inside the parameter box and 0 on the others. The kernel marks a row it was told to skip with +Inf;
+the dump holds 0 there (an SS is a sum of squares, never 0), so every number in it is finite unless
+an evaluation went wrong. With several ranks the names carry _rank<r>. The proposals come from a
+seeded generator, so two builds run with the same arguments can be compared value for value.
 
 Prints ONE JSON line on rank 0.
 """
@@ -705,6 +714,12 @@ def main():
     ap.add_argument("--launches-per-step", type=int, default=128,
                     help="batched launches per step: one step = this many lockstep proposal rounds")
     ap.add_argument("--distinct-rounds", type=int, default=8, help="distinct resident proposal batches cycled")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the SS values of the last timed launch to DIR/ss.npy and its "
+                         "in-bounds mask to DIR/in_bounds.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (kernel sweep, drop-in latency, end-to-end "
+                         "DRAM fits, configs 3/4/5, CPU baselines); the options below select among them")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true", help="skip the K in {1, 64, 256, 1024} kernel sweep")
@@ -834,6 +849,42 @@ def main():
         },
         "results_finite": finite_ok,
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ss, act_last, rank, world)
+    if args.full:
+        full_legs(res, args, lk, cells, rounds, dev, stream, rank, world, device_index, coll_dev, reduce)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    lk.close()
+    if distributed:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir: str, ss: np.ndarray, in_bounds: np.ndarray, rank: int, world: int):
+    """--dump-outputs: the SS array the last timed launch wrote, one float64 per row of its proposal
+    batch (ss.npy), and that launch's in-bounds mask as float32 (in_bounds.npy): 299 x K x 12 bytes,
+    0.9 MB at the default K. The rows outside the parameter box, which the kernel skips and marks
+    with +Inf, hold 0 in the dump; an in-bounds row is written as the kernel returned it. Beyond
+    64 MB (K > 17,000) a fixed seeded sample of the rows, in row order, is written instead."""
+    os.makedirs(out_dir, exist_ok=True)
+    in_bounds = np.asarray(in_bounds, dtype=bool)
+    ss = np.where(in_bounds, ss, 0.0)
+    cap = 64_000_000 // 12 - 64  # rows; leaves room for the two .npy headers
+    if ss.size > cap:
+        pick = np.sort(np.random.default_rng(20201028).choice(ss.size, cap, replace=False))
+        ss, in_bounds = ss[pick], in_bounds[pick]
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(out_dir, f"ss{tag}.npy"), np.ascontiguousarray(ss, dtype=np.float64))
+    np.save(os.path.join(out_dir, f"in_bounds{tag}.npy"), in_bounds.astype(np.float32))
+
+
+def full_legs(res: dict, args, lk, cells, rounds, dev, stream, rank: int, world: int, device_index: int, coll_dev,
+              reduce):
+    """--full: every leg beside `value`, after the timed steps, each into its own key of the line."""
+    import torch.distributed as dist
+
+    distributed = world > 1
     if not args.no_sweep:
         res["kernel_sweep"] = kernel_sweep(lk, cells, dev, stream, seed=77 + rank)
         res["kernel_x0_theta"] = x0_theta_kernel(lk, cells, dev, stream)
@@ -850,6 +901,7 @@ def main():
         h_el = (time.perf_counter() - h0) / 5
         res["host_api_pcie_inclusive"] = {"value": int(act_h.sum()) / h_el, "unit": "SS evals/s",
                                           "ms_per_call": h_el * 1e3, "bytes_h2d": int(theta_h.nbytes + rounds.B * 5)}
+    rounds.theta, rounds.active = [], []  # the resident proposal batches are freed before the fits
     del rounds
     if args.dram_steps > 1:
         if distributed:
@@ -872,12 +924,6 @@ def main():
     if distributed:
         dist.barrier()   # every GPU leg of every rank is done before the host cores are timed
     cpu_legs(res, rank, world, args, cells, theta_h, act_h, lk, spots)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    lk.close()
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def cpu_legs(res: dict, rank: int, world: int, args, cells, theta_h, act_h, lk, spots: dict):

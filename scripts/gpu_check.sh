@@ -16,7 +16,7 @@ rc=$?; tail -5 "$OUT/${TAG}_pytest_gpu.log"; stop_if_fault $rc
 echo "== smoke"; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/${TAG}_smoke.log" 2>&1
 rc=$?; tail -3 "$OUT/${TAG}_smoke.log"; stop_if_fault $rc
 fi
-echo "== bench"; timeout -k 10 600 python bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+echo "== bench"; timeout -k 10 600 python bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 rc=$?; cat "$OUT/${TAG}_bench.json"; stop_if_fault $rc
 echo "== rocprofv3 kernel trace"
 export TMPDIR=/tmp

@@ -1,5 +1,6 @@
 """bench.py's own multi-GPU launch (`--gpus N` without torch.distributed.run): the launch plan, the
-WORLD_SIZE mismatch exit and the child processes, on CPU (no GPU call is made by any of these)."""
+WORLD_SIZE mismatch exit and the child processes, on CPU (no GPU call is made by any of these), and
+the two tests marked gpu: what a plain run and a --full run print and dump."""
 import os
 import subprocess
 import sys
@@ -115,3 +116,80 @@ def test_cpu_baseline_is_in_the_line_at_every_world_size(monkeypatch, rank, worl
     bench.cpu_legs(res, rank, world, SimpleNamespace(no_cpu_baseline=True, proposals=4, cpu_seconds=1.0), C(),
                    None, None, None, {})
     assert res == {}
+
+
+def test_dump_outputs_writes_float64_and_samples_past_64_mb(tmp_path):
+    """--dump-outputs: DIR/ss.npy holds the SS as float64 with 0 on the skipped rows (the kernel's +Inf
+    mark there is not a result), DIR/in_bounds.npy the mask as float32; an in-bounds row is written as
+    it came, so a wrong Inf or NaN there still shows; per-rank names with several ranks; arrays past
+    64 MB in all are cut to a fixed sample of the rows, the same at every call."""
+    import numpy as np
+
+    ss, act = np.array([1.5, np.inf, 3.0, np.inf, np.nan]), np.array([1, 0, 1, 1, 1], np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), ss, act, 0, 1)
+    got, m = np.load(tmp_path / "a" / "ss.npy"), np.load(tmp_path / "a" / "in_bounds.npy")
+    assert got.dtype == np.float64 and m.dtype == np.float32
+    assert got.tobytes() == np.array([1.5, 0.0, 3.0, np.inf, np.nan]).tobytes() and m.tolist() == [1, 0, 1, 1, 1]
+    bench.dump_outputs(str(tmp_path / "a"), ss, act, 1, 2)
+    assert (tmp_path / "a" / "ss_rank1.npy").exists() and (tmp_path / "a" / "in_bounds_rank1.npy").exists()
+    big = np.arange(1.0, 5_500_001.0)
+    keep = np.arange(big.size) % 3 != 0
+    bench.dump_outputs(str(tmp_path / "b"), big, keep, 0, 1)
+    bench.dump_outputs(str(tmp_path / "c"), big, keep, 0, 1)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in ("ss.npy", "in_bounds.npy")) <= 64_000_000
+    b, mb = np.load(tmp_path / "b" / "ss.npy"), np.load(tmp_path / "b" / "in_bounds.npy")
+    assert b.shape == mb.shape and np.all(np.diff(b[mb == 1]) > 0) and np.all(b[mb == 0] == 0)
+    assert np.all((b[mb == 1] - 1) % 3 != 0)                      # mask and values are cut at the same rows
+    assert np.array_equal(b, np.load(tmp_path / "c" / "ss.npy"))
+
+
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "results_finite"}
+
+
+def _run_bench(dump_dir, *extra):
+    """One short benchmark process (3 steps, 1 warm-up): its JSON line and the two arrays it dumped."""
+    import json
+
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(dump_dir), *extra], env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(dump_dir)) == ["in_bounds.npy", "ss.npy"]
+    return (json.loads(r.stdout.strip().splitlines()[-1]), np.load(os.path.join(dump_dir, "ss.npy")),
+            np.load(os.path.join(dump_dir, "in_bounds.npy")))
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    return _run_bench(tmp_path_factory.mktemp("plain"))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_launch(plain_run):
+    """A plain run prints the headline line only (every other leg is behind --full), times exactly
+    --steps steps, and --dump-outputs writes the last timed launch's SS: one float64 per row, every one
+    finite, positive on the in-bounds rows and 0 on the skipped ones, beside the mask as float32."""
+    import numpy as np
+
+    d, a, m = plain_run
+    assert set(d) == PLAIN_KEYS
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["results_finite"]
+    assert d["ms_per_step"] == pytest.approx(d["config"]["timed_region_s"] * 1e3 / 3)
+    assert a.dtype == np.float64 and a.shape == (d["config"]["rows_per_launch_per_gpu"],)
+    assert m.dtype == np.float32 and m.shape == a.shape and set(np.unique(m)) == {0.0, 1.0}
+    assert np.all(np.isfinite(a)) and np.all(a[m == 1] > 0) and np.all(a[m == 0] == 0)
+
+
+@pytest.mark.gpu
+def test_full_adds_the_other_legs_to_the_same_line(plain_run, tmp_path):
+    """--full keeps the headline keys and adds the legs its options leave on (here the kernel sweep and
+    the drop-in latency; the fits, configs and CPU baselines are switched off to keep the test short).
+    The timed steps are the same ones: a second process with the same arguments dumps the same bits."""
+    d, a, m = _run_bench(tmp_path, "--full", "--no-cpu-baseline", "--dram-steps", "0", "--no-configs")
+    assert set(d) == PLAIN_KEYS | {"kernel_sweep", "kernel_x0_theta", "drop_in_latency", "host_api_pcie_inclusive"}
+    assert [s["K"] for s in d["kernel_sweep"]] == [1, 64, 256, 1024]
+    assert a.tobytes() == plain_run[1].tobytes() and m.tobytes() == plain_run[2].tobytes()
+
+
