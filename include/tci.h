@@ -172,8 +172,8 @@ typedef struct {
  *            state-independent random quantity (proposal offsets z*R on MFMA, uniforms, Gamma
  *            variates), then one workgroup per chain walks the chunk with its ssfun evaluations in
  *            the loop (one workgroup barrier per step): latency-bound runs (few chains). The draws
- *            that do not need the adapted R (normals, uniforms, Gamma variates) are drawn on a
- *            second stream one chunk ahead, under the previous chunk's walk.
+ *            that do not need the adapted R (normals, uniforms, Gamma variates) are drawn one chunk
+ *            ahead inside the previous chunk's walk launch (the first chunk's: one k_draws_rng launch).
  *   BATCHED: one launch per stage, every chain's ssfun in the batched likelihood kernel, replayed
  *            as a hipGraph per adaptation window: many chains, or cells too long for FUSED.
  *   WALK:    FUSED's draws pass, then ONE WAVEFRONT per chain walks the chunk (stage 2 evaluated
@@ -204,7 +204,7 @@ typedef struct {
   double kernel_ms[4];  /* with opt.kernel_times (FUSED / WALK): device ms summed per kernel class -- [0] the
                            draws pass (k_draws), [1] the chain walk (k_chain / k_walk), [2] the covariance
                            adaptation (k_adapt_*), [3] FUSED's split draws: the normals and scalar draws
-                           (k_draws_rng, on a second stream one chunk ahead, overlapping the walk) --
+                           of the first chunk (k_draws_rng; later chunks' are drawn inside the k_chain launches, class 1) --
                            written by tci_dram_run, 0 otherwise */
   int64_t kernel_launches[4]; /* launches per class behind kernel_ms */
 } tci_dram_outputs;
@@ -220,6 +220,30 @@ int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, co
                  const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                  const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
                  tci_dram_outputs* out);
+
+/* ---- Posterior predictive envelopes (mcmcstat's mcmcpred / plims) ---------------------------
+ * The forward model at S posterior samples per cell, reduced on the device to quantile bands of the
+ * simulated signal at every acquisition time; only the bands come back to the host. */
+typedef struct {
+  int32_t grid_mode;      /* TCI_GRID_RAW (default) or TCI_GRID_INTERP */
+  int64_t scratch_bytes;  /* cap on the device scratch for simulated rows; 0 = default (1 GiB) */
+} tci_predict_options;
+int tci_predict_defaults(tci_predict_options* opt);
+
+/* For k in [0,n_sel): rows theta[(k*S + s)*ld_theta .. ], s in [0,S), are S posterior samples of cell
+ * cell_id[k]. For each k, each dye and each acquisition time j < N(cell):
+ *   x = sort(sim[k, 0..S-1, j])            (NaN last, as MATLAB's sort)
+ *   h = (S-1)*probs[q]; lo = floor(h); f = h - lo
+ *   out[(k*nq + q)*ld_out + j] = (lo + 1 < S) ? x[lo] + f*(x[lo+1] - x[lo]) : x[S-1]
+ * i.e. mcmcstat's plims: interp1(sort(x), (n-1)*p+1). ms2 is already x A. Entries j >= N(cell) of an
+ * output row are NaN. HOST pointers, synchronous. opt may be NULL (the defaults). 1 <= S <= 4096,
+ * 1 <= nq <= 16, every prob finite and in [0, 1]; ld_theta >= 7 + N and ld_out >= N of every selected
+ * cell (TCI_ERANGE). The simulated rows (2 * n_sel * S * ld_out doubles) live in a scratch buffer the
+ * context owns; past opt->scratch_bytes whole cells are processed in chunks (same results), and
+ * TCI_EINVAL is returned when one cell alone does not fit. */
+int tci_predict(tci_ctx* ctx, const tci_predict_options* opt, const double* theta, int64_t ld_theta,
+                const int32_t* cell_id, int64_t n_sel, int64_t S, const double* probs, int32_t nq,
+                double* ms2_q, double* pp7_q, int64_t ld_out);
 
 const char* tci_version(void);
 

@@ -23,7 +23,13 @@ function [MCMCresults, MCMCplot, MCMCchain] = tci_fit(data, varargin)
 %   and the GPU's own:
 %     'device' (0), 'cells' (all: 1-based cell numbers to fit -- one GPU's share of a dataset),
 %     'thin' (1 = every chain row, as the reference keeps them; k keeps rows 1, 1+k, ...; 0 keeps none
-%        and MCMCchain is empty), 'seed' (0), 'engine' ('auto'), 'adapt_pmax' (0; see include/tci.h).
+%        and MCMCchain is empty), 'seed' (0), 'engine' ('auto'), 'adapt_pmax' (0; see include/tci.h),
+%     'predict' (0: none; nsample > 0 adds the predictive bands of mcmcstat's mcmcpred to MCMCplot:
+%        predMS2 and predPP7 (3 x N: the 2.5 %, 50 % and 97.5 % quantiles, at every time point, of the
+%        forward model at nsample posterior samples) and pred_probs, one tci_mex('predict', ...) call for
+%        all cells. Needs 'thin' > 0. Where mcmcpred draws chain rows at random, the rows used here
+%        are round(linspace(1, rows, nsample)) of the post-burn-in rows kept (all of them when fewer),
+%        at most 4096.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -49,6 +55,7 @@ p.addParameter('thin', 1);
 p.addParameter('seed', 0);
 p.addParameter('engine', 'auto');
 p.addParameter('adapt_pmax', 0);
+p.addParameter('predict', 0);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -116,7 +123,15 @@ MCMCresults = struct('mean_v',{},'sigma_v',{},'mean_ton',{},'sigma_ton',{},...  
     'mean_MS2_basal',{},'sigma_MS2_basal',{},'mean_PP7_basal',{},'sigma_PP7_basal',{},'mean_R',{},...
     'sigma_R',{},'mean_dR',{},'sigma_dR',{},'mean_sigma',{},'sigma_sigma',{},...
     'cell_index',{},'ApprovedFits',{});
-MCMCplot = struct('t_plot',{},'MS2_plot',{},'PP7_plot',{},'simMS2',{},'simPP7',{});
+if o.predict > 0
+    if o.thin <= 0
+        error('tci:predict', 'predict needs the chain rows: use thin > 0');
+    end
+    MCMCplot = struct('t_plot',{},'MS2_plot',{},'PP7_plot',{},'simMS2',{},'simPP7',{}, ...
+        'predMS2',{},'predPP7',{},'pred_probs',{});
+else
+    MCMCplot = struct('t_plot',{},'MS2_plot',{},'PP7_plot',{},'simMS2',{},'simPP7',{});
+end
 MCMCchain = struct('v_chain',{},'ton_chain',{},'A_chain',{},'tau_chain',{},...
     'MS2_basal_chain',{},'PP7_basal_chain',{},'R_chain',{},'dR_chain',{},'s2chain',{});
 nc = numel(setup);
@@ -152,6 +167,19 @@ else
     results = tci_mex('dram', h, 1:nc, X0, LB, UB, MU, SIG, J0, sigma2_0, options);
 end
 
+% ---- predictive bands: the same sample rows for every cell, one call (mcmcpred, deterministic rows) --
+if o.predict > 0
+    kept = find(sel);
+    if isempty(kept)
+        error('tci:predict', 'the fit kept no chain rows after n_burn');
+    end
+    if numel(kept) >= o.predict
+        kept = kept(round(linspace(1, numel(kept), o.predict)));
+    end
+    pred_probs = [0.025, 0.5, 0.975];
+    [predMS2, predPP7] = tci_mex('predict', h, 1:nc, permute(chain(:, :, kept), [1 3 2]), pred_probs, 'raw');
+end
+
 % ---- summaries, forward model at the means, the three structs (:276-356) -------------------------
 for k = 1:nc
     n = numel(setup(k).t);
@@ -171,8 +199,14 @@ for k = 1:nc
     r.ApprovedFits = setup(k).approved;               % :345-350
     MCMCresults(k) = r;
     [simMS2, simPP7] = tci_mex('forward', h, k, th, 'raw');   % :307-309 (x mean_A inside)
-    MCMCplot(k) = struct('t_plot', setup(k).t, 'MS2_plot', setup(k).MS2, 'PP7_plot', setup(k).PP7, ...
+    plotk = struct('t_plot', setup(k).t, 'MS2_plot', setup(k).MS2, 'PP7_plot', setup(k).PP7, ...
         'simMS2', simMS2, 'simPP7', simPP7);
+    if o.predict > 0
+        plotk.predMS2 = predMS2(1:n, :, k)';            % nq x N
+        plotk.predPP7 = predPP7(1:n, :, k)';
+        plotk.pred_probs = pred_probs;
+    end
+    MCMCplot(k) = plotk;
     if o.thin > 0
         c = reshape(chain(1:7+n, k, sel), 7+n, [])';   % rows x P
         MCMCchain(k) = struct('v_chain', c(:,1), 'ton_chain', c(:,3), 'A_chain', c(:,6), ...

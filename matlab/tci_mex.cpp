@@ -19,6 +19,12 @@
 //                                               cells: 1 x B; returns B x 1
 //   ss = tci_mex('ss_batch', h, cells, X, active)   active: 1 x B logical (false -> +Inf)
 //   [ms2, pp7] = tci_mex('forward', h, cell, x, 'raw' | 'interp')
+//   [ms2q, pp7q] = tci_mex('predict', h, cells, X, probs, 'raw' | 'interp')
+//          predictive bands (mcmcstat's mcmcpred / plims) reduced on the GPU (tci_predict): X is
+//          P x S x n, S posterior samples (one theta per column) of each of the n cells in `cells`
+//          (1 x n) -- column-major, the ABI's [n][S][P] with nothing transposed; probs: 1 to 16
+//          probabilities in [0, 1]. ms2q, pp7q: N_max x nq x n (N_max = the longest selected cell),
+//          the quantiles over the S simulated values at every acquisition time, NaN past a cell's N.
 //   tci_mex('destroy', h)
 //   n = tci_mex('device_count')                 HIP devices visible to this MATLAB process
 //   [results, chain, s2chain, R] = tci_mex('dram', h, cells, X0, LB, UB, MU, SIG, J0, sigma2[, options])
@@ -214,6 +220,61 @@ void cmd_forward(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   mxArray* pp7 = mxCreateDoubleMatrix(1, (mwSize)n, mxREAL);
   check(ctx, tci_forward(ctx, x, (int64_t)mxGetNumberOfElements(prhs[3]), &cell, 1, mode,
                          mxGetPr(plhs[0]), mxGetPr(pp7), n), "tci_forward");
+  if (nlhs > 1) plhs[1] = pp7; else mxDestroyArray(pp7);
+}
+
+void cmd_predict(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 5 || nrhs > 6) mexErrMsgIdAndTxt("tci:arg", "tci_mex('predict', h, cells, X, probs[, 'raw'|'interp'])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const size_t n = mxGetNumberOfElements(prhs[2]);
+  const double* c = doubles(prhs[2], -1, "cells");
+  if (n == 0) mexErrMsgIdAndTxt("tci:arg", "cells must name at least one cell");
+  const double* X = doubles(prhs[3], -1, "X");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[3]);
+  const mwSize* d = mxGetDimensions(prhs[3]);
+  const size_t P = d[0], S = nd > 1 ? d[1] : 1, nx = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || nx != n) mexErrMsgIdAndTxt("tci:arg", "X must be P x S x n: S samples per cell, n = numel(cells)");
+  if (P < 9) mexErrMsgIdAndTxt("tci:arg", "X must have at least 9 rows ([v, tau, ton, MS2_basal, PP7_basal, A, R, dR])");
+  if (S < 1 || S > 4096) mexErrMsgIdAndTxt("tci:arg", "X must hold 1 to 4096 samples per cell (its second dimension)");
+  const size_t nq = mxGetNumberOfElements(prhs[4]);
+  const double* pr = doubles(prhs[4], -1, "probs");
+  if (nq < 1 || nq > 16) mexErrMsgIdAndTxt("tci:arg", "probs must have 1 to 16 elements");
+  for (size_t q = 0; q < nq; ++q)
+    if (!(pr[q] >= 0.0 && pr[q] <= 1.0)) mexErrMsgIdAndTxt("tci:arg", "probs(%d) must be in [0, 1]", (int)q + 1);
+  tci_predict_options opt;
+  tci_predict_defaults(&opt);
+  if (nrhs > 5) {
+    if (!mxIsChar(prhs[5])) mexErrMsgIdAndTxt("tci:arg", "the grid must be 'raw' or 'interp'");
+    const std::string g = str_of(prhs[5]);
+    if (g == "interp") opt.grid_mode = TCI_GRID_INTERP;
+    else if (g == "raw") opt.grid_mode = TCI_GRID_RAW;
+    else mexErrMsgIdAndTxt("tci:arg", "the grid must be 'raw' or 'interp'");
+  }
+  std::vector<int32_t> cid(n);
+  for (size_t b = 0; b < n; ++b) {
+    if (!(c[b] >= 1 && c[b] <= 2147483647.0) || c[b] != (double)(int64_t)c[b])
+      mexErrMsgIdAndTxt("tci:arg", "cells(%d) must be a positive integer", (int)b + 1);
+    cid[b] = (int32_t)c[b] - 1;
+  }
+
+  tci_ctx* ctx = handle_of(prhs[1]);
+  int64_t nmax = 0;
+  for (size_t b = 0; b < n; ++b) {
+    int64_t nb = 0;
+    check(ctx, tci_cell_points(ctx, cid[b], &nb), "tci_cell_points");
+    nmax = std::max(nmax, nb);
+  }
+  const mwSize d3[3] = {(mwSize)nmax, (mwSize)nq, (mwSize)n};  // N_max x nq x n == [cell][q][N_max]
+  mxArray* ms2 = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+  mxArray* pp7 = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+  const int rc = tci_predict(ctx, &opt, X, (int64_t)P, cid.data(), (int64_t)n, (int64_t)S, pr, (int32_t)nq, mxGetPr(ms2),
+                             mxGetPr(pp7), nmax);
+  if (rc != TCI_OK) {
+    mxDestroyArray(ms2);
+    mxDestroyArray(pp7);
+    check(ctx, rc, "tci_predict");
+  }
+  plhs[0] = ms2;
   if (nlhs > 1) plhs[1] = pp7; else mxDestroyArray(pp7);
 }
 
@@ -417,6 +478,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "ss_batch") cmd_ss_batch(plhs, nrhs, prhs);
   else if (cmd == "forward") cmd_forward(nlhs, plhs, nrhs, prhs);
   else if (cmd == "dram") cmd_dram(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "predict") cmd_predict(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

@@ -69,6 +69,10 @@ class tci_dram_outputs(C.Structure):
                 ("elapsed_ms", C.c_double), ("kernel_ms", C.c_double * 4), ("kernel_launches", C.c_int64 * 4)]
 
 
+class tci_predict_options(C.Structure):
+    _fields_ = [("grid_mode", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -88,6 +92,9 @@ SIGNATURES = [
     ("tci_dram_defaults", C.c_int, [C.POINTER(tci_dram_options)]),
     ("tci_dram_run", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp, _dp,
                                _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs)]),
+    ("tci_predict_defaults", C.c_int, [C.POINTER(tci_predict_options)]),
+    ("tci_predict", C.c_int, [C.c_void_p, C.POINTER(tci_predict_options), _dp, C.c_int64, _i32p, C.c_int64, C.c_int64,
+                              _dp, C.c_int32, _dp, _dp, C.c_int64]),
     ("tci_version", C.c_char_p, []),
 ]
 

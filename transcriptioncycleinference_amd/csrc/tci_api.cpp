@@ -43,6 +43,8 @@ struct tci_ctx {
   double* d_out0 = nullptr;
   double* d_out1 = nullptr;
   size_t cap_theta = 0, cap_cell = 0, cap_active = 0, cap_out0 = 0, cap_out1 = 0;
+  double* d_sim = nullptr;          // tci_predict: the simulated rows of one chunk of cells (MS2 rows, then PP7 rows)
+  size_t cap_sim = 0;
   // small batches of the host-pointer entry points: one pinned, device-mapped buffer the kernel
   // reads and writes in place (no copy launches; tci_ss_batch)
   char* h_io = nullptr;
@@ -410,7 +412,7 @@ int tci_destroy(tci_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (void* q : {(void*)ctx->dbuf, (void*)ctx->d_theta, (void*)ctx->d_cell, (void*)ctx->d_active,
-                  (void*)ctx->d_out0, (void*)ctx->d_out1})
+                  (void*)ctx->d_out0, (void*)ctx->d_out1, (void*)ctx->d_sim})
     if (q) (void)hipFree(q);
   if (ctx->h_io) (void)hipHostFree(ctx->h_io);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -518,6 +520,90 @@ int tci_forward(tci_ctx* ctx, const double* theta, int64_t ld_theta, const int32
   TCI_HIP(ctx, hipMemcpyAsync(ms2_out, ctx->d_out0, nout * sizeof(double), hipMemcpyDeviceToHost, st));
   TCI_HIP(ctx, hipMemcpyAsync(pp7_out, ctx->d_out1, nout * sizeof(double), hipMemcpyDeviceToHost, st));
   TCI_HIP(ctx, hipStreamSynchronize(st));
+  return TCI_OK;
+}
+
+int tci_predict_defaults(tci_predict_options* o) {
+  if (!o) return TCI_EINVAL;
+  o->grid_mode = TCI_GRID_RAW;  // the plot call's grid (TranscriptionCycleMCMC.m:307-309)
+  o->scratch_bytes = 0;
+  return TCI_OK;
+}
+
+int tci_predict(tci_ctx* ctx, const tci_predict_options* opt, const double* theta, int64_t ld_theta,
+                const int32_t* cell_id, int64_t n_sel, int64_t S, const double* probs, int32_t nq, double* ms2_q,
+                double* pp7_q, int64_t ld_out) {
+  if (!ctx) return TCI_EINVAL;
+  tci_predict_options o;
+  tci_predict_defaults(&o);
+  if (opt) o = *opt;
+  // ---- every check comes before any device work
+  if (o.grid_mode != TCI_GRID_INTERP && o.grid_mode != TCI_GRID_RAW)
+    return fail(ctx, TCI_EINVAL, "tci_predict: grid_mode must be TCI_GRID_INTERP or TCI_GRID_RAW");
+  if (o.scratch_bytes < 0) return fail(ctx, TCI_EINVAL, "tci_predict: scratch_bytes must be >= 0");
+  if (S < 1 || S > 4096) return fail(ctx, TCI_EINVAL, "tci_predict: S=" + std::to_string(S) + " must be in [1, 4096]");
+  if (nq < 1 || nq > 16) return fail(ctx, TCI_EINVAL, "tci_predict: nq=" + std::to_string(nq) + " must be in [1, 16]");
+  if (!probs) return fail(ctx, TCI_EINVAL, "tci_predict: probs is NULL");
+  for (int32_t q = 0; q < nq; ++q)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+      return fail(ctx, TCI_EINVAL, "tci_predict: probs[" + std::to_string(q) + "] must be finite and in [0, 1]");
+  if (n_sel < 0 || (n_sel > 0 && (!theta || !cell_id || !ms2_q || !pp7_q)))
+    return fail(ctx, TCI_EINVAL, "tci_predict: null pointer or negative n_sel");
+  if (n_sel == 0) return TCI_OK;
+  int rc = check_rows(ctx, ld_theta, cell_id, n_sel);
+  if (rc != TCI_OK) return rc;
+  for (int64_t k = 0; k < n_sel; ++k)
+    if (ld_out < ctx->meta[(size_t)cell_id[k]].n) return fail(ctx, TCI_ERANGE, "tci_predict: ld_out shorter than a cell");
+  if (ld_theta > ((int64_t)1 << 24) || ld_out > ((int64_t)1 << 24))
+    return fail(ctx, TCI_ERANGE, "tci_predict: ld_theta / ld_out above 2^24");
+  const int64_t cap = o.scratch_bytes > 0 ? o.scratch_bytes : (int64_t)1 << 30;
+  const int64_t per_cell = 2 * S * ld_out * (int64_t)sizeof(double);  // <= 2^41
+  if (per_cell > cap)
+    return fail(ctx, TCI_EINVAL, "tci_predict: one cell needs " + std::to_string(per_cell) +
+                                     " bytes of scratch (2 x S x ld_out doubles), scratch_bytes allows " +
+                                     std::to_string(cap));
+  int64_t chunk = 0;
+  if (tci::quantile_max_cells(S, ld_out, &chunk) != TCI_OK)
+    return fail(ctx, TCI_EINVAL, "tci_predict: S x ld_out too large for one launch");
+  chunk = std::min(std::min(chunk, cap / per_cell), n_sel);  // whole cells per chunk, at least one
+  std::vector<int32_t> row_cell;
+  try {
+    row_cell.resize((size_t)(chunk * S));
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, "tci_predict: host allocation failed");
+  }
+
+  // ---- device work: per chunk, the forward launch into the scratch, then the quantile reduction
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t rows_max = (size_t)(chunk * S), nsim = rows_max * (size_t)ld_out;
+  const size_t nqo_max = (size_t)chunk * (size_t)nq * (size_t)ld_out;
+  if ((rc = ensure(ctx, &ctx->d_theta, &ctx->cap_theta, rows_max * (size_t)ld_theta)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_cell, &ctx->cap_cell, rows_max)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_sim, &ctx->cap_sim, 2 * nsim)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_out0, &ctx->cap_out0, nqo_max)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_out1, &ctx->cap_out1, nqo_max)) != TCI_OK) return rc;
+  hipStream_t st = ctx->stream;
+  const int mode = o.grid_mode == TCI_GRID_RAW ? tci::MODE_FWD_RAW : tci::MODE_FWD_INTERP;
+  for (int64_t k0 = 0; k0 < n_sel; k0 += chunk) {
+    const int64_t nc = std::min(chunk, n_sel - k0), B = nc * S;
+    for (int64_t k = 0; k < nc; ++k) std::fill_n(row_cell.begin() + k * S, S, cell_id[k0 + k]);
+    const size_t nqo = (size_t)nc * (size_t)nq * (size_t)ld_out;
+    double* sim0 = ctx->d_sim;
+    double* sim1 = ctx->d_sim + (size_t)B * (size_t)ld_out;
+    TCI_HIP(ctx, hipMemcpyAsync(ctx->d_theta, theta + (size_t)k0 * (size_t)S * (size_t)ld_theta,
+                                (size_t)B * (size_t)ld_theta * sizeof(double), hipMemcpyHostToDevice, st));
+    TCI_HIP(ctx, hipMemcpyAsync(ctx->d_cell, row_cell.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = run(ctx, mode, ctx->d_theta, ld_theta, ctx->d_cell, nullptr, B, sim0, sim1, ld_out, (void*)st)) != TCI_OK)
+      return rc;
+    rc = tci::launch_quantile(ctx->kp, ctx->d_cell, sim0, sim1, nc, S, ld_out, probs, nq, ctx->d_out0, ctx->d_out1,
+                              (void*)st);
+    if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "tci_predict: quantile kernel launch");
+    if (rc != TCI_OK) return fail(ctx, rc, "tci_predict: the quantile kernel's tile does not fit a CU's LDS or the grid");
+    const size_t oo = (size_t)k0 * (size_t)nq * (size_t)ld_out;
+    TCI_HIP(ctx, hipMemcpyAsync(ms2_q + oo, ctx->d_out0, nqo * sizeof(double), hipMemcpyDeviceToHost, st));
+    TCI_HIP(ctx, hipMemcpyAsync(pp7_q + oo, ctx->d_out1, nqo * sizeof(double), hipMemcpyDeviceToHost, st));
+    TCI_HIP(ctx, hipStreamSynchronize(st));  // row_cell and the staging buffers are reused by the next chunk
+  }
   return TCI_OK;
 }
 

@@ -81,4 +81,14 @@ int launch(const KParams& kp, int rpl, int mode, const double* theta, int64_t ld
            const int32_t* cell_id, const uint8_t* active, int64_t B, double* out0, double* out1,
            int64_t ld_out, void* stream);
 
+// Quantiles over samples (tci_predict.hip, k_quantile). sim0/sim1: the forward launch's MS2/PP7 rows,
+// S consecutive rows of ld_out per selected cell; row_cell: the forward launch's cell id per row;
+// out0/out1: [n_sel * nq][ld_out], entries past a cell's N are NaN. probs are host values in [0, 1].
+// TCI_EINVAL when the launch would not fit (grid or LDS), TCI_EHIP on a HIP error.
+int launch_quantile(const KParams& kp, const int32_t* row_cell, const double* sim0, const double* sim1, int64_t n_sel,
+                    int64_t S, int64_t ld_out, const double* probs, int32_t nq, double* out0, double* out1,
+                    void* stream);
+// The most selected cells one forward + quantile launch pair takes (grid limits).
+int quantile_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
+
 }  // namespace tci

@@ -114,6 +114,45 @@ class Likelihood:
                                           _lib.ptr(ms2, _lib._dp), _lib.ptr(pp7, _lib._dp), ld_out))
         return ms2, pp7
 
+    def predict(self, theta: np.ndarray, cell_id: Sequence[int], probs=(0.025, 0.5, 0.975), grid: str = "raw",
+                scratch_bytes: int = 0):
+        """Posterior predictive bands (mcmcstat's ``mcmcpred`` / ``plims``) reduced on the device
+        (``tci_predict``): ``theta`` is ``[n_sel, S, ld]``, S posterior samples of cell ``cell_id[k]``
+        each. Returns ``ms2_q, pp7_q`` shaped ``[n_sel, nq, max N]``: at every acquisition time the
+        ``probs`` quantiles over the S simulated values, ``interp1(sort(x), (S-1)*p+1)`` with NaN
+        sorted last; NaN past a cell's N. ``scratch_bytes``: cap on the device scratch holding the
+        simulated rows (0 = 1 GiB); beyond it whole cells go in chunks, with the same results."""
+        if grid not in ("interp", "raw"):
+            raise ValueError(f"grid must be 'raw' or 'interp', got {grid!r}")
+        theta = np.ascontiguousarray(theta, np.float64)
+        if theta.ndim != 3:
+            raise ValueError("theta must be [n_sel, S, ld]: S posterior samples per selected cell")
+        cid = np.ascontiguousarray(cell_id, np.int32)
+        n_sel, S, ld = theta.shape
+        if cid.shape != (n_sel,):
+            raise ValueError("cell_id must have one entry per selected cell (theta.shape[0])")
+        pr = np.ascontiguousarray(np.atleast_1d(probs), np.float64)
+        if pr.ndim != 1 or not 1 <= len(pr) <= 16:
+            raise ValueError("probs must hold 1 to 16 probabilities")
+        if not np.all((pr >= 0) & (pr <= 1)):
+            raise ValueError("probs must be finite and in [0, 1]")
+        if not 1 <= S <= 4096:
+            raise ValueError(f"S = theta.shape[1] = {S} must be in [1, 4096]")
+        if int(scratch_bytes) < 0:
+            raise ValueError("scratch_bytes must be >= 0")
+        if n_sel and (cid.min() < 0 or cid.max() >= len(self.lengths)):
+            raise ValueError("cell_id out of range")
+        ld_out = int(self.lengths[cid].max()) if n_sel else 1
+        nq = len(pr)
+        ms2 = np.full((n_sel, nq, ld_out), np.nan)
+        pp7 = np.full((n_sel, nq, ld_out), np.nan)
+        opt = _lib.tci_predict_options({"interp": _lib.TCI_GRID_INTERP, "raw": _lib.TCI_GRID_RAW}[grid],
+                                       int(scratch_bytes))
+        self._check(self._lib.tci_predict(self._h, C.byref(opt), _lib.ptr(theta, _lib._dp), ld,
+                                          _lib.ptr(cid, _lib._i32p), n_sel, S, _lib.ptr(pr, _lib._dp), nq,
+                                          _lib.ptr(ms2, _lib._dp), _lib.ptr(pp7, _lib._dp), ld_out))
+        return ms2, pp7
+
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:
         """Launch on device tensors already resident in HBM (torch tensors or raw pointers):

@@ -35,6 +35,7 @@ RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_
 CHAIN_FIELDS = ("v_chain", "ton_chain", "A_chain", "tau_chain", "MS2_basal_chain", "PP7_basal_chain", "R_chain",
                 "dR_chain", "s2chain")  # :149-150
 PLOT_FIELDS = ("t_plot", "MS2_plot", "PP7_plot", "simMS2", "simPP7")  # :156-157
+PRED_FIELDS = ("predMS2", "predPP7", "pred_probs")  # added to MCMCplot by :func:`predict`
 THETA_INDEX = {"v": 0, "tau": 1, "ton": 2, "MS2_basal": 3, "PP7_basal": 4, "A": 5, "R": 6}
 
 
@@ -320,6 +321,72 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
 
 
 # ---------------------------------------------------------------------------
+# Posterior predictive envelopes (mcmcstat's mcmcpred on the fit's chain)
+# ---------------------------------------------------------------------------
+
+
+def predict_rows(rows: int, nsample: int) -> np.ndarray:
+    """Indices of the chain rows :func:`predict` simulates: all of them when there are fewer than
+    ``nsample``, else ``round(linspace(0, rows-1, nsample))``."""
+    rows, nsample = int(rows), int(nsample)
+    if nsample < 1:
+        raise ValueError("nsample must be >= 1")
+    if rows < nsample:
+        return np.arange(rows, dtype=np.int64)
+    return np.round(np.linspace(0, rows - 1, nsample)).astype(np.int64)
+
+
+def chain_theta(chain: Mapping, n: int, idx: np.ndarray) -> np.ndarray:
+    """Rows ``idx`` of one ``MCMCchain`` entry as theta rows in the ABI order
+    ``[v, tau, ton, MS2_basal, PP7_basal, A, R, dR_1 .. dR_n]`` (include/tci.h)."""
+    th = np.zeros((len(idx), 7 + n))
+    for name, col in THETA_INDEX.items():
+        th[:, col] = np.asarray(chain[name + "_chain"], np.float64).reshape(-1)[idx]
+    th[:, 7:] = np.asarray(chain["dR_chain"], np.float64).reshape(-1, n)[idx]
+    return th
+
+
+def predict(lk, fit_result: FitResult, nsample: int = 500, probs=(0.025, 0.5, 0.975), grid: str = "raw",
+            cell_offset: int = 0, scratch_bytes: int = 0) -> FitResult:
+    """Predictive bands of every fitted cell, as mcmcstat's ``mcmcpred`` + ``mcmcpredplot`` give
+    them: the forward model at ``nsample`` posterior samples of the cell's chain and, at every
+    acquisition time, the ``probs`` quantiles of the simulated MS2 and PP7 signals (``plims``), all on
+    the device (``Likelihood.predict``). Adds ``predMS2`` and ``predPP7`` (nq x N) and ``pred_probs`` to
+    each ``MCMCplot`` entry of ``fit_result`` and returns it.
+
+    The samples are the post-burn-in rows kept in ``MCMCchain`` (fit with ``thin > 0``). mcmcpred
+    draws ``nsample`` chain rows at random; here the choice is deterministic: every row when a cell
+    has fewer than ``nsample``, else rows ``round(linspace(0, rows-1, nsample))``, so a prediction
+    can be reproduced from the result file alone. ``nsample`` is at most 4096. Observation-noise bands
+    (mcmcpred's ``obslims``) are not computed. ``cell_offset``: as in :func:`fit`."""
+    if not fit_result.MCMCchain or any(not c or np.size(c.get("v_chain", ())) == 0 for c in fit_result.MCMCchain):
+        raise ValueError("predict needs the fit's chain rows and this fit kept none: run fit(..., thin=k) with "
+                         "k > 0 and n_burn <= n_steps")
+    pr = np.ascontiguousarray(np.atleast_1d(probs), np.float64)
+    cl: Cells = lk.cells
+    groups: Dict[int, List[int]] = {}
+    thetas = []
+    for k, ch in enumerate(fit_result.MCMCchain):
+        c = int(fit_result.cell_index[k]) - int(cell_offset)
+        n = int(cl.lengths[c])
+        th = chain_theta(ch, n, predict_rows(np.size(ch["v_chain"]), nsample))
+        thetas.append(th)
+        groups.setdefault(len(th), []).append(k)
+    for S, ks in groups.items():   # one device call per distinct sample count (a fit has one)
+        ld = max(thetas[k].shape[1] for k in ks)
+        theta = np.zeros((len(ks), S, ld))
+        for i, k in enumerate(ks):
+            theta[i, :, :thetas[k].shape[1]] = thetas[k]
+        cid = np.array([int(fit_result.cell_index[k]) - int(cell_offset) for k in ks], np.int32)
+        ms2_q, pp7_q = lk.predict(theta, cid, probs=pr, grid=grid, scratch_bytes=scratch_bytes)
+        for i, k in enumerate(ks):
+            n = thetas[k].shape[1] - 7
+            fit_result.MCMCplot[k].update(predMS2=ms2_q[i, :, :n].copy(), predPP7=pp7_q[i, :, :n].copy(),
+                                          pred_probs=pr.copy())
+    return fit_result
+
+
+# ---------------------------------------------------------------------------
 # Result files (TranscriptionCycleMCMC.m:371-378)
 # ---------------------------------------------------------------------------
 
@@ -343,8 +410,10 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
 
     date = date or datetime.date.today().strftime("%d-%b-%Y")
     base = os.path.join(save_loc, f"{date}-{fit_result.DatasetName}")
+    # the predictive bands only after predict(): a fit without them writes the same file as before
+    plot_fields = PLOT_FIELDS + (PRED_FIELDS if any("predMS2" in p for p in fit_result.MCMCplot) else ())
     sio.savemat(base + ".mat", {"MCMCresults": _struct_array(fit_result.MCMCresults, RESULT_FIELDS),
-                                "MCMCplot": _struct_array(fit_result.MCMCplot, PLOT_FIELDS),
+                                "MCMCplot": _struct_array(fit_result.MCMCplot, plot_fields),
                                 "DatasetName": fit_result.DatasetName})
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))
