@@ -719,13 +719,61 @@ def test_gpu_chains_follow_the_cpu_restatement(lk, c_oracle, construct, engine):
 #   long:    N = 210, P = 217 > 208 -- the generic adaptation kernel k_adapt_gt;
 #   mid:     N = 145 / 160 / 180 (P = 152 / 167 / 187: 10, 11 and 12 tiles per dimension), the tile
 #            ownership maps of k_adapt_mfma<8, 13> no BASELINE config reaches (tci_adapt_map.h).
+#   short:   N = 2 / 9 / 10 / 40 / 65 (P = 9 / 16 / 17 / 47 / 72): an RPL = 1 context (k_chain<1, 1>,
+#            k_walk<1, 1>), one to five tiles of k_adapt_mfma<8, 9, 6, 4>, a full last tile (P = 16) and
+#            a one-row last tile (P = 17);
+#   edge144: N = 121 / 122 / 137 (P = 128 / 129 / 144): the largest P of k_adapt_mfma<8, 9, 6, 4>;
+#   edge208: N = 138 / 201 (P = 145 / 208): the smallest and the largest P of k_adapt_mfma<8, 13, 12>;
+#   edge209: N = 202 (P = 209): the first P of k_adapt_gt;
+#   seg3 / seg4 at N = 40 (RPL = 1) and N = 100 (RPL = 2): the 3- and 4-segment constructs of
+#            test_multi_segment_constructs_vs_oracle -- k_chain<RPL, 3|4>, k_walk<RPL, 3|4> and the
+#            batched engine's tci_cohort_kernel<RPL, 3|4, SS>.
+# The new shapes hold two cells per length.
 RESTATEMENT_SHAPES = {
     "config4": (24, 200, "builtin", 20201028),
     "config5": (16, 200, "two_segment", 20201029),
     "long": (8, 210, "builtin", 20201030),
     "mid": (4, (145, 160, 180), "builtin", 20201031),
+    "short": (2, (2, 9, 10, 40, 65), "builtin", 20201032),
+    "edge144": (2, (121, 122, 137), "builtin", 20201033),
+    "edge208": (2, (138, 201), "builtin", 20201034),
+    "edge209": (2, (202,), "builtin", 20201035),
+    "seg3_rpl1": (2, 40, "seg3", 20201036),
+    "seg3_rpl2": (2, 100, "seg3", 20201037),
+    "seg4_rpl1": (2, 40, "seg4", 20201038),
+    "seg4_rpl2": (2, 100, "seg4", 20201039),
+}
+# shape -> (largest P, rows per lane of the context, the adaptation kernel dram_launch_adapt picks)
+RESTATEMENT_EXPECT = {
+    "config4": (207, 4, "mfma<8,13,12>"), "config5": (207, 4, "mfma<8,13,12>"), "long": (217, 4, "gt"),
+    "mid": (187, 4, "mfma<8,13,12>"), "short": (72, 1, "mfma<8,9,6,4>"), "edge144": (144, 4, "mfma<8,9,6,4>"),
+    "edge208": (208, 4, "mfma<8,13,12>"), "edge209": (209, 4, "gt"), "seg3_rpl1": (47, 1, "mfma<8,9,6,4>"),
+    "seg3_rpl2": (107, 2, "mfma<8,9,6,4>"), "seg4_rpl1": (47, 1, "mfma<8,9,6,4>"),
+    "seg4_rpl2": (107, 2, "mfma<8,9,6,4>"),
 }
 _restatement_cache = {}
+
+
+def _adapt_kernel(pmax):
+    """dram_launch_adapt's rule (tci_dram.hip), from the largest P of the run."""
+    if pmax <= 16 * 9:
+        return "mfma<8,9,6,4>"
+    if pmax <= 16 * 13 and pmax <= 208:  # kAdaptGtFrom
+        return "mfma<8,13,12>"
+    return "gt"
+
+
+def _restatement_construct(cname):
+    from transcriptioncycleinference_amd.construct import Construct, builtin_construct, long_two_loop_construct
+
+    if cname == "builtin":
+        return builtin_construct("P2P-MS2v5-LacZ-PP7v4")
+    if cname == "two_segment":
+        return long_two_loop_construct()
+    nseg = {"seg3": 3, "seg4": 4}[cname]  # as test_multi_segment_constructs_vs_oracle builds them
+    a = np.linspace(0.05, 9.0, nseg)
+    return Construct(11.0, list(a), list(a + 0.8), [24.0, 12.0, 6.0, 24.0][:nseg],
+                     list(a + 0.3), list(a + 1.9), [24.0] * nseg, cname)
 
 
 def _restatement_case(shape, c_oracle):
@@ -734,12 +782,11 @@ def _restatement_case(shape, c_oracle):
     if shape in _restatement_cache:
         return _restatement_cache[shape]
     from transcriptioncycleinference_amd import Likelihood, from_lists
-    from transcriptioncycleinference_amd.construct import builtin_construct, long_two_loop_construct
     from transcriptioncycleinference_amd.data import synthetic_cells
     from transcriptioncycleinference_amd.mcmc import DramOptions, plan_fit
 
     n_cells, n_points, cname, seed = RESTATEMENT_SHAPES[shape]
-    cs = builtin_construct("P2P-MS2v5-LacZ-PP7v4") if cname == "builtin" else long_two_loop_construct()
+    cs = _restatement_construct(cname)
 
     def fwd(times, theta):
         nan = [np.full(len(t), np.nan) for t in times]
@@ -773,19 +820,32 @@ def test_gpu_chains_follow_the_cpu_restatement_at_config_shapes(c_oracle, shape,
     (TranscriptionCycleMCMC.m:263-273): 700 steps, burn-in scaling at rows 100-300, then four covariance
     updates (rows 400-700) on the P <= 208 matrix-core adaptation (k_adapt_mfma<8, 13>) or, for P = 217,
     on k_adapt_gt, and on cells of 10-12 tiles per dimension (the "mid" shape); every engine. Same accept / reject decision at every step; rows, s2chain, summaries
-    and the final proposal factor R within 1e-9."""
+    and the final proposal factor R within 1e-9. The short / edge / seg shapes (RESTATEMENT_SHAPES) put
+    the in-kernel evaluation on RPL = 1 and on 3 and 4 segments, and the adaptation on each side of its
+    two kernel switches (P = 144 | 145, 208 | 209), on one tile, a full last tile and a one-row last tile."""
     from transcriptioncycleinference_amd import Likelihood
     from transcriptioncycleinference_amd.mcmc import dram_run
 
     cells, cs, plan, o, keys, c = _restatement_case(shape, c_oracle)
     o = dataclasses.replace(o, engine=engine)
     with Likelihood(cells, cs, device=0) as L:
+        rpl = L.info["rows_per_lane"]
         g = dram_run(L, np.array(plan.cells, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu,
                      plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys, want_qcov=True)
     n = cells.lengths[plan.cells]
-    assert int(7 + n.max()) == {"config4": 207, "config5": 207, "long": 217, "mid": 187}[shape]
+    pmax, want_rpl, want_kernel = RESTATEMENT_EXPECT[shape]
+    assert int(7 + n.max()) == pmax
+    assert rpl == want_rpl
+    assert _adapt_kernel(int(7 + n.max())) == want_kernel
     if shape == "mid":
         assert sorted(set(((7 + n + 15) // 16).tolist())) == [10, 11, 12]
+    if shape == "short":  # P = 9, 16, 17, 47, 72: one to five tiles, a full and a one-row last tile
+        assert sorted(set((7 + n).tolist())) == [9, 16, 17, 47, 72]
+        assert sorted(set(((7 + n + 15) // 16).tolist())) == [1, 2, 3, 5]
+    if shape == "edge144":
+        assert sorted(set((7 + n).tolist())) == [128, 129, 144]
+    if shape == "edge208":
+        assert sorted(set((7 + n).tolist())) == [145, 208]
     for k in range(len(plan.cells)):
         P = 7 + int(n[k])
         G, Cc = g.chain[:, k, :P], c["chain"][:, k, :P]

@@ -203,3 +203,39 @@ def test_oracles_agree_on_random_theta(n, construct, c_oracle):
     d = {"xdata": t, "ydata": np.concatenate([y1, y2])}
     for i, r in enumerate(rows):
         assert ss[i] == O.sum_of_squares(construct, d, r)
+
+
+@pytest.mark.parametrize("cname", ["two_segment", "seg3", "seg4"])
+@pytest.mark.parametrize("n", [10, 65, 130])
+def test_oracles_agree_on_multi_segment_constructs(n, cname, c_oracle):
+    """The C oracle's multi-segment rows -- what tests/test_variant_matrix_gpu.py trusts -- pinned by the
+    independent numpy restatement (the matrix form of GetFluorFromPolPos.m:47-70, the basal floor inside
+    the segment loop): SS and both forward modes, bit for bit as for the built-in construct, on random
+    rows, the edge rows and the rows that put a position P_m on a threshold of every segment
+    (tests/variant_rows.py families a, b, c)."""
+    import variant_rows as VR
+
+    cs = VR.matrix_constructs()[cname]
+    ocs = VR.oracle_construct(cs)
+    rng = np.random.default_rng(7 * n + cs.n_seg)
+    (t, y1, y2), = VR.synthetic_cell_list(rng, n, n_cells=1, nan_fraction=0.3)
+    rows, _ = VR.random_rows(rng, n, 1, count=6)
+    rows += VR.edge_rows(t)
+    # the gene end L0 + tau*v needs m*d > tau: 9 steps of ~0.25 reach it only with a short dwell
+    rc, _, lanes, _, _ = VR.threshold_rows(cs, [t], tau=0.5 if n == 10 else 2.0)
+    assert len(rc) >= 8 and set(lanes) == set(range(1 + 4 * cs.n_seg))
+    rows += rc
+    off = np.array([0, n])
+    ss, st = c_oracle.ss_batch(off, t, y1, y2, ocs, pack(rows), np.zeros(len(rows), np.int32))
+    assert np.all(st == 0)
+    d = {"xdata": t, "ydata": np.concatenate([y1, y2])}
+    for i, r in enumerate(rows):
+        assert ss[i] == O.sum_of_squares(ocs, d, r), i
+        m, p = c_oracle.forward(t, ocs, r, mode=0)
+        mn, pn = O.forward_raw(ocs, t, r)
+        np.testing.assert_array_equal(m, mn, err_msg=f"raw ms2 row {i}")
+        np.testing.assert_array_equal(p, pn, err_msg=f"raw pp7 row {i}")
+        m, p = c_oracle.forward(t, ocs, r, mode=1)
+        mn, pn = O.forward_interp(ocs, t, r)
+        np.testing.assert_array_equal(m, mn, err_msg=f"interp ms2 row {i}")
+        np.testing.assert_array_equal(p, pn, err_msg=f"interp pp7 row {i}")

@@ -273,7 +273,12 @@ __global__ __launch_bounds__(64) void tci_tile_kernel(const KParams kp, const do
   const double L = kp.L0 + tau * v;                 // GetFluorFromPolPos.m:19-20, no FMA
   const double pstop = L > kp.emax ? L : kp.emax;  // f(p) == 0 for every p >= pstop
 
-  bool fast = MODE != MODE_FWD_RAW && !(kp.force_exact & 2);
+  // Only the SS takes the O(1) row sums here. They place a cohort at P_m = m * vd0 where the reference
+  // sums v*dt forward; the two differ by up to ~m^2 u v d (eval_wave's eps), which is inside the SS's
+  // 1e-10 but, past 512 steps, no longer inside the 1e-12 the forward rows keep: a row just above its
+  // basal floor came out 1.9e-12 off at N = 1025, v = 0.056. Forward rows of long cells
+  // take the exact sweep (the plot / predictive path, never the sampler's).
+  bool fast = MODE == MODE_SS && !(kp.force_exact & 2);
   const double vd0 = v * cm.d;
   Cuts<NSEG> cu;
   // ---- distance cuts over m = 1..S and their exactness proof (as eval_wave)
