@@ -245,6 +245,58 @@ int tci_predict(tci_ctx* ctx, const tci_predict_options* opt, const double* thet
                 const int32_t* cell_id, int64_t n_sel, int64_t S, const double* probs, int32_t nq,
                 double* ms2_q, double* pp7_q, int64_t ld_out);
 
+/* ---- Chain convergence diagnostics (mcmcstat's chainstats) -----------------------------------
+ * Per column x[0..n) (one parameter of one chain over the n diagnostic rows; a chain's s2 is one more
+ * column), all in FP64, reduced on the device so that only a few vectors per chain cross the bus:
+ *   mcerr   b = max(10, floor(n/20)), nb = floor(n/b) batches from row 0 (the rows past nb*b left out),
+ *           s = sqrt(b * sum_i (ybar_i - xbar)^2 / (nb - 1)) with xbar the mean of all n rows;
+ *           mcerr = s / sqrt(n) (bmstd / sqrt(n)). NaN for n < 20.
+ *   tau     Sokal's adaptive window (iact): y = x - xbar, c(k) = sum_t y[t] y[(t+k) mod n] (circular, what
+ *           mcmcstat's FFT computes, here summed lag by lag with an early exit); c(0) == 0: tau = 0,
+ *           window = 0; else S = -1/3 and for i = 1, 2, ..: S += c(i-1)/c(0) - 1/6, and at the first
+ *           S < 0: tau = 2 (S + (i-1)/6), window = i. No crossing within max_lag lags: tau = +Inf,
+ *           window = max_lag.
+ *   geweke  segment A = the first floor(0.1 n) rows, B = the last floor(0.5 n);
+ *           z = (mean_A - mean_B) / sqrt(s_A^2/n_A + s_B^2/n_B), s_A and s_B the batch-means s above of each
+ *           segment (b from the segment's length), p = erfc(|z| / sqrt(2)). NaN when a segment has fewer
+ *           than 20 rows (n < 200); a constant column gives 0/0 = NaN. mcmcstat estimates the same
+ *           spectral density at zero with a Welch periodogram; batch means are used here because this
+ *           variant is pinned by its formula alone.
+ * A non-finite entry makes every statistic of its column NaN (its window -1). */
+typedef struct {
+  int64_t max_lag;  /* most lags iact may use; 0 = n (mcmcstat's rule). Bounds the O(n * window) work */
+} tci_chainstats_options;
+
+/* Host buffers (any may be NULL). Per-chain vectors have stride ld; padding (j >= npar of the chain) is
+ * NaN, its window -1. */
+typedef struct {
+  double *mcerr, *tau, *geweke_z, *geweke_p;             /* [n_chains][ld] */
+  int32_t* tau_window;
+  double *s2_mcerr, *s2_tau, *s2_geweke_z, *s2_geweke_p; /* [n_chains]; NaN / -1 without an s2 chain */
+  int32_t* s2_tau_window;
+  int64_t n_rows;    /* written: rows the statistics used */
+  double kernel_ms;  /* written: device time of the statistics kernels (HIP events) */
+} tci_chainstats_outputs;
+
+int tci_chainstats_defaults(tci_chainstats_options* opt);
+
+/* The statistics of a chain already on the host (e.g. read back from a _RawChain file): chain is
+ * [n_rows][n_chains][ld], s2chain [n_rows][n_chains] or NULL, npar [n_chains] (NULL: ld for every chain;
+ * TCI_ERANGE outside [0, ld]). opt may be NULL (the defaults). TCI_EINVAL for n_rows < 1 or max_lag < 0,
+ * TCI_ENOMEM when the chain does not fit the device. */
+int tci_chainstats(tci_ctx* ctx, const tci_chainstats_options* opt, const double* chain, const double* s2chain,
+                   int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chainstats_outputs* out);
+
+/* tci_dram_run plus the statistics of the rows it kept, taken from the device chain before any copy:
+ * the kept rows (1, 1 + thin, ..) whose 1-based chain row is >= stats_from, for theta and for s2. The
+ * device chain exists for the statistics alone when out->chain is NULL (nothing of it is copied). sopt may
+ * be NULL. TCI_EINVAL when opt->thin == 0, when no kept row is in the range, or for max_lag < 0. Every
+ * engine gives the same chain bits, hence the same statistics bits. */
+int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                       const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                       const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                       tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -30,6 +30,10 @@ function [MCMCresults, MCMCplot, MCMCchain] = tci_fit(data, varargin)
 %        all cells. Needs 'thin' > 0. Where mcmcpred draws chain rows at random, the rows used here
 %        are round(linspace(1, rows, nsample)) of the post-burn-in rows kept (all of them when fewer),
 %        at most 4096.)
+%     'diagnostics' (0; 1 fills the fourth output MCMCdiag, one entry per fitted cell: mcmcstat's
+%        chainstats columns reduced on the device from the rows MCMCchain keeps -- mcerr_*, tau_* and
+%        geweke_p_* for v, ton, A, tau, MS2_basal, PP7_basal, R, dR (vectors) and s2, n_rows,
+%        ess_min = n_rows / max tau and cell_index; formulas in include/tci.h. Needs 'thin' > 0.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -56,6 +60,7 @@ p.addParameter('seed', 0);
 p.addParameter('engine', 'auto');
 p.addParameter('adapt_pmax', 0);
 p.addParameter('predict', 0);
+p.addParameter('diagnostics', 0);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -159,7 +164,15 @@ options = struct('nsimu', n_steps, 'burnintime', n_burn, 'adaptint', 100, 'metho
     'updatesigma', 1, 'verbosity', 0, 'stats_from', max(n_burn, 1), 'thin', o.thin, ...
     'seed', o.seed*1000003 + 20201028, 'engine', o.engine, 'adapt_pmax', o.adapt_pmax, ...
     'chain_keys', [setup.cellNum] - 1);
-if o.thin > 0
+MCMCdiag = struct([]);
+if o.diagnostics && o.thin <= 0
+    error('tci:diagnostics', 'the diagnostics need the kept chain rows: thin > 0');
+end
+if o.diagnostics
+    [results, chain, s2chain, ~, stats] = tci_mex('dram', h, 1:nc, X0, LB, UB, MU, SIG, J0, sigma2_0, options);
+    rows = 1 + o.thin*(0:size(chain, 3)-1);
+    sel = rows >= max(n_burn, 1);
+elseif o.thin > 0
     [results, chain, s2chain] = tci_mex('dram', h, 1:nc, X0, LB, UB, MU, SIG, J0, sigma2_0, options);  % :273
     rows = 1 + o.thin*(0:size(chain, 3)-1);         % chain rows kept: 1, 1+thin, ...
     sel = rows >= max(n_burn, 1);                   % chain(n_burn:end, :) (:276-283)
@@ -207,6 +220,24 @@ for k = 1:nc
         plotk.pred_probs = pred_probs;
     end
     MCMCplot(k) = plotk;
+    if o.diagnostics
+        names = {'v', 'ton', 'A', 'tau', 'MS2_basal', 'PP7_basal', 'R'};
+        col = [1 3 6 2 4 5 7];
+        src = {'mcerr', stats.mcerr, stats.s2_mcerr; 'tau', stats.tau, stats.s2_tau; ...
+               'geweke_p', stats.geweke_p, stats.s2_geweke_p};
+        dg = struct();
+        for q = 1:3
+            for w = 1:7
+                dg.([src{q, 1} '_' names{w}]) = src{q, 2}(col(w), k);
+            end
+            dg.([src{q, 1} '_dR']) = src{q, 2}(8:7+n, k)';
+            dg.([src{q, 1} '_s2']) = src{q, 3}(k);
+        end
+        dg.n_rows = stats.n_rows;
+        dg.ess_min = stats.n_rows / max(stats.tau(1:7+n, k));
+        dg.cell_index = setup(k).cellNum;
+        if isempty(MCMCdiag), MCMCdiag = dg; else, MCMCdiag(k) = dg; end
+    end
     if o.thin > 0
         c = reshape(chain(1:7+n, k, sel), 7+n, [])';   % rows x P
         MCMCchain(k) = struct('v_chain', c(:,1), 'ton_chain', c(:,3), 'A_chain', c(:,6), ...

@@ -42,6 +42,15 @@
 //          (:302-303), accept_rate, n_evals (1 x n) and elapsed_ms; chain: P x n x ceil(nsimu/thin);
 //          s2chain: n x ceil(nsimu/thin); R: P x P x n upper factors with R(:,:,k)'*R(:,:,k) the final
 //          proposal covariance of chain k (mcmcstat results.qcov).
+//   [results, chain, s2chain, R, stats] = tci_mex('dram', ...)
+//          a fifth output asks for the chain diagnostics (tci_dram_run_stats) of the kept rows at or past
+//          stats_from, reduced from the device chain; options.max_lag caps the lags of tau (0 = rows).
+//          stats: struct with mcerr, tau, tau_window, geweke_z, geweke_p (P x n; NaN and window -1 past a
+//          chain's 7 + N), s2_mcerr, s2_tau, s2_tau_window, s2_geweke_z, s2_geweke_p (1 x n), n_rows, kernel_ms.
+//   stats = tci_mex('chainstats', h, chain, s2chain, npar[, max_lag])
+//          the same diagnostics (mcmcstat's chainstats: batch-means error, Sokal's iact, Geweke; formulas
+//          in include/tci.h) of a chain held in MATLAB: chain is P x n x rows and s2chain n x rows (or []),
+//          as 'dram' returns them; npar: 1 x n real columns per chain (or []: P).
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -312,6 +321,48 @@ const double* chain_matrix(const mxArray* a, const char* what, size_t P, size_t 
   return mxGetPr(a);
 }
 
+// The statistics struct of 'chainstats' and of 'dram''s fifth output, written in place by the ABI: mcerr,
+// tau, geweke_z, geweke_p (P x n) and tau_window (P x n, as doubles; -1 = padding or a non-finite column),
+// the same five for s2 (1 x n, s2_ prefixed), n_rows and kernel_ms.
+struct StatsOut {
+  mxArray* res;
+  mxArray* a[8];
+  std::vector<int32_t> win, s2win;
+  size_t P, n;
+  tci_chainstats_outputs out;
+  StatsOut(size_t P_, size_t n_) : win(P_ * n_), s2win(n_), P(P_), n(n_) {
+    static const char* fields[] = {"mcerr", "tau", "geweke_z", "geweke_p", "s2_mcerr", "s2_tau", "s2_geweke_z",
+                                   "s2_geweke_p", "tau_window", "s2_tau_window", "n_rows", "kernel_ms"};
+    res = mxCreateStructMatrix(1, 1, 12, fields);
+    for (int k = 0; k < 8; ++k) {
+      a[k] = k < 4 ? mxCreateDoubleMatrix(P, n, mxREAL) : mxCreateDoubleMatrix(1, n, mxREAL);
+      mxSetField(res, 0, fields[k], a[k]);
+    }
+    memset(&out, 0, sizeof out);
+    out.mcerr = mxGetPr(a[0]);
+    out.tau = mxGetPr(a[1]);
+    out.geweke_z = mxGetPr(a[2]);
+    out.geweke_p = mxGetPr(a[3]);
+    out.s2_mcerr = mxGetPr(a[4]);
+    out.s2_tau = mxGetPr(a[5]);
+    out.s2_geweke_z = mxGetPr(a[6]);
+    out.s2_geweke_p = mxGetPr(a[7]);
+    out.tau_window = win.data();
+    out.s2_tau_window = s2win.data();
+  }
+  mxArray* finish() {
+    mxArray* w = mxCreateDoubleMatrix(P, n, mxREAL);
+    for (size_t i = 0; i < P * n; ++i) mxGetPr(w)[i] = (double)win[i];
+    mxArray* w2 = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t i = 0; i < n; ++i) mxGetPr(w2)[i] = (double)s2win[i];
+    mxSetField(res, 0, "tau_window", w);
+    mxSetField(res, 0, "s2_tau_window", w2);
+    mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+    mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+    return res;
+  }
+};
+
 void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (nrhs < 10 || nrhs > 11)
     mexErrMsgIdAndTxt("tci:arg", "tci_mex('dram', h, cells, X0, LB, UB, MU, SIG, J0, sigma2[, options])");
@@ -346,7 +397,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"nsimu", "burnintime", "adaptint", "method", "updatesigma", "drscale", "adascale",
                                   "qcovadj", "burnin_scale", "stats_from", "thin", "seed", "engine", "max_chunk",
-                                  "chain_keys", "adapt_pmax", "verbosity", "waitbar", "printint"};
+                                  "chain_keys", "adapt_pmax", "max_lag", "verbosity", "waitbar", "printint"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
       bool ok = false;
@@ -388,6 +439,10 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else mexErrMsgIdAndTxt("tci:opts", "options.engine must be 'auto', 'fused', 'walk' or 'batched'");
   opt.max_chunk = (int32_t)opt_int(o, "max_chunk", 0, 0);
   opt.adapt_pmax = opt_int(o, "adapt_pmax", 0, 0);
+  tci_chainstats_options sopt;
+  tci_chainstats_defaults(&sopt);
+  sopt.max_lag = opt_int(o, "max_lag", 0, 0);
+  const bool want_stats = nlhs >= 5;
   std::vector<int64_t> keys;
   if (const mxArray* k = o ? mxGetField(o, 0, "chain_keys") : nullptr) {
     const double* kv = doubles(k, (long long)n, "options.chain_keys");
@@ -436,8 +491,12 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     rbuf.resize(n * P * P);
     out.qcov_R = rbuf.data();
   }
-  const int rc = tci_dram_run(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5], s2v.data(),
-                              (int64_t)P, &out);
+  StatsOut so(want_stats ? P : 0, want_stats ? n : 0);
+  const int rc = want_stats ? tci_dram_run_stats(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
+                                                 in[5], s2v.data(), (int64_t)P, &out, &sopt, &so.out)
+                            : tci_dram_run(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
+                                           s2v.data(), (int64_t)P, &out);
+  if (rc != TCI_OK || !want_stats) mxDestroyArray(so.res);
   if (rc != TCI_OK) {
     mxDestroyArray(res);
     if (ch) mxDestroyArray(ch);
@@ -461,6 +520,52 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (size_t j = 0; j < P; ++j) r[k * P * P + j * P + i] = rbuf[k * P * P + i * P + j];
     plhs[3] = R;
   }
+  if (want_stats) plhs[4] = so.finish();
+}
+
+// ---- 'chainstats': chain diagnostics -----------------------------------------------------------
+
+void cmd_chainstats(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs < 5 || nrhs > 6) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chainstats', h, chain, s2chain, npar[, max_lag])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  const double* s2 = nullptr;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = no s2 chain
+    s2 = doubles(prhs[3], (long long)(n * rows), "s2chain");
+    if (n * rows > 1 && (mxGetNumberOfDimensions(prhs[3]) != 2 || mxGetM(prhs[3]) != n))
+      mexErrMsgIdAndTxt("tci:arg", "s2chain must be n x rows, as 'dram' returns it");
+  }
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[4]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[4], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  tci_chainstats_options opt;
+  tci_chainstats_defaults(&opt);
+  if (nrhs > 5) {
+    const double v = *doubles(prhs[5], 1, "max_lag");
+    if (!(v >= 0 && v <= 9.0e15) || v != (double)(int64_t)v) mexErrMsgIdAndTxt("tci:arg", "max_lag must be an integer >= 0");
+    opt.max_lag = (int64_t)v;
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  StatsOut so(P, n);
+  const int rc = tci_chainstats(ctx, &opt, X, s2, (int64_t)rows, (int64_t)n, (int64_t)P, npar.empty() ? nullptr : npar.data(),
+                                &so.out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(so.res);
+    check(ctx, rc, "tci_chainstats");
+  }
+  plhs[0] = so.finish();
 }
 
 }  // namespace
@@ -479,6 +584,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "forward") cmd_forward(nlhs, plhs, nrhs, prhs);
   else if (cmd == "dram") cmd_dram(nlhs, plhs, nrhs, prhs);
   else if (cmd == "predict") cmd_predict(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chainstats") cmd_chainstats(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

@@ -73,6 +73,16 @@ class tci_predict_options(C.Structure):
     _fields_ = [("grid_mode", C.c_int32), ("scratch_bytes", C.c_int64)]
 
 
+class tci_chainstats_options(C.Structure):
+    _fields_ = [("max_lag", C.c_int64)]
+
+
+class tci_chainstats_outputs(C.Structure):
+    _fields_ = [("mcerr", _dp), ("tau", _dp), ("geweke_z", _dp), ("geweke_p", _dp), ("tau_window", _i32p),
+                ("s2_mcerr", _dp), ("s2_tau", _dp), ("s2_geweke_z", _dp), ("s2_geweke_p", _dp),
+                ("s2_tau_window", _i32p), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -95,6 +105,12 @@ SIGNATURES = [
     ("tci_predict_defaults", C.c_int, [C.POINTER(tci_predict_options)]),
     ("tci_predict", C.c_int, [C.c_void_p, C.POINTER(tci_predict_options), _dp, C.c_int64, _i32p, C.c_int64, C.c_int64,
                               _dp, C.c_int32, _dp, _dp, C.c_int64]),
+    ("tci_chainstats_defaults", C.c_int, [C.POINTER(tci_chainstats_options)]),
+    ("tci_chainstats", C.c_int, [C.c_void_p, C.POINTER(tci_chainstats_options), _dp, _dp, C.c_int64, C.c_int64,
+                                 C.c_int64, _i32p, C.POINTER(tci_chainstats_outputs)]),
+    ("tci_dram_run_stats", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                     _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                     C.POINTER(tci_chainstats_options), C.POINTER(tci_chainstats_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

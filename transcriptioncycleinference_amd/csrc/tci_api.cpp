@@ -650,6 +650,59 @@ struct DevAllocs {
   }
 };
 
+// The statistics kernels on a device chain (launch_chainstats), timed with HIP events, and their results
+// scattered into the caller's host buffers (d_npar null: ld columns for every chain).
+int chainstats_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                      int64_t n_chains, int64_t ld, const int32_t* d_npar, int64_t max_lag, tci_chainstats_outputs* out) {
+  const size_t ldc = (size_t)ld + 1, plane = (size_t)n_chains * ldc;
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  double* d_stats = A.alloc<double>(5 * plane, &e);
+  if (e != hipSuccess) return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the statistics failed");
+  int32_t* d_win = A.alloc<int32_t>(plane, &e);
+  if (e != hipSuccess) return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the statistics failed");
+  std::vector<double> hs;
+  std::vector<int32_t> hw;
+  try {
+    hs.resize(4 * plane);
+    hw.resize(plane);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  hipStream_t s = ctx->stream;
+  hipEvent_t ev0, ev1;
+  TCI_HIP(ctx, hipEventCreate(&ev0));
+  TCI_HIP(ctx, hipEventCreate(&ev1));
+  TCI_HIP(ctx, hipEventRecord(ev0, s));
+  const int rc = tci::launch_chainstats(d_chain, d_s2, n_rows, n_chains, ld, d_npar, max_lag, d_stats, d_win, (void*)s);
+  hipError_t e1 = hipEventRecord(ev1, s);
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(hs.data(), d_stats, 4 * plane * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(hw.data(), d_win, plane * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  float ms = 0.f;
+  if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "chain statistics kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "chain statistics kernels");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain statistics copy");
+  double* dst[4] = {out->mcerr, out->tau, out->geweke_z, out->geweke_p};
+  double* dst2[4] = {out->s2_mcerr, out->s2_tau, out->s2_geweke_z, out->s2_geweke_p};
+  for (int64_t c = 0; c < n_chains; ++c) {
+    const size_t o = (size_t)c * ldc;
+    for (int k = 0; k < 4; ++k) {
+      if (dst[k]) std::memcpy(dst[k] + (size_t)c * (size_t)ld, hs.data() + (size_t)k * plane + o, (size_t)ld * sizeof(double));
+      if (dst2[k]) dst2[k][c] = hs[(size_t)k * plane + o + (size_t)ld];
+    }
+    if (out->tau_window) std::memcpy(out->tau_window + (size_t)c * (size_t)ld, hw.data() + o, (size_t)ld * sizeof(int32_t));
+    if (out->s2_tau_window) out->s2_tau_window[c] = hw[o + (size_t)ld];
+  }
+  out->n_rows = n_rows;
+  out->kernel_ms = ms;
+  return TCI_OK;
+}
+
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
 // -> [window records] -> [adapt] -> step + 1.
 int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& p, hipStream_t s, bool with_stats,
@@ -695,10 +748,15 @@ int tci_dram_defaults(tci_dram_options* o) {
   return TCI_OK;
 }
 
-int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
-                 const double* theta0, const double* lower, const double* upper, const double* prior_mu,
-                 const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
-                 tci_dram_outputs* out) {
+}  // extern "C"
+
+namespace {
+
+// tci_dram_run, and with sout the chain statistics of the kept rows (tci_dram_run_stats).
+int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                  const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                  const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                  tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout) {
   if (!ctx) return TCI_EINVAL;
   if (!opt || !out || n_chains <= 0 || !cell_id || !theta0 || !lower || !upper || !prior_mu || !prior_sig ||
       !qcov_diag || !sigma2_0)
@@ -709,6 +767,18 @@ int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, co
     return fail(ctx, TCI_EINVAL,
                 "tci_dram_run: bad options (n_steps >= 1, ntry in {1,2}, adaptint >= 0, engine in {0,1,2,3}, "
                 "max_chunk >= 0, 0 <= adapt_pmax <= 2055)");
+  // the statistics' rows: the kept rows k (chain row 1 + k * thin) from the first one at or past stats_from
+  const int64_t max_lag = sopt ? sopt->max_lag : 0;
+  int64_t stats_k0 = 0, stats_rows = 0;
+  if (sout) {
+    if (opt->thin <= 0)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: the statistics need the kept rows (thin >= 1)");
+    if (max_lag < 0) return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: max_lag must be >= 0");
+    const int64_t from = std::max<int64_t>(opt->stats_from, 1);
+    stats_k0 = (from - 1 + opt->thin - 1) / opt->thin;
+    stats_rows = (opt->n_steps + opt->thin - 1) / opt->thin - stats_k0;
+    if (stats_rows < 1) return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: no kept row at or past stats_from (n_rows < 1)");
+  }
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
   if (ld > TCI_MAX_POINTS + 7) return fail(ctx, TCI_ERANGE, "tci_dram_run: ld too large");
@@ -822,7 +892,17 @@ int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, co
   TCI_ALLOC(prof, int64_t, 32);
   TCI_HIP(ctx, hipMemsetAsync(st.prof, 0, 32 * sizeof(int64_t), ctx->stream));
 #endif
-  if (n_keep > 0 && (out->chain || out->s2chain)) {
+  if (n_keep > 0 && sout && !(out->chain || out->s2chain)) {
+    // the chain is kept on the device for the statistics alone: running out of memory is the caller's to handle
+    st.chain_out = A.alloc<double>((size_t)n_keep * n * L, &e);
+    if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, TCI_ENOMEM, "tci_dram_run_stats: the device chain (" +
+                                       std::to_string((size_t)n_keep * n * L * sizeof(double)) + " bytes) does not fit");
+    }
+    TCI_HIP(ctx, hipMemsetAsync(st.chain_out, 0, (size_t)n_keep * n * L * sizeof(double), ctx->stream));
+  } else if (n_keep > 0 && (out->chain || out->s2chain)) {
     TCI_ALLOC(chain_out, double, (size_t)n_keep * n * L);
     TCI_ALLOC(s2_out, double, (size_t)n_keep * n);
     // entries past a chain's P are never written: zero them so outputs are deterministic
@@ -1064,7 +1144,74 @@ int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, co
   }
   if (st.s2_out && out->s2chain)
     TCI_HIP(ctx, hipMemcpy(out->s2chain, st.s2_out, (size_t)n_keep * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (sout)  // the device chain's rows from the first one in the statistics range
+    return chainstats_device(ctx, "tci_dram_run_stats", st.chain_out + (size_t)stats_k0 * n * L,
+                             st.s2_out + (size_t)stats_k0 * n, stats_rows, n_chains, ld, st.npar, max_lag, sout);
   return TCI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                 const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                 const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                 tci_dram_outputs* out) {
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, nullptr, nullptr);
+}
+
+int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                       const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                       const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                       tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout) {
+  if (!ctx) return TCI_EINVAL;
+  if (!sout) return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: null statistics outputs");
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, sopt, sout);
+}
+
+int tci_chainstats_defaults(tci_chainstats_options* o) {
+  if (!o) return TCI_EINVAL;
+  o->max_lag = 0;  // n: mcmcstat's iact sums until Sokal's window closes
+  return TCI_OK;
+}
+
+int tci_chainstats(tci_ctx* ctx, const tci_chainstats_options* opt, const double* chain, const double* s2chain,
+                   int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chainstats_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  const int64_t max_lag = opt ? opt->max_lag : 0;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chainstats: null argument");
+  if (n_rows < 1) return fail(ctx, TCI_EINVAL, "tci_chainstats: n_rows must be >= 1");
+  if (max_lag < 0) return fail(ctx, TCI_EINVAL, "tci_chainstats: max_lag must be >= 0");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chainstats: n_chains and ld must be >= 1");
+  if (ld > ((int64_t)1 << 24) || n_rows > ((int64_t)1 << 30) || n_chains > ((int64_t)1 << 30))
+    return fail(ctx, TCI_ERANGE, "tci_chainstats: ld above 2^24, or n_rows or n_chains above 2^30");
+  if (npar)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (npar[c] < 0 || npar[c] > ld)
+        return fail(ctx, TCI_ERANGE, "tci_chainstats: npar[" + std::to_string(c) + "] outside [0, ld]");
+  const size_t per_row = (size_t)n_chains * (size_t)ld;
+  if (per_row > (((size_t)1 << 46) / sizeof(double)) / (size_t)n_rows)
+    return fail(ctx, TCI_ENOMEM, "tci_chainstats: the chain is larger than any device memory");
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t nch = (size_t)n_rows * per_row, ns2 = (size_t)n_rows * (size_t)n_chains;
+  double* d_chain = A.alloc<double>(nch, &e);
+  double* d_s2 = e == hipSuccess && s2chain ? A.alloc<double>(ns2, &e) : nullptr;
+  int32_t* d_npar = e == hipSuccess && npar ? A.alloc<int32_t>((size_t)n_chains, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chainstats: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return chainstats_device(ctx, "tci_chainstats", d_chain, d_s2, n_rows, n_chains, ld, d_npar, max_lag, out);
 }
 
 }  // extern "C"

@@ -91,4 +91,12 @@ int launch_quantile(const KParams& kp, const int32_t* row_cell, const double* si
 // The most selected cells one forward + quantile launch pair takes (grid limits).
 int quantile_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
 
+// Chain diagnostics (tci_chainstats.hip) of a device chain [n_rows][n_chains][ld] and, when s2 is not null,
+// of s2 [n_rows][n_chains] as column ld of every chain. npar (device, may be null = ld): columns j >= npar[c]
+// are padding. stats (device): [5][n_chains * (ld + 1)] doubles = mcerr, tau, Geweke z, Geweke p and the
+// column means; win (device): [n_chains * (ld + 1)] windows. Padding and non-finite columns: NaN and -1.
+// max_lag 0 = n_rows. Asynchronous on `stream`. TCI_EINVAL on a size the grid cannot take, TCI_EHIP on a HIP error.
+int launch_chainstats(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
+                      const int32_t* npar, int64_t max_lag, double* stats, int32_t* win, void* stream);
+
 }  // namespace tci

@@ -7,6 +7,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Optional, Sequence
 
 import numpy as np
@@ -14,6 +15,37 @@ import numpy as np
 from . import _lib
 from .construct import Construct, as_construct
 from .data import Cells
+
+
+@dataclasses.dataclass
+class ChainStats:
+    """Per-column chain diagnostics (``tci_chainstats_outputs``): arrays ``[n_chains, ld]`` for the
+    parameters and ``[n_chains]`` for s2."""
+
+    mcerr: np.ndarray
+    tau: np.ndarray
+    tau_window: np.ndarray
+    geweke_z: np.ndarray
+    geweke_p: np.ndarray
+    s2_mcerr: np.ndarray
+    s2_tau: np.ndarray
+    s2_tau_window: np.ndarray
+    s2_geweke_z: np.ndarray
+    s2_geweke_p: np.ndarray
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n: int, ld: int) -> "ChainStats":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        w = lambda *s: np.full(s, -1, np.int32)  # noqa: E731
+        return cls(d(n, ld), d(n, ld), w(n, ld), d(n, ld), d(n, ld), d(n), d(n), w(n), d(n), d(n))
+
+    def to_c(self) -> "_lib.tci_chainstats_outputs":
+        P, W = (lambda a: _lib.ptr(a, _lib._dp)), (lambda a: _lib.ptr(a, _lib._i32p))  # noqa: E731
+        return _lib.tci_chainstats_outputs(P(self.mcerr), P(self.tau), P(self.geweke_z), P(self.geweke_p),
+                                           W(self.tau_window), P(self.s2_mcerr), P(self.s2_tau), P(self.s2_geweke_z),
+                                           P(self.s2_geweke_p), W(self.s2_tau_window), 0, 0.0)
 
 
 class Likelihood:
@@ -152,6 +184,34 @@ class Likelihood:
                                           _lib.ptr(cid, _lib._i32p), n_sel, S, _lib.ptr(pr, _lib._dp), nq,
                                           _lib.ptr(ms2, _lib._dp), _lib.ptr(pp7, _lib._dp), ld_out))
         return ms2, pp7
+
+    def chainstats(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, max_lag: int = 0):
+        """Convergence diagnostics of a chain held on the host (mcmcstat's ``chainstats``), reduced
+        on the device (``tci_chainstats``; formulas in ``include/tci.h``). ``chain`` is
+        ``[rows, n_chains, ld]`` (a 2-D ``[rows, ld]`` array is one chain), ``s2chain`` ``[rows, n_chains]``
+        or None, ``npar`` the number of real columns per chain (None: ``ld``); ``max_lag``: most lags the
+        autocorrelation time may use (0 = rows). Returns a :class:`ChainStats`; padding is NaN
+        (window -1), and so is every statistic of a column holding a non-finite value."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = None
+        if s2chain is not None:
+            s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        st = ChainStats.empty(n, ld)
+        opt = _lib.tci_chainstats_options(int(max_lag))
+        out = st.to_c()
+        self._check(self._lib.tci_chainstats(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp),
+                                             rows, n, ld, _lib.ptr(npr, _lib._i32p), C.byref(out)))
+        st.n_rows, st.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return st
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
+from .likelihood import ChainStats
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -36,6 +37,10 @@ CHAIN_FIELDS = ("v_chain", "ton_chain", "A_chain", "tau_chain", "MS2_basal_chain
                 "dR_chain", "s2chain")  # :149-150
 PLOT_FIELDS = ("t_plot", "MS2_plot", "PP7_plot", "simMS2", "simPP7")  # :156-157
 PRED_FIELDS = ("predMS2", "predPP7", "pred_probs")  # added to MCMCplot by :func:`predict`
+_SCALARS = ("v", "ton", "A", "tau", "MS2_basal", "PP7_basal", "R")
+# MCMCdiag (fit(..., diagnostics=True)): chain diagnostics per fitted cell, mcmcstat's chainstats columns
+DIAG_FIELDS = (tuple(f"{s}_{n}" for s in ("mcerr", "tau", "geweke_p") for n in _SCALARS + ("dR", "s2"))
+               + ("n_rows", "ess_min", "cell_index"))
 THETA_INDEX = {"v": 0, "tau": 1, "ton": 2, "MS2_basal": 3, "PP7_basal": 4, "A": 5, "R": 6}
 
 
@@ -90,13 +95,18 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    stats: Optional[ChainStats] = None            # dram_run(stats=True): diagnostics of the kept rows
 
 
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
-             opts: DramOptions, want_qcov: bool = False, chain_keys=None) -> DramResult:
+             opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
+             max_lag: int = 0, want_chain: bool = True) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
-    RNG stream key per chain (default: the row index)."""
+    RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
+    (``tci_dram_run_stats``) of the kept rows at or past ``opts.stats_from``, reduced from the device
+    chain (``DramResult.stats``; needs ``opts.thin >= 1``; ``max_lag`` as in ``Likelihood.chainstats``).
+    ``want_chain=False``: the kept rows are not copied to the host (``chain`` and ``s2chain`` are None)."""
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
     theta0, lower, upper, prior_mu, prior_sig, qcov_diag = map(f, (theta0, lower, upper, prior_mu, prior_sig,
                                                                     qcov_diag))
@@ -107,8 +117,8 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     smean, sstd, acc = np.empty(n), np.empty(n), np.empty(n)
     nev = np.empty(n, np.int64)
     n_keep = (opts.n_steps + opts.thin - 1) // opts.thin if opts.thin > 0 else 0
-    chain = np.empty((n_keep, n, ld)) if n_keep else None
-    s2c = np.empty((n_keep, n)) if n_keep else None
+    chain = np.empty((n_keep, n, ld)) if n_keep and want_chain else None
+    s2c = np.empty((n_keep, n)) if n_keep and want_chain else None
     qR = np.empty((n, ld, ld)) if want_qcov else None
     out = _lib.tci_dram_outputs(_lib.ptr(mean, _lib._dp), _lib.ptr(std, _lib._dp), _lib.ptr(fin, _lib._dp),
                                 _lib.ptr(smean, _lib._dp), _lib.ptr(sstd, _lib._dp), _lib.ptr(acc, _lib._dp),
@@ -119,10 +129,18 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
         raise ValueError("chain_keys must have one entry per chain")
     o = opts.to_c(keys)
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
-    lk._check(lk._lib.tci_dram_run(lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper),
-                                   P(prior_mu), P(prior_sig), P(qcov_diag), P(s20), ld, C.byref(out)))
+    args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
+            P(qcov_diag), P(s20), ld, C.byref(out))
+    cs = None
+    if stats:
+        cs = ChainStats.empty(n, ld)
+        sopt, sout = _lib.tci_chainstats_options(int(max_lag)), cs.to_c()
+        lk._check(lk._lib.tci_dram_run_stats(*args, C.byref(sopt), C.byref(sout)))
+        cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
+    else:
+        lk._check(lk._lib.tci_dram_run(*args))
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qR,
-                      np.array(out.kernel_ms[:], np.float64), np.array(out.kernel_launches[:], np.int64))
+                      np.array(out.kernel_ms[:], np.float64), np.array(out.kernel_launches[:], np.int64), cs)
 
 
 # ---------------------------------------------------------------------------
@@ -163,6 +181,7 @@ class FitResult:
     gather_bytes: int = 0                      # parallel.fit_sharded: bytes every rank receives in it
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
+    MCMCdiag: Optional[List[Dict]] = None      # fit(..., diagnostics=True): DIAG_FIELDS per fitted cell
 
 
 @dataclass
@@ -257,7 +276,8 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
 
 def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 50.0, seed: int = 0,
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
-        opts: Optional[DramOptions] = None, cell_offset: int = 0) -> FitResult:
+        opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
+        max_lag: int = 0) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -273,7 +293,11 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     :func:`parallel.fit_sharded`) reproduces those cells' results of the full fit bit for bit.
     ``cell_offset``: ``lk`` holds only a contiguous block of a larger dataset, starting at this
     dataset-wide cell index; keys, x0, per-cell inputs and ``cell_index`` use the dataset-wide index
-    (a rank that loaded only its own shard reproduces the one-GPU fit of the whole dataset)."""
+    (a rank that loaded only its own shard reproduces the one-GPU fit of the whole dataset).
+
+    ``diagnostics``: also ``MCMCdiag``, one dict of ``DIAG_FIELDS`` per fitted cell: the Monte-Carlo
+    error, the integrated autocorrelation time and Geweke's p of every parameter and of s2, over the
+    rows ``MCMCchain`` keeps (needs ``thin >= 1``), reduced on the device (:func:`diag_entry`)."""
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -286,7 +310,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     o.n_steps, o.burnintime, o.stats_from, o.thin = int(n_steps), int(n_burn), int(max(n_burn, 1)), int(thin)
     o.seed = int(seed) * 1000003 + 20201028
     res = dram_run(lk, np.array(keep, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu, plan.prior_sig,
-                   plan.qcov_diag, 1.0, o, chain_keys=np.array(keep, np.int64) + off)
+                   plan.qcov_diag, 1.0, o, chain_keys=np.array(keep, np.int64) + off,
+                   **(dict(stats=True, max_lag=max_lag) if diagnostics else {}))
     # forward model at the means on the raw times (:307-309)
     ms2, pp7 = lk.forward(res.mean, np.array(keep, np.int32), grid="raw")
     results, plots, chains = [], [], []
@@ -316,8 +341,30 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
             ch["dR_chain"] = th[:, 7:].copy()
             ch["s2chain"] = res.s2chain[:, k].copy()  # s2chain is not sliced by n_burn (:323)
         chains.append(ch)
+    diag = None
+    if diagnostics:
+        diag = [diag_entry(res.stats, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
     return FitResult(cl.name, results, plots, chains, res.accept_rate, int(res.n_evals.sum()), res.elapsed_ms,
-                     np.array(keep, np.int64) + off, res.final_theta)
+                     np.array(keep, np.int64) + off, res.final_theta, MCMCdiag=diag)
+
+
+def diag_entry(st: ChainStats, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCdiag`` entry (``DIAG_FIELDS``) from chain ``k`` of ``st``, a cell of ``n`` points.
+    ``ess_min = n_rows / max tau`` over the cell's parameters (s2 left out): the effective sample
+    size of its slowest parameter; NaN when that tau is NaN, 0 when it is +Inf."""
+    d = {}
+    for stat, arr, s2 in (("mcerr", st.mcerr, st.s2_mcerr), ("tau", st.tau, st.s2_tau),
+                          ("geweke_p", st.geweke_p, st.s2_geweke_p)):
+        for name in _SCALARS:
+            d[f"{stat}_{name}"] = float(arr[k, THETA_INDEX[name]])
+        d[f"{stat}_dR"] = arr[k, 7:7 + n].copy()
+        d[f"{stat}_s2"] = float(s2[k])
+    tau = st.tau[k, :7 + n]
+    d["n_rows"] = int(st.n_rows)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d["ess_min"] = float(np.float64(st.n_rows) / np.max(tau)) if tau.size else float("nan")
+    d["cell_index"] = int(cell_index)
+    return {f: d[f] for f in DIAG_FIELDS}
 
 
 # ---------------------------------------------------------------------------
@@ -412,9 +459,12 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
     base = os.path.join(save_loc, f"{date}-{fit_result.DatasetName}")
     # the predictive bands only after predict(): a fit without them writes the same file as before
     plot_fields = PLOT_FIELDS + (PRED_FIELDS if any("predMS2" in p for p in fit_result.MCMCplot) else ())
-    sio.savemat(base + ".mat", {"MCMCresults": _struct_array(fit_result.MCMCresults, RESULT_FIELDS),
-                                "MCMCplot": _struct_array(fit_result.MCMCplot, plot_fields),
-                                "DatasetName": fit_result.DatasetName})
+    variables = {"MCMCresults": _struct_array(fit_result.MCMCresults, RESULT_FIELDS),
+                 "MCMCplot": _struct_array(fit_result.MCMCplot, plot_fields),
+                 "DatasetName": fit_result.DatasetName}
+    if fit_result.MCMCdiag is not None:  # only a fit with diagnostics: any other writes the same file as before
+        variables["MCMCdiag"] = _struct_array(fit_result.MCMCdiag, DIAG_FIELDS)
+    sio.savemat(base + ".mat", variables)
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))
         for f in CHAIN_FIELDS:

@@ -162,6 +162,43 @@ def unpack_results(rows: np.ndarray, cells, dataset_name: str, n_evals: int, ela
                      (rows[:, 0].astype(np.int64) - 1))
 
 
+_DIAG_STATS = ("mcerr", "tau", "geweke_p")
+_DIAG_NAMES = ("v", "ton", "A", "tau", "MS2_basal", "PP7_basal", "R", "s2")
+
+
+def pack_diag(diag, n_max: int) -> np.ndarray:
+    """``MCMCdiag`` as one float64 row per fitted cell: cell_index, N, n_rows, ess_min, the 24 scalar
+    diagnostics, then mcerr_dR, tau_dR, geweke_p_dR (each padded to ``n_max``)."""
+    ns = len(_DIAG_STATS) * len(_DIAG_NAMES)
+    out = np.full((len(diag), 4 + ns + len(_DIAG_STATS) * n_max), np.nan)
+    for i, d in enumerate(diag):
+        n = len(d["tau_dR"])
+        out[i, :4] = d["cell_index"], n, d["n_rows"], d["ess_min"]
+        out[i, 4:4 + ns] = [d[f"{s}_{v}"] for s in _DIAG_STATS for v in _DIAG_NAMES]
+        for j, s in enumerate(_DIAG_STATS):
+            out[i, 4 + ns + j * n_max:4 + ns + j * n_max + n] = d[s + "_dR"]
+    return out
+
+
+def unpack_diag(rows: np.ndarray):
+    """Inverse of :func:`pack_diag` over the gathered rows (any rank order), sorted by cell."""
+    from .mcmc import DIAG_FIELDS
+
+    rows = rows[np.argsort(rows[:, 0], kind="stable")]
+    ns = len(_DIAG_STATS) * len(_DIAG_NAMES)
+    n_max = (rows.shape[1] - 4 - ns) // len(_DIAG_STATS)
+    out = []
+    for row in rows:
+        n = int(row[1])
+        d = {"cell_index": int(row[0]), "n_rows": int(row[2]), "ess_min": float(row[3])}
+        d.update({f"{s}_{v}": float(x) for (s, v), x in
+                  zip(((s, v) for s in _DIAG_STATS for v in _DIAG_NAMES), row[4:4 + ns])})
+        for j, s in enumerate(_DIAG_STATS):
+            d[s + "_dR"] = row[4 + ns + j * n_max:4 + ns + j * n_max + n].copy()
+        out.append({f: d[f] for f in DIAG_FIELDS})
+    return out
+
+
 def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=None,
                 cell_offset: Optional[int] = None, **fit_kwargs):
     """``TranscriptionCycleMCMC`` over ``torch.distributed`` ranks, one GPU each: rank r fits its
@@ -188,7 +225,11 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
     0-based in a sequence); ``fit`` reads them by dataset-wide cell, so every shard passes them
     unchanged. The result carries the gather's wall time (``gather_s``), the bytes every rank
     receives in it (``gather_bytes``) and this rank's own ``FitResult`` (``local``: raw chains,
-    final states). Without an initialised process group it is the one-rank case."""
+    final states). Without an initialised process group it is the one-rank case.
+
+    ``diagnostics=True`` (passed on to :func:`mcmc.fit`): every rank's ``MCMCdiag`` rows are gathered
+    too, in a second all-gather of their own (``gather_bytes`` counts both); without it the gather is
+    byte for byte the one above."""
     import time
 
     import torch
@@ -220,6 +261,7 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
         t = torch.tensor([pmax, rpl_hi, -rpl_lo], dtype=torch.int64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
         pmax, rpl_hi, rpl_lo = int(t[0].item()), int(t[1].item()), -int(t[2].item())
+    diagnostics = bool(fit_kwargs.get("diagnostics", False))
     opts = fit_kwargs.pop("opts", None)
     opts = dataclasses.replace(opts) if opts is not None else DramOptions()
     opts.adapt_pmax = max(int(opts.adapt_pmax), pmax)
@@ -234,6 +276,11 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
         dist.barrier(group)
     g0 = time.perf_counter()
     rows = gather_rows(local, group=group, device=device)
+    drows = None
+    if diagnostics:
+        ns = len(_DIAG_STATS) * len(_DIAG_NAMES)
+        dlocal = pack_diag(fr.MCMCdiag, n_max) if fr is not None else np.zeros((0, 4 + ns + len(_DIAG_STATS) * n_max))
+        drows = gather_rows(dlocal, group=group, device=device)
     gather_s = time.perf_counter() - g0
     ev, ms = (fr.n_evals, fr.elapsed_ms) if fr else (0, 0.0)
     if on:
@@ -248,5 +295,8 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
         cl = from_lists([], "empty-shard")
     out = unpack_results(rows, cl, cl.name, int(ev), float(ms), cell_offset=off)
     out.gather_s, out.gather_bytes, out.local = gather_s, int(rows.nbytes), fr
+    if drows is not None:
+        out.MCMCdiag = unpack_diag(drows)
+        out.gather_bytes += int(drows.nbytes)
     out.rows_per_lane_uniform = rpl_lo >= rpl_hi   # no rank fitted anything, or all ran one variant
     return out
