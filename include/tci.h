@@ -297,6 +297,54 @@ int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chai
                        const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
                        tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout);
 
+/* ---- Posterior mean, covariance and correlation of every chain (MATLAB's mean / cov / corrcoef) ----
+ * Per chain c over its n = n_rows rows and its P = npar[c] columns (i, j < P), all in FP64, reduced on the device
+ * so that the chain itself does not cross the bus:
+ *   mean[i]     Neumaier-compensated sum of the column in row order, divided by n; a constant column's mean is
+ *               its value.
+ *   cov[i][j]   (sum_t (x_ti - mean_i) (x_tj - mean_j)) / (n - 1): cov(chain). Always two-pass and centred (a
+ *               hierarchical fit holds v within 1e-5 of a value near 5, where a one-pass form cancels). The rows
+ *               are summed in order, four per v_mfma_f64_16x16x4, by one wavefront per 16 x 16 tile; the tiles
+ *               on and above the diagonal are computed, the lower triangle is their mirror (the same bits).
+ *   corr[i][j]  cov_ij / (sqrt(cov_ii) * sqrt(cov_jj)), clamped to [-1, 1]; the diagonal is exactly 1.0 where
+ *               cov_ii is finite and > 0. A constant column gives NaN in its whole row and column, diagonal
+ *               included (0/0, as corrcoef gives).
+ * A non-finite entry makes its column's mean, and its row and column of both matrices, NaN. Padding (i >= P or
+ * j >= P) is NaN in all three outputs. An element's bits depend on its two columns, their indices and n alone:
+ * not on n_chains, the chain's position, ld or scratch_bytes. */
+typedef struct {
+  int64_t scratch_bytes;  /* cap on the device buffer for the matrices (cov and corr, 2 x ld x ld doubles per
+                             chain); 0 = 1 GiB. Past it the chains go through the buffer in groups */
+} tci_chaincov_options;
+
+/* Host buffers (any of the three may be NULL). */
+typedef struct {
+  double* mean;      /* [n_chains][ld] */
+  double* cov;       /* [n_chains][ld][ld] */
+  double* corr;      /* [n_chains][ld][ld] */
+  int64_t n_rows;    /* written: rows the matrices used */
+  double kernel_ms;  /* written: device time of the kernels (HIP events) */
+} tci_chaincov_outputs;
+
+int tci_chaincov_defaults(tci_chaincov_options* opt);
+
+/* The matrices of a chain already on the host: chain is [n_rows][n_chains][ld], npar [n_chains] (NULL: ld for
+ * every chain; TCI_ERANGE outside [0, ld]). opt may be NULL (the defaults). TCI_EINVAL for a null argument,
+ * n_rows < 2, scratch_bytes < 0 or one chain's two ld x ld matrices above scratch_bytes; TCI_ENOMEM when the
+ * chain does not fit the device. */
+int tci_chaincov(tci_ctx* ctx, const tci_chaincov_options* opt, const double* chain, int64_t n_rows, int64_t n_chains,
+                 int64_t ld, const int32_t* npar, tci_chaincov_outputs* out);
+
+/* tci_dram_run_stats plus the matrices of the same rows (the kept rows whose 1-based chain row is >=
+ * stats_from), taken from the device chain before any copy. sout may be NULL (no chain statistics); cout is
+ * required; sopt and copt may be NULL. TCI_EINVAL when opt->thin == 0 or fewer than 2 kept rows are in the
+ * range. */
+int tci_dram_run_cov(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                     const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                     const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                     tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout,
+                     const tci_chaincov_options* copt, tci_chaincov_outputs* cout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -51,6 +51,10 @@
 //          the same diagnostics (mcmcstat's chainstats: batch-means error, Sokal's iact, Geweke; formulas
 //          in include/tci.h) of a chain held in MATLAB: chain is P x n x rows and s2chain n x rows (or []),
 //          as 'dram' returns them; npar: 1 x n real columns per chain (or []: P).
+//   out = tci_mex('chaincov', h, chain, npar)
+//          mean(chain), cov(chain) and corrcoef(chain) of every chain (tci_chaincov; formulas in
+//          include/tci.h), reduced on the device: chain and npar as for 'chainstats', at least 2 rows.
+//          out: struct with mean (P x n), cov, corr (P x P x n; NaN past a chain's npar), n_rows, kernel_ms.
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -568,6 +572,53 @@ void cmd_chainstats(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   plhs[0] = so.finish();
 }
 
+// ---- 'chaincov': posterior mean, covariance and correlation of every chain -----------------------
+
+void cmd_chaincov(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs != 4) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chaincov', h, chain, npar)");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[3], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  static const char* fields[] = {"mean", "cov", "corr", "n_rows", "kernel_ms"};
+  mxArray* res = mxCreateStructMatrix(1, 1, 5, fields);
+  const mwSize d3[3] = {(mwSize)P, (mwSize)P, (mwSize)n};  // P x P x n == [chain][P][P]: the matrices are symmetric
+  mxArray* mean = mxCreateDoubleMatrix(P, n, mxREAL);
+  mxArray* cov = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+  mxArray* corr = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+  mxSetField(res, 0, "mean", mean);
+  mxSetField(res, 0, "cov", cov);
+  mxSetField(res, 0, "corr", corr);
+  tci_chaincov_outputs out;
+  memset(&out, 0, sizeof out);
+  out.mean = mxGetPr(mean);
+  out.cov = mxGetPr(cov);
+  out.corr = mxGetPr(corr);
+  const int rc = tci_chaincov(ctx, nullptr, X, (int64_t)rows, (int64_t)n, (int64_t)P, npar.empty() ? nullptr : npar.data(),
+                              &out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_chaincov");
+  }
+  mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+  mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+  plhs[0] = res;
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -585,6 +636,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "dram") cmd_dram(nlhs, plhs, nrhs, prhs);
   else if (cmd == "predict") cmd_predict(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainstats") cmd_chainstats(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chaincov") cmd_chaincov(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

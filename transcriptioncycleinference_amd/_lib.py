@@ -83,6 +83,14 @@ class tci_chainstats_outputs(C.Structure):
                 ("s2_tau_window", _i32p), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class tci_chaincov_options(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_int64)]
+
+
+class tci_chaincov_outputs(C.Structure):
+    _fields_ = [("mean", _dp), ("cov", _dp), ("corr", _dp), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -111,6 +119,13 @@ SIGNATURES = [
     ("tci_dram_run_stats", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
                                      _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
                                      C.POINTER(tci_chainstats_options), C.POINTER(tci_chainstats_outputs)]),
+    ("tci_chaincov_defaults", C.c_int, [C.POINTER(tci_chaincov_options)]),
+    ("tci_chaincov", C.c_int, [C.c_void_p, C.POINTER(tci_chaincov_options), _dp, C.c_int64, C.c_int64, C.c_int64,
+                               _i32p, C.POINTER(tci_chaincov_outputs)]),
+    ("tci_dram_run_cov", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                   _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                   C.POINTER(tci_chainstats_options), C.POINTER(tci_chainstats_outputs),
+                                   C.POINTER(tci_chaincov_options), C.POINTER(tci_chaincov_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -45,6 +45,8 @@ struct tci_ctx {
   size_t cap_theta = 0, cap_cell = 0, cap_active = 0, cap_out0 = 0, cap_out1 = 0;
   double* d_sim = nullptr;          // tci_predict: the simulated rows of one chunk of cells (MS2 rows, then PP7 rows)
   size_t cap_sim = 0;
+  double* d_cov = nullptr;          // tci_chaincov: cov then corr of one group of chains
+  size_t cap_cov = 0;
   // small batches of the host-pointer entry points: one pinned, device-mapped buffer the kernel
   // reads and writes in place (no copy launches; tci_ss_batch)
   char* h_io = nullptr;
@@ -412,7 +414,7 @@ int tci_destroy(tci_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (void* q : {(void*)ctx->dbuf, (void*)ctx->d_theta, (void*)ctx->d_cell, (void*)ctx->d_active,
-                  (void*)ctx->d_out0, (void*)ctx->d_out1, (void*)ctx->d_sim})
+                  (void*)ctx->d_out0, (void*)ctx->d_out1, (void*)ctx->d_sim, (void*)ctx->d_cov})
     if (q) (void)hipFree(q);
   if (ctx->h_io) (void)hipHostFree(ctx->h_io);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -703,6 +705,79 @@ int chainstats_device(tci_ctx* ctx, const char* who, const double* d_chain, cons
   return TCI_OK;
 }
 
+// Checks of tci_chaincov_options against ld, before any device work: the chains per group through the scratch.
+int chaincov_group(tci_ctx* ctx, const char* who, const tci_chaincov_options* copt, int64_t n_chains, int64_t ld,
+                   int64_t* group) {
+  const int64_t sb = copt ? copt->scratch_bytes : 0;
+  if (sb < 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": scratch_bytes must be >= 0");
+  if (ld > ((int64_t)1 << 24)) return fail(ctx, TCI_ERANGE, std::string(who) + ": ld above 2^24");
+  const int64_t cap = sb > 0 ? sb : (int64_t)1 << 30;
+  const int64_t per_chain = 2 * ld * ld * (int64_t)sizeof(double);  // <= 2^52
+  if (per_chain > cap)
+    return fail(ctx, TCI_EINVAL, std::string(who) + ": one chain needs " + std::to_string(per_chain) +
+                                     " bytes of scratch (2 x ld x ld doubles), scratch_bytes allows " +
+                                     std::to_string(cap));
+  *group = std::min(std::min(cap / per_chain, tci::chaincov_max_chains(ld)), n_chains);
+  return TCI_OK;
+}
+
+// The covariance kernels on a device chain (launch_chaincov), `group` chains at a time through the context's
+// scratch, timed with HIP events; every group's matrices are copied straight into the caller's host buffers.
+int chaincov_device(tci_ctx* ctx, const char* who, const double* d_chain, int64_t n_rows, int64_t n_chains, int64_t ld,
+                    const int32_t* d_npar, int64_t group, tci_chaincov_outputs* out) {
+  const size_t L = (size_t)ld, L2 = L * L;
+  int rc = ensure(ctx, &ctx->d_cov, &ctx->cap_cov, 2 * (size_t)group * L2);
+  if (rc != TCI_OK) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the matrices failed");
+  }
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  double* d_mean = A.alloc<double>((size_t)n_chains * L, &e);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the means failed");
+  }
+  hipStream_t s = ctx->stream;
+  hipEvent_t ev0, ev1;
+  TCI_HIP(ctx, hipEventCreate(&ev0));
+  e = hipEventCreate(&ev1);
+  if (e != hipSuccess) {
+    (void)hipEventDestroy(ev0);
+    return hip_fail(ctx, e, "hipEventCreate");
+  }
+  double total_ms = 0.0;
+  hipError_t e1 = hipSuccess;
+  rc = TCI_OK;
+  for (int64_t c0 = 0; c0 < n_chains && rc == TCI_OK && e1 == hipSuccess; c0 += group) {
+    const int64_t nc = std::min(group, n_chains - c0);
+    double* d_cv = ctx->d_cov;
+    double* d_cr = ctx->d_cov + (size_t)nc * L2;
+    e1 = hipEventRecord(ev0, s);
+    if (e1 != hipSuccess) break;
+    rc = tci::launch_chaincov(d_chain, n_rows, n_chains, ld, d_npar, c0, nc, d_mean, d_cv, d_cr, (void*)s);
+    e1 = hipEventRecord(ev1, s);
+    const size_t o = (size_t)c0 * L2, nb = (size_t)nc * L2 * sizeof(double);
+    if (rc == TCI_OK && e1 == hipSuccess && out->cov) e1 = hipMemcpyAsync(out->cov + o, d_cv, nb, hipMemcpyDeviceToHost, s);
+    if (rc == TCI_OK && e1 == hipSuccess && out->corr) e1 = hipMemcpyAsync(out->corr + o, d_cr, nb, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);  // the scratch is reused by the next group
+    if (e1 == hipSuccess) e1 = e2;
+    float ms = 0.f;
+    if (rc == TCI_OK && e1 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
+    total_ms += ms;
+  }
+  if (rc == TCI_OK && e1 == hipSuccess && out->mean)
+    e1 = hipMemcpy(out->mean, d_mean, (size_t)n_chains * L * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "chain covariance kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain covariance kernels");
+  out->n_rows = n_rows;
+  out->kernel_ms = total_ms;
+  return TCI_OK;
+}
+
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
 // -> [window records] -> [adapt] -> step + 1.
 int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& p, hipStream_t s, bool with_stats,
@@ -752,11 +827,13 @@ int tci_dram_defaults(tci_dram_options* o) {
 
 namespace {
 
-// tci_dram_run, and with sout the chain statistics of the kept rows (tci_dram_run_stats).
+// tci_dram_run, with sout the chain statistics of the kept rows (tci_dram_run_stats), with cvout their mean,
+// covariance and correlation (tci_dram_run_cov).
 int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
                   const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                   const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
-                  tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout) {
+                  tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout,
+                  const tci_chaincov_options* copt, tci_chaincov_outputs* cvout) {
   if (!ctx) return TCI_EINVAL;
   if (!opt || !out || n_chains <= 0 || !cell_id || !theta0 || !lower || !upper || !prior_mu || !prior_sig ||
       !qcov_diag || !sigma2_0)
@@ -778,6 +855,17 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     stats_k0 = (from - 1 + opt->thin - 1) / opt->thin;
     stats_rows = (opt->n_steps + opt->thin - 1) / opt->thin - stats_k0;
     if (stats_rows < 1) return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: no kept row at or past stats_from (n_rows < 1)");
+  }
+  int64_t cov_k0 = 0, cov_rows = 0, cov_group = 0;  // the matrices use the statistics' rows
+  if (cvout) {
+    if (opt->thin <= 0) return fail(ctx, TCI_EINVAL, "tci_dram_run_cov: the matrices need the kept rows (thin >= 1)");
+    const int64_t from = std::max<int64_t>(opt->stats_from, 1);
+    cov_k0 = (from - 1 + opt->thin - 1) / opt->thin;
+    cov_rows = (opt->n_steps + opt->thin - 1) / opt->thin - cov_k0;
+    if (cov_rows < 2)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_cov: fewer than 2 kept rows at or past stats_from (n_rows < 2)");
+    const int rcg = chaincov_group(ctx, "tci_dram_run_cov", copt, n_chains, ld, &cov_group);
+    if (rcg != TCI_OK) return rcg;
   }
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
@@ -892,13 +980,13 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   TCI_ALLOC(prof, int64_t, 32);
   TCI_HIP(ctx, hipMemsetAsync(st.prof, 0, 32 * sizeof(int64_t), ctx->stream));
 #endif
-  if (n_keep > 0 && sout && !(out->chain || out->s2chain)) {
+  if (n_keep > 0 && (sout || cvout) && !(out->chain || out->s2chain)) {
     // the chain is kept on the device for the statistics alone: running out of memory is the caller's to handle
     st.chain_out = A.alloc<double>((size_t)n_keep * n * L, &e);
     if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(ctx, TCI_ENOMEM, "tci_dram_run_stats: the device chain (" +
+      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : "tci_dram_run_cov") + ": the device chain (" +
                                        std::to_string((size_t)n_keep * n * L * sizeof(double)) + " bytes) does not fit");
     }
     TCI_HIP(ctx, hipMemsetAsync(st.chain_out, 0, (size_t)n_keep * n * L * sizeof(double), ctx->stream));
@@ -1144,9 +1232,14 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   }
   if (st.s2_out && out->s2chain)
     TCI_HIP(ctx, hipMemcpy(out->s2chain, st.s2_out, (size_t)n_keep * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (sout)  // the device chain's rows from the first one in the statistics range
-    return chainstats_device(ctx, "tci_dram_run_stats", st.chain_out + (size_t)stats_k0 * n * L,
-                             st.s2_out + (size_t)stats_k0 * n, stats_rows, n_chains, ld, st.npar, max_lag, sout);
+  if (sout) {  // the device chain's rows from the first one in the statistics range
+    rc = chainstats_device(ctx, "tci_dram_run_stats", st.chain_out + (size_t)stats_k0 * n * L,
+                           st.s2_out + (size_t)stats_k0 * n, stats_rows, n_chains, ld, st.npar, max_lag, sout);
+    if (rc != TCI_OK) return rc;
+  }
+  if (cvout)
+    return chaincov_device(ctx, "tci_dram_run_cov", st.chain_out + (size_t)cov_k0 * n * L, cov_rows, n_chains, ld,
+                           st.npar, cov_group, cvout);
   return TCI_OK;
 }
 
@@ -1159,7 +1252,7 @@ int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, co
                  const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
                  tci_dram_outputs* out) {
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
-                       out, nullptr, nullptr);
+                       out, nullptr, nullptr, nullptr, nullptr);
 }
 
 int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
@@ -1169,7 +1262,59 @@ int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chai
   if (!ctx) return TCI_EINVAL;
   if (!sout) return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: null statistics outputs");
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
-                       out, sopt, sout);
+                       out, sopt, sout, nullptr, nullptr);
+}
+
+int tci_dram_run_cov(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                     const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                     const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                     tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout,
+                     const tci_chaincov_options* copt, tci_chaincov_outputs* cvout) {
+  if (!ctx) return TCI_EINVAL;
+  if (!cvout) return fail(ctx, TCI_EINVAL, "tci_dram_run_cov: null covariance outputs");
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, sopt, sout, copt, cvout);
+}
+
+int tci_chaincov_defaults(tci_chaincov_options* o) {
+  if (!o) return TCI_EINVAL;
+  o->scratch_bytes = 0;  // 1 GiB
+  return TCI_OK;
+}
+
+int tci_chaincov(tci_ctx* ctx, const tci_chaincov_options* opt, const double* chain, int64_t n_rows, int64_t n_chains,
+                 int64_t ld, const int32_t* npar, tci_chaincov_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chaincov: null argument");
+  if (n_rows < 2) return fail(ctx, TCI_EINVAL, "tci_chaincov: n_rows must be >= 2");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chaincov: n_chains and ld must be >= 1");
+  if (n_rows > ((int64_t)1 << 30) || n_chains > ((int64_t)1 << 30))
+    return fail(ctx, TCI_ERANGE, "tci_chaincov: n_rows or n_chains above 2^30");
+  if (npar)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (npar[c] < 0 || npar[c] > ld)
+        return fail(ctx, TCI_ERANGE, "tci_chaincov: npar[" + std::to_string(c) + "] outside [0, ld]");
+  int64_t group = 0;
+  const int rc = chaincov_group(ctx, "tci_chaincov", opt, n_chains, ld, &group);
+  if (rc != TCI_OK) return rc;
+  const size_t per_row = (size_t)n_chains * (size_t)ld;
+  if (per_row > (((size_t)1 << 46) / sizeof(double)) / (size_t)n_rows)
+    return fail(ctx, TCI_ENOMEM, "tci_chaincov: the chain is larger than any device memory");
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t nch = (size_t)n_rows * per_row;
+  double* d_chain = A.alloc<double>(nch, &e);
+  int32_t* d_npar = e == hipSuccess && npar ? A.alloc<int32_t>((size_t)n_chains, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chaincov: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return chaincov_device(ctx, "tci_chaincov", d_chain, n_rows, n_chains, ld, d_npar, group, out);
 }
 
 int tci_chainstats_defaults(tci_chainstats_options* o) {

@@ -24,6 +24,7 @@
 
 #include <cmath>
 
+#include "tci_csum.h"
 #include "tci_internal.h"
 
 namespace tci {
@@ -47,17 +48,6 @@ struct CsView {
 __device__ __forceinline__ double cs_load(const CsView& v, int64_t row, int64_t c, int64_t j) {
   return j < v.ld ? v.chain[(row * v.n_chains + c) * v.ld + j] : v.s2[row * v.n_chains + c];
 }
-
-// Neumaier's compensated sum: the means are right to the last bit or two whatever n is.
-struct CSum {
-  double s = 0.0, c = 0.0;
-  __device__ __forceinline__ void add(double x) {
-    const double t = s + x;
-    c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
-    s = t;
-  }
-  __device__ __forceinline__ double total() const { return s + c; }
-};
 
 // One batch-means problem: nb batches of b rows from the problem's first row, the rest left out;
 // q = sum_i (batch mean_i - centre)^2.

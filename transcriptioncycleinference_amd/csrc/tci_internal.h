@@ -99,4 +99,14 @@ int quantile_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
 int launch_chainstats(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
                       const int32_t* npar, int64_t max_lag, double* stats, int32_t* win, void* stream);
 
+// Mean, covariance and correlation (tci_chaincov.hip) of the chains c0 .. c0 + nc - 1 of a device chain
+// [n_rows][n_chains][ld], n_rows >= 2. npar (device, may be null = ld): columns j >= npar[c] are padding.
+// mean (device): [n_chains][ld], written for the launch's chains; cov, corr (device): [nc][ld][ld], indexed by
+// c - c0. Padding and non-finite columns: NaN. Asynchronous on `stream`. TCI_EINVAL on a size the grid cannot
+// take (nc above chaincov_max_chains(ld)), TCI_EHIP on a HIP error.
+int launch_chaincov(const double* chain, int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, int64_t c0,
+                    int64_t nc, double* mean, double* cov, double* corr, void* stream);
+// The most chains one launch_chaincov takes (grid limits).
+int64_t chaincov_max_chains(int64_t ld);
+
 }  // namespace tci

@@ -48,6 +48,26 @@ class ChainStats:
                                            P(self.s2_geweke_p), W(self.s2_tau_window), 0, 0.0)
 
 
+@dataclasses.dataclass
+class ChainCov:
+    """Per-chain posterior moments (``tci_chaincov_outputs``): ``mean`` ``[n_chains, ld]``, ``cov`` and
+    ``corr`` ``[n_chains, ld, ld]``; padding is NaN."""
+
+    mean: np.ndarray
+    cov: np.ndarray
+    corr: np.ndarray
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n: int, ld: int) -> "ChainCov":
+        return cls(np.full((n, ld), np.nan), np.full((n, ld, ld), np.nan), np.full((n, ld, ld), np.nan))
+
+    def to_c(self) -> "_lib.tci_chaincov_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        return _lib.tci_chaincov_outputs(P(self.mean), P(self.cov), P(self.corr), 0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -212,6 +232,31 @@ class Likelihood:
                                              rows, n, ld, _lib.ptr(npr, _lib._i32p), C.byref(out)))
         st.n_rows, st.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return st
+
+    def chaincov(self, chain: np.ndarray, npar=None, scratch_bytes: int = 0) -> ChainCov:
+        """Mean, covariance and correlation of every chain held on the host (MATLAB's ``mean(chain)``,
+        ``cov(chain)``, ``corrcoef(chain)``), reduced on the device (``tci_chaincov``; formulas in
+        ``include/tci.h``). ``chain`` and ``npar`` as in :meth:`chainstats`; at least 2 rows.
+        ``scratch_bytes``: cap on the device buffer for the matrices (0 = 1 GiB); past it the chains go
+        through in groups, with the same bits. Returns a :class:`ChainCov`; padding is NaN, and so are the
+        mean, row and column of a column holding a non-finite value."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        cc = ChainCov.empty(n, ld)
+        opt = _lib.tci_chaincov_options(int(scratch_bytes))
+        out = cc.to_c()
+        self._check(self._lib.tci_chaincov(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), rows, n, ld,
+                                           _lib.ptr(npr, _lib._i32p), C.byref(out)))
+        cc.n_rows, cc.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return cc
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import ChainStats
+from .likelihood import ChainCov, ChainStats
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -41,6 +41,8 @@ _SCALARS = ("v", "ton", "A", "tau", "MS2_basal", "PP7_basal", "R")
 # MCMCdiag (fit(..., diagnostics=True)): chain diagnostics per fitted cell, mcmcstat's chainstats columns
 DIAG_FIELDS = (tuple(f"{s}_{n}" for s in ("mcerr", "tau", "geweke_p") for n in _SCALARS + ("dR", "s2"))
                + ("n_rows", "ess_min", "cell_index"))
+# MCMCcov (fit(..., covariance=True)): posterior mean, covariance and correlation per fitted cell, P = 7 + N wide
+COV_FIELDS = ("mean", "cov", "corr", "n_rows", "cell_index")
 THETA_INDEX = {"v": 0, "tau": 1, "ton": 2, "MS2_basal": 3, "PP7_basal": 4, "A": 5, "R": 6}
 
 
@@ -96,17 +98,22 @@ class DramResult:
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
     stats: Optional[ChainStats] = None            # dram_run(stats=True): diagnostics of the kept rows
+    cov: Optional[ChainCov] = None                # dram_run(cov=True): mean / cov / corr of the same rows
 
 
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
-             max_lag: int = 0, want_chain: bool = True) -> DramResult:
+             max_lag: int = 0, want_chain: bool = True, cov: bool = False,
+             cov_scratch_bytes: int = 0) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
     (``tci_dram_run_stats``) of the kept rows at or past ``opts.stats_from``, reduced from the device
     chain (``DramResult.stats``; needs ``opts.thin >= 1``; ``max_lag`` as in ``Likelihood.chainstats``).
-    ``want_chain=False``: the kept rows are not copied to the host (``chain`` and ``s2chain`` are None)."""
+    ``want_chain=False``: the kept rows are not copied to the host (``chain`` and ``s2chain`` are None).
+    ``cov``: also the mean, covariance and correlation (``tci_dram_run_cov``) of those same rows, at least 2
+    of them, reduced from the device chain (``DramResult.cov``; ``cov_scratch_bytes`` as ``scratch_bytes`` of
+    ``Likelihood.chaincov``); works with or without ``stats``."""
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
     theta0, lower, upper, prior_mu, prior_sig, qcov_diag = map(f, (theta0, lower, upper, prior_mu, prior_sig,
                                                                     qcov_diag))
@@ -131,16 +138,25 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = None
+    cs = cc = None
+    sopt = sout = None
     if stats:
         cs = ChainStats.empty(n, ld)
         sopt, sout = _lib.tci_chainstats_options(int(max_lag)), cs.to_c()
+    if cov:
+        cc = ChainCov.empty(n, ld)
+        copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
+        lk._check(lk._lib.tci_dram_run_cov(*args, C.byref(sopt) if stats else None, C.byref(sout) if stats else None,
+                                           C.byref(copt), C.byref(cout)))
+        cc.n_rows, cc.kernel_ms = int(cout.n_rows), float(cout.kernel_ms)
+    elif stats:
         lk._check(lk._lib.tci_dram_run_stats(*args, C.byref(sopt), C.byref(sout)))
-        cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
     else:
         lk._check(lk._lib.tci_dram_run(*args))
+    if stats:
+        cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qR,
-                      np.array(out.kernel_ms[:], np.float64), np.array(out.kernel_launches[:], np.int64), cs)
+                      np.array(out.kernel_ms[:], np.float64), np.array(out.kernel_launches[:], np.int64), cs, cc)
 
 
 # ---------------------------------------------------------------------------
@@ -182,6 +198,7 @@ class FitResult:
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
     MCMCdiag: Optional[List[Dict]] = None      # fit(..., diagnostics=True): DIAG_FIELDS per fitted cell
+    MCMCcov: Optional[List[Dict]] = None       # fit(..., covariance=True): COV_FIELDS per fitted cell
 
 
 @dataclass
@@ -277,7 +294,7 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
 def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 50.0, seed: int = 0,
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
-        max_lag: int = 0) -> FitResult:
+        max_lag: int = 0, covariance: bool = False) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -297,7 +314,12 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
 
     ``diagnostics``: also ``MCMCdiag``, one dict of ``DIAG_FIELDS`` per fitted cell: the Monte-Carlo
     error, the integrated autocorrelation time and Geweke's p of every parameter and of s2, over the
-    rows ``MCMCchain`` keeps (needs ``thin >= 1``), reduced on the device (:func:`diag_entry`)."""
+    rows ``MCMCchain`` keeps (needs ``thin >= 1``), reduced on the device (:func:`diag_entry`).
+
+    ``covariance``: also ``MCMCcov``, one dict of ``COV_FIELDS`` per fitted cell: the posterior mean
+    ``[P]``, covariance and correlation ``[P, P]`` (``P = 7 + N``; MATLAB's ``cov(chain)`` and
+    ``corrcoef(chain)``) of the rows ``MCMCchain`` keeps (needs ``thin >= 1`` and 2 such rows), reduced on
+    the device."""
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -311,7 +333,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     o.seed = int(seed) * 1000003 + 20201028
     res = dram_run(lk, np.array(keep, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu, plan.prior_sig,
                    plan.qcov_diag, 1.0, o, chain_keys=np.array(keep, np.int64) + off,
-                   **(dict(stats=True, max_lag=max_lag) if diagnostics else {}))
+                   **(dict(stats=True, max_lag=max_lag) if diagnostics else {}),
+                   **(dict(cov=True) if covariance else {}))
     # forward model at the means on the raw times (:307-309)
     ms2, pp7 = lk.forward(res.mean, np.array(keep, np.int32), grid="raw")
     results, plots, chains = [], [], []
@@ -344,8 +367,19 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     diag = None
     if diagnostics:
         diag = [diag_entry(res.stats, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
+    cov = None
+    if covariance:
+        cov = [cov_entry(res.cov, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
     return FitResult(cl.name, results, plots, chains, res.accept_rate, int(res.n_evals.sum()), res.elapsed_ms,
-                     np.array(keep, np.int64) + off, res.final_theta, MCMCdiag=diag)
+                     np.array(keep, np.int64) + off, res.final_theta, MCMCdiag=diag, MCMCcov=cov)
+
+
+def cov_entry(cc: ChainCov, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCcov`` entry (``COV_FIELDS``) from chain ``k`` of ``cc``, a cell of ``n`` points: the
+    matrices trimmed to the cell's ``P = 7 + n`` columns (theta order: ``THETA_INDEX``, then dR)."""
+    P = 7 + n
+    return {"mean": cc.mean[k, :P].copy(), "cov": cc.cov[k, :P, :P].copy(), "corr": cc.corr[k, :P, :P].copy(),
+            "n_rows": int(cc.n_rows), "cell_index": int(cell_index)}
 
 
 def diag_entry(st: ChainStats, k: int, n: int, cell_index: int) -> Dict:
@@ -464,6 +498,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
                  "DatasetName": fit_result.DatasetName}
     if fit_result.MCMCdiag is not None:  # only a fit with diagnostics: any other writes the same file as before
         variables["MCMCdiag"] = _struct_array(fit_result.MCMCdiag, DIAG_FIELDS)
+    if fit_result.MCMCcov is not None:  # only a fit with covariance=True
+        variables["MCMCcov"] = _struct_array(fit_result.MCMCcov, COV_FIELDS)
     sio.savemat(base + ".mat", variables)
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))

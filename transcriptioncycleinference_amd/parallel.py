@@ -229,7 +229,11 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
 
     ``diagnostics=True`` (passed on to :func:`mcmc.fit`): every rank's ``MCMCdiag`` rows are gathered
     too, in a second all-gather of their own (``gather_bytes`` counts both); without it the gather is
-    byte for byte the one above."""
+    byte for byte the one above.
+
+    ``covariance=True`` is passed on to :func:`mcmc.fit` untouched: every rank's ``local`` carries the
+    ``MCMCcov`` of its own cells. The gathered result's ``MCMCcov`` stays ``None``: the ragged ``P x P``
+    blocks are not gathered."""
     import time
 
     import torch
