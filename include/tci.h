@@ -345,6 +345,63 @@ int tci_dram_run_cov(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains
                      tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout,
                      const tci_chaincov_options* copt, tci_chaincov_outputs* cout);
 
+/* ---- Posterior quantiles of every chain column (mcmcstat's plims: median and credible intervals) ----
+ * Per column x[0..n) (one parameter of one chain over the n = n_rows rows; a chain's s2 is one more column), all
+ * in FP64, selected on the device so that the chain itself does not cross the bus. For each p = probs[q]:
+ *   key(x)  the 64-bit total order of tci_predict: the bits of x, all inverted for a negative x, the sign bit set
+ *           otherwise; so -0 sorts before +0
+ *   y = x sorted ascending by key
+ *   h = (n-1)*p;  lo = floor(h);  f = h - lo
+ *   out = (lo + 1 < n) ? y[lo] + f * (y[lo+1] - y[lo]) : y[n-1]
+ * i.e. plims' interp1(sort(x), (n-1)*p+1), the formula of tci_predict: a multiply and an add as written, never
+ * fused. Unlike tci_predict, which sorts NaN last, a non-finite entry (NaN or +-Inf) makes every quantile of its
+ * column NaN, as tci_chainstats and tci_chaincov treat such a column. Padding (j >= npar[c]) is NaN.
+ * The result is exact: y[lo] and y[lo+1] are the column's true order statistics (a radix selection on the keys;
+ * no sketch, no sampling, no histogram approximation), so an output's bits depend on the column's values, n and p
+ * alone: not on n_chains, the chain's position, ld or any tile size. */
+typedef struct {
+  int32_t nq;        /* 1 <= nq <= 16 */
+  double probs[16];  /* each finite and in [0, 1]; defaults: nq = 3, {0.025, 0.5, 0.975} */
+} tci_chainquant_options;
+
+/* Host buffers (any may be NULL). */
+typedef struct {
+  double* q;         /* [n_chains][nq][ld] */
+  double* s2_q;      /* [n_chains][nq]; NaN without an s2 chain */
+  int64_t n_rows;    /* written: rows the quantiles used */
+  double kernel_ms;  /* written: device time of the kernel (HIP events) */
+} tci_chainquant_outputs;
+
+int tci_chainquant_defaults(tci_chainquant_options* opt);
+
+/* The quantiles of a chain already on the host: chain is [n_rows][n_chains][ld], s2chain [n_rows][n_chains] or
+ * NULL, npar [n_chains] (NULL: ld for every chain; TCI_ERANGE outside [0, ld]). opt may be NULL (the defaults).
+ * TCI_EINVAL for a null argument, n_rows < 1, nq outside [1, 16] or a prob that is not in [0, 1]; TCI_ENOMEM
+ * when the chain does not fit the device. */
+int tci_chainquant(tci_ctx* ctx, const tci_chainquant_options* opt, const double* chain, const double* s2chain,
+                   int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chainquant_outputs* out);
+
+/* The optional reductions of a run's device chain. Each *out that is NULL: that reduction is not run; each *opt
+ * may be NULL (its defaults). */
+typedef struct {
+  const tci_chainstats_options* sopt;
+  tci_chainstats_outputs* sout;
+  const tci_chaincov_options* copt;
+  tci_chaincov_outputs* cout;
+  const tci_chainquant_options* qopt;
+  tci_chainquant_outputs* qout;
+} tci_dram_reductions;
+
+/* tci_dram_run plus any of the three reductions, all over the same rows (the kept rows whose 1-based chain row is
+ * >= stats_from), taken from the device chain before any copy; the device chain exists for them alone when
+ * out->chain is NULL. tci_dram_run_stats and tci_dram_run_cov are this call with the fields they name.
+ * TCI_EINVAL for a null red, and, when a reduction is asked for, when opt->thin == 0 or no kept row (covariance:
+ * fewer than 2) is in the range. */
+int tci_dram_run_reduced(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                         const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                         const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                         tci_dram_outputs* out, const tci_dram_reductions* red);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -55,6 +55,10 @@
 //          mean(chain), cov(chain) and corrcoef(chain) of every chain (tci_chaincov; formulas in
 //          include/tci.h), reduced on the device: chain and npar as for 'chainstats', at least 2 rows.
 //          out: struct with mean (P x n), cov, corr (P x P x n; NaN past a chain's npar), n_rows, kernel_ms.
+//   out = tci_mex('chainquant', h, chain, npar, probs)
+//          plims(chain, probs) of every chain column (tci_chainquant; the definition is in include/tci.h),
+//          exact and selected on the device: chain and npar as for 'chainstats'; probs: 1 to 16 values in [0, 1].
+//          out: struct with q (P x numel(probs) x n; NaN past a chain's npar) and n_rows.
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -619,6 +623,56 @@ void cmd_chaincov(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = res;
 }
 
+// ---- 'chainquant': exact posterior quantiles of every chain column ------------------------------------
+
+void cmd_chainquant(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs != 5) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chainquant', h, chain, npar, probs)");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[3], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  const size_t nq = mxGetNumberOfElements(prhs[4]);
+  const double* pr = doubles(prhs[4], -1, "probs");
+  if (nq < 1 || nq > 16) mexErrMsgIdAndTxt("tci:arg", "probs must have 1 to 16 elements");
+  tci_chainquant_options opt;
+  tci_chainquant_defaults(&opt);
+  opt.nq = (int32_t)nq;
+  for (size_t q = 0; q < nq; ++q) {
+    if (!(pr[q] >= 0.0 && pr[q] <= 1.0)) mexErrMsgIdAndTxt("tci:arg", "probs(%d) must be in [0, 1]", (int)q + 1);
+    opt.probs[q] = pr[q];
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  static const char* fields[] = {"q", "n_rows"};
+  mxArray* res = mxCreateStructMatrix(1, 1, 2, fields);
+  const mwSize d3[3] = {(mwSize)P, (mwSize)nq, (mwSize)n};  // P x nq x n == the ABI's [chain][nq][P]
+  mxArray* q = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+  mxSetField(res, 0, "q", q);
+  tci_chainquant_outputs out;
+  memset(&out, 0, sizeof out);
+  out.q = mxGetPr(q);
+  const int rc = tci_chainquant(ctx, &opt, X, nullptr, (int64_t)rows, (int64_t)n, (int64_t)P,
+                                npar.empty() ? nullptr : npar.data(), &out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_chainquant");
+  }
+  mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+  plhs[0] = res;
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -637,6 +691,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "predict") cmd_predict(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainstats") cmd_chainstats(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chaincov") cmd_chaincov(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chainquant") cmd_chainquant(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

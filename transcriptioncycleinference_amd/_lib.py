@@ -91,6 +91,20 @@ class tci_chaincov_outputs(C.Structure):
     _fields_ = [("mean", _dp), ("cov", _dp), ("corr", _dp), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class tci_chainquant_options(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("probs", C.c_double * 16)]
+
+
+class tci_chainquant_outputs(C.Structure):
+    _fields_ = [("q", _dp), ("s2_q", _dp), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+class tci_dram_reductions(C.Structure):
+    _fields_ = [("sopt", C.POINTER(tci_chainstats_options)), ("sout", C.POINTER(tci_chainstats_outputs)),
+                ("copt", C.POINTER(tci_chaincov_options)), ("cout", C.POINTER(tci_chaincov_outputs)),
+                ("qopt", C.POINTER(tci_chainquant_options)), ("qout", C.POINTER(tci_chainquant_outputs))]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -126,6 +140,12 @@ SIGNATURES = [
                                    _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
                                    C.POINTER(tci_chainstats_options), C.POINTER(tci_chainstats_outputs),
                                    C.POINTER(tci_chaincov_options), C.POINTER(tci_chaincov_outputs)]),
+    ("tci_chainquant_defaults", C.c_int, [C.POINTER(tci_chainquant_options)]),
+    ("tci_chainquant", C.c_int, [C.c_void_p, C.POINTER(tci_chainquant_options), _dp, _dp, C.c_int64, C.c_int64,
+                                 C.c_int64, _i32p, C.POINTER(tci_chainquant_outputs)]),
+    ("tci_dram_run_reduced", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                       _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                       C.POINTER(tci_dram_reductions)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -778,6 +778,70 @@ int chaincov_device(tci_ctx* ctx, const char* who, const double* d_chain, int64_
   return TCI_OK;
 }
 
+// Checks of tci_chainquant_options before any device work; *probs, *nq: the probs to use (the defaults for null).
+int chainquant_probs(tci_ctx* ctx, const char* who, const tci_chainquant_options* qopt, int64_t n_chains, int64_t ld,
+                     const double** probs, int32_t* nq) {
+  static const double def[3] = {0.025, 0.5, 0.975};
+  *probs = qopt ? qopt->probs : def;
+  *nq = qopt ? qopt->nq : 3;
+  if (*nq < 1 || *nq > 16) return fail(ctx, TCI_EINVAL, std::string(who) + ": nq must be in [1, 16]");
+  for (int32_t q = 0; q < *nq; ++q)
+    if (!((*probs)[q] >= 0.0 && (*probs)[q] <= 1.0))
+      return fail(ctx, TCI_EINVAL, std::string(who) + ": probs[" + std::to_string(q) + "] is not in [0, 1]");
+  if (ld > ((int64_t)1 << 24) || n_chains > ((int64_t)1 << 30) / ((ld + 64) / 64))
+    return fail(ctx, TCI_ERANGE, std::string(who) + ": ld above 2^24, or n_chains x ceil((ld + 1) / 64) above 2^30");
+  return TCI_OK;
+}
+
+// The selection kernel on a device chain (launch_chainquant), timed with HIP events, and its results scattered
+// into the caller's host buffers (d_npar null: ld columns for every chain; d_s2 null: s2_q is NaN).
+int chainquant_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                      int64_t n_chains, int64_t ld, const int32_t* d_npar, const double* probs, int32_t nq,
+                      tci_chainquant_outputs* out) {
+  const size_t ldc = (size_t)ld + 1, total = (size_t)n_chains * (size_t)nq * ldc;
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  double* d_q = A.alloc<double>(total, &e);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the quantiles failed");
+  }
+  std::vector<double> hq;
+  try {
+    hq.resize(total);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  hipStream_t s = ctx->stream;
+  hipEvent_t ev0, ev1;
+  TCI_HIP(ctx, hipEventCreate(&ev0));
+  e = hipEventCreate(&ev1);
+  if (e != hipSuccess) {
+    (void)hipEventDestroy(ev0);
+    return hip_fail(ctx, e, "hipEventCreate");
+  }
+  hipError_t e1 = hipEventRecord(ev0, s);
+  const int rc = tci::launch_chainquant(d_chain, d_s2, n_rows, n_chains, ld, d_npar, probs, nq, d_q, (void*)s);
+  if (e1 == hipSuccess) e1 = hipEventRecord(ev1, s);
+  if (rc == TCI_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(hq.data(), d_q, total * sizeof(double), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  float ms = 0.f;
+  if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "chain quantile kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "chain quantile kernel");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain quantile copy");
+  for (size_t cq = 0; cq < (size_t)n_chains * (size_t)nq; ++cq) {
+    if (out->q) std::memcpy(out->q + cq * (size_t)ld, hq.data() + cq * ldc, (size_t)ld * sizeof(double));
+    if (out->s2_q) out->s2_q[cq] = hq[cq * ldc + (size_t)ld];
+  }
+  out->n_rows = n_rows;
+  out->kernel_ms = ms;
+  return TCI_OK;
+}
+
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
 // -> [window records] -> [adapt] -> step + 1.
 int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& p, hipStream_t s, bool with_stats,
@@ -827,14 +891,19 @@ int tci_dram_defaults(tci_dram_options* o) {
 
 namespace {
 
-// tci_dram_run, with sout the chain statistics of the kept rows (tci_dram_run_stats), with cvout their mean,
-// covariance and correlation (tci_dram_run_cov).
+// tci_dram_run, with the reductions of the kept rows that `red` asks for: red.sout the chain statistics
+// (tci_dram_run_stats), red.cout their mean, covariance and correlation (tci_dram_run_cov), red.qout their
+// quantiles (tci_dram_run_reduced).
 int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
                   const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                   const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
-                  tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout,
-                  const tci_chaincov_options* copt, tci_chaincov_outputs* cvout) {
+                  tci_dram_outputs* out, const tci_dram_reductions& red) {
   if (!ctx) return TCI_EINVAL;
+  const tci_chainstats_options* sopt = red.sopt;
+  tci_chainstats_outputs* sout = red.sout;
+  const tci_chaincov_options* copt = red.copt;
+  tci_chaincov_outputs* cvout = red.cout;
+  tci_chainquant_outputs* qout = red.qout;
   if (!opt || !out || n_chains <= 0 || !cell_id || !theta0 || !lower || !upper || !prior_mu || !prior_sig ||
       !qcov_diag || !sigma2_0)
     return fail(ctx, TCI_EINVAL, "tci_dram_run: null argument or no chains");
@@ -866,6 +935,20 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
       return fail(ctx, TCI_EINVAL, "tci_dram_run_cov: fewer than 2 kept rows at or past stats_from (n_rows < 2)");
     const int rcg = chaincov_group(ctx, "tci_dram_run_cov", copt, n_chains, ld, &cov_group);
     if (rcg != TCI_OK) return rcg;
+  }
+  int64_t q_k0 = 0, q_rows = 0;  // the quantiles use the statistics' rows too
+  const double* q_probs = nullptr;
+  int32_t q_nq = 0;
+  if (qout) {
+    if (opt->thin <= 0)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_reduced: the quantiles need the kept rows (thin >= 1)");
+    const int64_t from = std::max<int64_t>(opt->stats_from, 1);
+    q_k0 = (from - 1 + opt->thin - 1) / opt->thin;
+    q_rows = (opt->n_steps + opt->thin - 1) / opt->thin - q_k0;
+    if (q_rows < 1)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_reduced: no kept row at or past stats_from (n_rows < 1)");
+    const int rcq = chainquant_probs(ctx, "tci_dram_run_reduced", red.qopt, n_chains, ld, &q_probs, &q_nq);
+    if (rcq != TCI_OK) return rcq;
   }
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
@@ -980,13 +1063,14 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   TCI_ALLOC(prof, int64_t, 32);
   TCI_HIP(ctx, hipMemsetAsync(st.prof, 0, 32 * sizeof(int64_t), ctx->stream));
 #endif
-  if (n_keep > 0 && (sout || cvout) && !(out->chain || out->s2chain)) {
+  if (n_keep > 0 && (sout || cvout || qout) && !(out->chain || out->s2chain)) {
     // the chain is kept on the device for the statistics alone: running out of memory is the caller's to handle
     st.chain_out = A.alloc<double>((size_t)n_keep * n * L, &e);
     if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : "tci_dram_run_cov") + ": the device chain (" +
+      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : cvout ? "tci_dram_run_cov" : "tci_dram_run_reduced") +
+                                       ": the device chain (" +
                                        std::to_string((size_t)n_keep * n * L * sizeof(double)) + " bytes) does not fit");
     }
     TCI_HIP(ctx, hipMemsetAsync(st.chain_out, 0, (size_t)n_keep * n * L * sizeof(double), ctx->stream));
@@ -1237,9 +1321,14 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
                            st.s2_out + (size_t)stats_k0 * n, stats_rows, n_chains, ld, st.npar, max_lag, sout);
     if (rc != TCI_OK) return rc;
   }
-  if (cvout)
-    return chaincov_device(ctx, "tci_dram_run_cov", st.chain_out + (size_t)cov_k0 * n * L, cov_rows, n_chains, ld,
-                           st.npar, cov_group, cvout);
+  if (cvout) {
+    rc = chaincov_device(ctx, "tci_dram_run_cov", st.chain_out + (size_t)cov_k0 * n * L, cov_rows, n_chains, ld, st.npar,
+                         cov_group, cvout);
+    if (rc != TCI_OK) return rc;
+  }
+  if (qout)
+    return chainquant_device(ctx, "tci_dram_run_reduced", st.chain_out + (size_t)q_k0 * n * L,
+                             st.s2_out + (size_t)q_k0 * n, q_rows, n_chains, ld, st.npar, q_probs, q_nq, qout);
   return TCI_OK;
 }
 
@@ -1252,7 +1341,7 @@ int tci_dram_run(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, co
                  const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
                  tci_dram_outputs* out) {
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
-                       out, nullptr, nullptr, nullptr, nullptr);
+                       out, tci_dram_reductions{});
 }
 
 int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
@@ -1261,8 +1350,11 @@ int tci_dram_run_stats(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chai
                        tci_dram_outputs* out, const tci_chainstats_options* sopt, tci_chainstats_outputs* sout) {
   if (!ctx) return TCI_EINVAL;
   if (!sout) return fail(ctx, TCI_EINVAL, "tci_dram_run_stats: null statistics outputs");
+  tci_dram_reductions red{};
+  red.sopt = sopt;
+  red.sout = sout;
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
-                       out, sopt, sout, nullptr, nullptr);
+                       out, red);
 }
 
 int tci_dram_run_cov(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
@@ -1272,8 +1364,71 @@ int tci_dram_run_cov(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains
                      const tci_chaincov_options* copt, tci_chaincov_outputs* cvout) {
   if (!ctx) return TCI_EINVAL;
   if (!cvout) return fail(ctx, TCI_EINVAL, "tci_dram_run_cov: null covariance outputs");
+  tci_dram_reductions red{};
+  red.sopt = sopt;
+  red.sout = sout;
+  red.copt = copt;
+  red.cout = cvout;
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
-                       out, sopt, sout, copt, cvout);
+                       out, red);
+}
+
+int tci_dram_run_reduced(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                         const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                         const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                         tci_dram_outputs* out, const tci_dram_reductions* red) {
+  if (!ctx) return TCI_EINVAL;
+  if (!red) return fail(ctx, TCI_EINVAL, "tci_dram_run_reduced: null reductions");
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, *red);
+}
+
+int tci_chainquant_defaults(tci_chainquant_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  o->nq = 3;
+  o->probs[0] = 0.025;
+  o->probs[1] = 0.5;
+  o->probs[2] = 0.975;
+  return TCI_OK;
+}
+
+int tci_chainquant(tci_ctx* ctx, const tci_chainquant_options* opt, const double* chain, const double* s2chain,
+                   int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chainquant_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chainquant: null argument");
+  if (n_rows < 1) return fail(ctx, TCI_EINVAL, "tci_chainquant: n_rows must be >= 1");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chainquant: n_chains and ld must be >= 1");
+  if (n_rows > ((int64_t)1 << 30) || n_chains > ((int64_t)1 << 30))
+    return fail(ctx, TCI_ERANGE, "tci_chainquant: n_rows or n_chains above 2^30");
+  const double* probs = nullptr;
+  int32_t nq = 0;
+  const int rc = chainquant_probs(ctx, "tci_chainquant", opt, n_chains, ld, &probs, &nq);
+  if (rc != TCI_OK) return rc;
+  if (npar)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (npar[c] < 0 || npar[c] > ld)
+        return fail(ctx, TCI_ERANGE, "tci_chainquant: npar[" + std::to_string(c) + "] outside [0, ld]");
+  const size_t per_row = (size_t)n_chains * (size_t)ld;
+  if (per_row > (((size_t)1 << 46) / sizeof(double)) / (size_t)n_rows)
+    return fail(ctx, TCI_ENOMEM, "tci_chainquant: the chain is larger than any device memory");
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t nch = (size_t)n_rows * per_row, ns2 = (size_t)n_rows * (size_t)n_chains;
+  double* d_chain = A.alloc<double>(nch, &e);
+  double* d_s2 = e == hipSuccess && s2chain ? A.alloc<double>(ns2, &e) : nullptr;
+  int32_t* d_npar = e == hipSuccess && npar ? A.alloc<int32_t>((size_t)n_chains, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chainquant: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return chainquant_device(ctx, "tci_chainquant", d_chain, d_s2, n_rows, n_chains, ld, d_npar, probs, nq, out);
 }
 
 int tci_chaincov_defaults(tci_chaincov_options* o) {

@@ -109,4 +109,12 @@ int launch_chaincov(const double* chain, int64_t n_rows, int64_t n_chains, int64
 // The most chains one launch_chaincov takes (grid limits).
 int64_t chaincov_max_chains(int64_t ld);
 
+// Exact quantiles (tci_chainquant.hip) of every column of a device chain [n_rows][n_chains][ld] and, when s2 is
+// not null, of s2 [n_rows][n_chains] as column ld of every chain. npar (device, may be null = ld): columns
+// j >= npar[c] are padding. probs: nq host values in [0, 1], 1 <= nq <= 16. out (device): [n_chains][nq][ld + 1];
+// padding, non-finite columns and column ld without s2 are NaN. Asynchronous on `stream`. TCI_EINVAL on a size
+// the grid cannot take or a bad prob, TCI_EHIP on a HIP error.
+int launch_chainquant(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
+                      const int32_t* npar, const double* probs, int32_t nq, double* out, void* stream);
+
 }  // namespace tci

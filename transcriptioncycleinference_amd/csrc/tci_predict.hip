@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tci_internal.h"
+#include "tci_key.h"
 
 namespace tci {
 
@@ -27,17 +28,6 @@ namespace {
 
 constexpr int kQThreads = 256;
 constexpr int64_t kQTileKeys = 8192;  // keys per workgroup: 64 KiB of LDS + padding, two workgroups per CU
-constexpr uint64_t kSign = 0x8000000000000000ull;
-
-__device__ __forceinline__ uint64_t to_key(double x) {
-  uint64_t u = (uint64_t)__double_as_longlong(x);
-  if (x != x) u = 0x7FF8000000000000ull;
-  return (u & kSign) ? ~u : (u | kSign);
-}
-
-__device__ __forceinline__ double from_key(uint64_t k) {
-  return __longlong_as_double((long long)((k & kSign) ? (k ^ kSign) : ~k));
-}
 
 template <int CTRL>
 __device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {

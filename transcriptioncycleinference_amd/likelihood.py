@@ -68,6 +68,42 @@ class ChainCov:
         return _lib.tci_chaincov_outputs(P(self.mean), P(self.cov), P(self.corr), 0, 0.0)
 
 
+def quant_probs(probs) -> np.ndarray:
+    """``probs`` as the float64 vector ``tci_chainquant_options`` takes: 1 to 16 values in [0, 1]."""
+    pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, np.float64)))
+    if pr.ndim != 1 or not 1 <= len(pr) <= 16:
+        raise ValueError("probs must hold 1 to 16 probabilities")
+    if not np.all((pr >= 0) & (pr <= 1)):
+        raise ValueError("probs must be finite and in [0, 1]")
+    return pr
+
+
+@dataclasses.dataclass
+class ChainQuant:
+    """Per-column posterior quantiles (``tci_chainquant_outputs``): ``q`` ``[n_chains, nq, ld]`` and ``s2_q``
+    ``[n_chains, nq]`` at the probabilities ``probs`` ``[nq]``; padding is NaN."""
+
+    q: np.ndarray
+    s2_q: np.ndarray
+    probs: np.ndarray
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n: int, ld: int, probs=(0.025, 0.5, 0.975)) -> "ChainQuant":
+        pr = quant_probs(probs)
+        return cls(np.full((n, len(pr), ld), np.nan), np.full((n, len(pr)), np.nan), pr)
+
+    def options(self) -> "_lib.tci_chainquant_options":
+        o = _lib.tci_chainquant_options(len(self.probs))
+        o.probs[:len(self.probs)] = self.probs.tolist()
+        return o
+
+    def to_c(self) -> "_lib.tci_chainquant_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        return _lib.tci_chainquant_outputs(P(self.q), P(self.s2_q), 0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -257,6 +293,33 @@ class Likelihood:
                                            _lib.ptr(npr, _lib._i32p), C.byref(out)))
         cc.n_rows, cc.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return cc
+
+    def chainquant(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None,
+                   probs=(0.025, 0.5, 0.975)) -> ChainQuant:
+        """Exact quantiles of every column of a chain held on the host (mcmcstat's ``plims(chain, probs)``:
+        ``interp1(sort(x), (rows-1)*p+1)``), selected on the device (``tci_chainquant``; the definition is in
+        ``include/tci.h``). ``chain``, ``s2chain`` and ``npar`` as in :meth:`chainstats`; ``probs``: 1 to 16
+        probabilities in [0, 1]. Returns a :class:`ChainQuant`; padding is NaN, and so is every quantile of a
+        column holding a non-finite value."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = None
+        if s2chain is not None:
+            s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        cq = ChainQuant.empty(n, ld, probs)
+        opt, out = cq.options(), cq.to_c()
+        self._check(self._lib.tci_chainquant(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp),
+                                             rows, n, ld, _lib.ptr(npr, _lib._i32p), C.byref(out)))
+        cq.n_rows, cq.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return cq
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import ChainCov, ChainStats
+from .likelihood import ChainCov, ChainQuant, ChainStats
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -43,6 +43,8 @@ DIAG_FIELDS = (tuple(f"{s}_{n}" for s in ("mcerr", "tau", "geweke_p") for n in _
                + ("n_rows", "ess_min", "cell_index"))
 # MCMCcov (fit(..., covariance=True)): posterior mean, covariance and correlation per fitted cell, P = 7 + N wide
 COV_FIELDS = ("mean", "cov", "corr", "n_rows", "cell_index")
+# MCMCquant (fit(..., quantiles=probs)): posterior quantiles per fitted cell, [nq] per parameter at `probs`
+QUANT_FIELDS = tuple("q_" + s for s in _SCALARS) + ("q_dR", "q_s2", "probs", "n_rows", "cell_index")
 THETA_INDEX = {"v": 0, "tau": 1, "ton": 2, "MS2_basal": 3, "PP7_basal": 4, "A": 5, "R": 6}
 
 
@@ -97,6 +99,7 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    quant: Optional[ChainQuant] = None            # dram_run(quant=probs): quantiles of the kept rows
     stats: Optional[ChainStats] = None            # dram_run(stats=True): diagnostics of the kept rows
     cov: Optional[ChainCov] = None                # dram_run(cov=True): mean / cov / corr of the same rows
 
@@ -104,7 +107,7 @@ class DramResult:
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
-             cov_scratch_bytes: int = 0) -> DramResult:
+             cov_scratch_bytes: int = 0, quant=None) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -113,7 +116,10 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     ``want_chain=False``: the kept rows are not copied to the host (``chain`` and ``s2chain`` are None).
     ``cov``: also the mean, covariance and correlation (``tci_dram_run_cov``) of those same rows, at least 2
     of them, reduced from the device chain (``DramResult.cov``; ``cov_scratch_bytes`` as ``scratch_bytes`` of
-    ``Likelihood.chaincov``); works with or without ``stats``."""
+    ``Likelihood.chaincov``); works with or without ``stats``. ``quant``: a sequence of 1 to 16 probabilities:
+    also the exact quantiles of those same rows at them (``DramResult.quant``, as ``Likelihood.chainquant``
+    gives), selected from the device chain; the run then goes through ``tci_dram_run_reduced``, which takes any
+    of the three reductions."""
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
     theta0, lower, upper, prior_mu, prior_sig, qcov_diag = map(f, (theta0, lower, upper, prior_mu, prior_sig,
                                                                     qcov_diag))
@@ -138,12 +144,28 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = cc = None
+    cs = cc = cq = None
     sopt = sout = None
+    if quant is not None:
+        cq = ChainQuant.empty(n, ld, quant)
     if stats:
         cs = ChainStats.empty(n, ld)
         sopt, sout = _lib.tci_chainstats_options(int(max_lag)), cs.to_c()
-    if cov:
+    if cq is not None:
+        red = _lib.tci_dram_reductions()
+        qopt, qout = cq.options(), cq.to_c()
+        red.qopt, red.qout = C.pointer(qopt), C.pointer(qout)
+        if stats:
+            red.sopt, red.sout = C.pointer(sopt), C.pointer(sout)
+        if cov:
+            cc = ChainCov.empty(n, ld)
+            copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
+            red.copt, red.cout = C.pointer(copt), C.pointer(cout)
+        lk._check(lk._lib.tci_dram_run_reduced(*args, C.byref(red)))
+        cq.n_rows, cq.kernel_ms = int(qout.n_rows), float(qout.kernel_ms)
+        if cov:
+            cc.n_rows, cc.kernel_ms = int(cout.n_rows), float(cout.kernel_ms)
+    elif cov:
         cc = ChainCov.empty(n, ld)
         copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
         lk._check(lk._lib.tci_dram_run_cov(*args, C.byref(sopt) if stats else None, C.byref(sout) if stats else None,
@@ -155,8 +177,9 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
         lk._check(lk._lib.tci_dram_run(*args))
     if stats:
         cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
-    return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qR,
-                      np.array(out.kernel_ms[:], np.float64), np.array(out.kernel_launches[:], np.int64), cs, cc)
+    return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
+                      kernel_ms=np.array(out.kernel_ms[:], np.float64),
+                      kernel_launches=np.array(out.kernel_launches[:], np.int64), quant=cq, stats=cs, cov=cc)
 
 
 # ---------------------------------------------------------------------------
@@ -197,6 +220,7 @@ class FitResult:
     gather_bytes: int = 0                      # parallel.fit_sharded: bytes every rank receives in it
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
+    MCMCquant: Optional[List[Dict]] = None     # fit(..., quantiles=probs): QUANT_FIELDS per fitted cell
     MCMCdiag: Optional[List[Dict]] = None      # fit(..., diagnostics=True): DIAG_FIELDS per fitted cell
     MCMCcov: Optional[List[Dict]] = None       # fit(..., covariance=True): COV_FIELDS per fitted cell
 
@@ -294,7 +318,7 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
 def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 50.0, seed: int = 0,
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
-        max_lag: int = 0, covariance: bool = False) -> FitResult:
+        max_lag: int = 0, covariance: bool = False, quantiles=None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -319,7 +343,11 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     ``covariance``: also ``MCMCcov``, one dict of ``COV_FIELDS`` per fitted cell: the posterior mean
     ``[P]``, covariance and correlation ``[P, P]`` (``P = 7 + N``; MATLAB's ``cov(chain)`` and
     ``corrcoef(chain)``) of the rows ``MCMCchain`` keeps (needs ``thin >= 1`` and 2 such rows), reduced on
-    the device."""
+    the device.
+
+    ``quantiles``: a sequence of 1 to 16 probabilities: also ``MCMCquant``, one dict of ``QUANT_FIELDS`` per
+    fitted cell: the exact quantiles (mcmcstat's ``plims``: median, credible intervals) of every parameter and
+    of s2 over the rows ``MCMCchain`` keeps (needs ``thin >= 1``), selected on the device (:func:`quant_entry`)."""
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -334,7 +362,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     res = dram_run(lk, np.array(keep, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu, plan.prior_sig,
                    plan.qcov_diag, 1.0, o, chain_keys=np.array(keep, np.int64) + off,
                    **(dict(stats=True, max_lag=max_lag) if diagnostics else {}),
-                   **(dict(cov=True) if covariance else {}))
+                   **(dict(cov=True) if covariance else {}),
+                   **(dict(quant=quantiles) if quantiles is not None else {}))
     # forward model at the means on the raw times (:307-309)
     ms2, pp7 = lk.forward(res.mean, np.array(keep, np.int32), grid="raw")
     results, plots, chains = [], [], []
@@ -370,8 +399,11 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     cov = None
     if covariance:
         cov = [cov_entry(res.cov, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
+    quant = None
+    if quantiles is not None:
+        quant = [quant_entry(res.quant, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
     return FitResult(cl.name, results, plots, chains, res.accept_rate, int(res.n_evals.sum()), res.elapsed_ms,
-                     np.array(keep, np.int64) + off, res.final_theta, MCMCdiag=diag, MCMCcov=cov)
+                     np.array(keep, np.int64) + off, res.final_theta, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
 
 
 def cov_entry(cc: ChainCov, k: int, n: int, cell_index: int) -> Dict:
@@ -380,6 +412,18 @@ def cov_entry(cc: ChainCov, k: int, n: int, cell_index: int) -> Dict:
     P = 7 + n
     return {"mean": cc.mean[k, :P].copy(), "cov": cc.cov[k, :P, :P].copy(), "corr": cc.corr[k, :P, :P].copy(),
             "n_rows": int(cc.n_rows), "cell_index": int(cell_index)}
+
+
+def quant_entry(cq: ChainQuant, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCquant`` entry (``QUANT_FIELDS``) from chain ``k`` of ``cq``, a cell of ``n`` points: ``[nq]`` per
+    scalar parameter and for s2, ``[nq, n]`` for dR, at ``probs``."""
+    d = {"q_" + name: cq.q[k, :, THETA_INDEX[name]].copy() for name in _SCALARS}
+    d["q_dR"] = cq.q[k, :, 7:7 + n].copy()
+    d["q_s2"] = cq.s2_q[k].copy()
+    d["probs"] = cq.probs.copy()
+    d["n_rows"] = int(cq.n_rows)
+    d["cell_index"] = int(cell_index)
+    return {f: d[f] for f in QUANT_FIELDS}
 
 
 def diag_entry(st: ChainStats, k: int, n: int, cell_index: int) -> Dict:
@@ -500,6 +544,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCdiag"] = _struct_array(fit_result.MCMCdiag, DIAG_FIELDS)
     if fit_result.MCMCcov is not None:  # only a fit with covariance=True
         variables["MCMCcov"] = _struct_array(fit_result.MCMCcov, COV_FIELDS)
+    if fit_result.MCMCquant is not None:  # only a fit with quantiles=probs
+        variables["MCMCquant"] = _struct_array(fit_result.MCMCquant, QUANT_FIELDS)
     sio.savemat(base + ".mat", variables)
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))

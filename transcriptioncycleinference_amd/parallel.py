@@ -199,6 +199,50 @@ def unpack_diag(rows: np.ndarray):
     return out
 
 
+_QUANT_NAMES = ("v", "ton", "A", "tau", "MS2_basal", "PP7_basal", "R", "s2")
+
+
+def quant_width(nq: int, n_max: int) -> int:
+    """Columns of a :func:`pack_quant` row."""
+    return 4 + nq + nq * len(_QUANT_NAMES) + nq * n_max
+
+
+def pack_quant(quant, n_max: int) -> np.ndarray:
+    """``MCMCquant`` as one float64 row per fitted cell: cell_index, N, n_rows, nq, then probs ``[nq]``, the 8
+    scalar columns' quantiles ``[nq]`` each, then q_dR row by row (each of the nq rows padded to ``n_max``).
+    Every entry holds the same number of probs."""
+    nq = len(quant[0]["probs"]) if quant else 0
+    out = np.full((len(quant), quant_width(nq, n_max)), np.nan)
+    for i, d in enumerate(quant):
+        n = d["q_dR"].shape[1]
+        out[i, :4] = d["cell_index"], n, d["n_rows"], nq
+        out[i, 4:4 + nq] = d["probs"]
+        for j, v in enumerate(_QUANT_NAMES):
+            out[i, 4 + nq * (1 + j):4 + nq * (2 + j)] = d["q_" + v]
+        base = 4 + nq * (1 + len(_QUANT_NAMES))
+        for q in range(nq):
+            out[i, base + q * n_max:base + q * n_max + n] = d["q_dR"][q]
+    return out
+
+
+def unpack_quant(rows: np.ndarray):
+    """Inverse of :func:`pack_quant` over the gathered rows (any rank order), sorted by cell."""
+    from .mcmc import QUANT_FIELDS
+
+    rows = rows[np.argsort(rows[:, 0], kind="stable")]
+    out = []
+    for row in rows:
+        n, nq = int(row[1]), int(row[3])
+        base = 4 + nq * (1 + len(_QUANT_NAMES))
+        n_max = (len(row) - base) // nq
+        d = {"cell_index": int(row[0]), "n_rows": int(row[2]), "probs": row[4:4 + nq].copy()}
+        for j, v in enumerate(_QUANT_NAMES):
+            d["q_" + v] = row[4 + nq * (1 + j):4 + nq * (2 + j)].copy()
+        d["q_dR"] = np.stack([row[base + q * n_max:base + q * n_max + n] for q in range(nq)])
+        out.append({f: d[f] for f in QUANT_FIELDS})
+    return out
+
+
 def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=None,
                 cell_offset: Optional[int] = None, **fit_kwargs):
     """``TranscriptionCycleMCMC`` over ``torch.distributed`` ranks, one GPU each: rank r fits its
@@ -233,7 +277,11 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
 
     ``covariance=True`` is passed on to :func:`mcmc.fit` untouched: every rank's ``local`` carries the
     ``MCMCcov`` of its own cells. The gathered result's ``MCMCcov`` stays ``None``: the ragged ``P x P``
-    blocks are not gathered."""
+    blocks are not gathered.
+
+    ``quantiles=probs`` (passed on to :func:`mcmc.fit`): every rank's ``MCMCquant`` rows are gathered in an
+    all-gather of their own (:func:`pack_quant`; ``gather_bytes`` counts it), so the gathered result carries
+    ``MCMCquant`` the way it carries ``MCMCdiag``."""
     import time
 
     import torch
@@ -266,6 +314,7 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
         pmax, rpl_hi, rpl_lo = int(t[0].item()), int(t[1].item()), -int(t[2].item())
     diagnostics = bool(fit_kwargs.get("diagnostics", False))
+    quantiles = fit_kwargs.get("quantiles")
     opts = fit_kwargs.pop("opts", None)
     opts = dataclasses.replace(opts) if opts is not None else DramOptions()
     opts.adapt_pmax = max(int(opts.adapt_pmax), pmax)
@@ -285,6 +334,11 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
         ns = len(_DIAG_STATS) * len(_DIAG_NAMES)
         dlocal = pack_diag(fr.MCMCdiag, n_max) if fr is not None else np.zeros((0, 4 + ns + len(_DIAG_STATS) * n_max))
         drows = gather_rows(dlocal, group=group, device=device)
+    qrows = None
+    if quantiles is not None:
+        nq = len(np.atleast_1d(quantiles))
+        qlocal = pack_quant(fr.MCMCquant, n_max) if fr is not None else np.zeros((0, quant_width(nq, n_max)))
+        qrows = gather_rows(qlocal, group=group, device=device)
     gather_s = time.perf_counter() - g0
     ev, ms = (fr.n_evals, fr.elapsed_ms) if fr else (0, 0.0)
     if on:
@@ -302,5 +356,8 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
     if drows is not None:
         out.MCMCdiag = unpack_diag(drows)
         out.gather_bytes += int(drows.nbytes)
+    if qrows is not None:
+        out.MCMCquant = unpack_quant(qrows)
+        out.gather_bytes += int(qrows.nbytes)
     out.rows_per_lane_uniform = rpl_lo >= rpl_hi   # no rank fitted anything, or all ran one variant
     return out
