@@ -381,8 +381,74 @@ int tci_chainquant_defaults(tci_chainquant_options* opt);
 int tci_chainquant(tci_ctx* ctx, const tci_chainquant_options* opt, const double* chain, const double* s2chain,
                    int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chainquant_outputs* out);
 
+/* ---- Marginal posterior density and histogram of every chain column (mcmcstat's density.m / mcmcplot's
+ * 'denspanel' and 'hist') ----
+ * Per column x[0..n) (one parameter of one chain over the n = n_rows >= 2 rows; a chain's s2 is one more column),
+ * all in FP64, reduced on the device so that the chain itself does not cross the bus. With G = n_grid and
+ * B = n_bins:
+ *   xmin, xmax  the extremes in the key order of tci_chainquant (-0 sorts below +0); r = xmax - xmin.
+ *               range = {xmin, xmax}.
+ *   mean        the Neumaier-compensated sum of the column, divided by n; a constant column's mean is its value
+ *               (xmin == xmax), as in tci_chaincov, so that its sd is exactly 0.
+ *   sd          sqrt(sum_t (x_t - mean)^2 / (n - 1)), two-pass and centred.
+ *   iqr         q(0.75) - q(0.25), q exactly tci_chainquant's quantile (plims) of the column.
+ *   bw          ((bw_scale * 1.06) * s) * n^(-1/5), s = (iqr > 0 ? min(sd, iqr / 1.34) : sd); n^(-1/5) is
+ *               pow((double)n, -0.2), computed once on the host.
+ *   grid        lo = xmin - 0.08 * r;  hi = xmax + 0.08 * r;  step = (hi - lo) / (G - 1);  g_k = lo + k * step,
+ *               k = 0 .. G - 1: every product, sum and quotient rounded once, as written, never fused. The grid's
+ *               bits follow from xmin, xmax and G alone; it is not an output, a caller restates it from range.
+ *   dens[k]     (1 / (n * bw)) * sum_t phi((g_k - x_t) / bw), phi(u) = exp(-u^2 / 2) / sqrt(2 pi): a Gaussian
+ *               kernel estimate with the device library's exp (no fast-math variant).
+ *   counts[b]   the rows of bin b of B equal-width bins over [xmin, xmax]: row t goes to bin
+ *               min(B - 1, (int)floor((x_t - xmin) / r * B)) -- a subtraction, a division and a multiplication,
+ *               in that order -- so a value equal to xmax lands in the last bin; r == 0: all n rows in bin 0.
+ * range and counts are exact. bw is within (n + 16) * 2^-53 (relative) and dens within (4 n + 96) * 2^-53 *
+ * peak, peak = 1 / (bw * sqrt(2 pi)), of the formulas evaluated without rounding (DESIGN.md has the derivation).
+ * A constant column (sd == 0) has bw = 0 and every dens[k] NaN (0/0, as density.m gives); its range is the value
+ * twice and its counts are as above. A non-finite entry (NaN or +-Inf) makes range, bw and dens of its column NaN
+ * and its counts -1, as tci_chainquant and tci_chaincov treat such a column. Padding (j >= npar[c]) is NaN / -1.
+ * An output's bits depend on the column's values, n and the options alone: not on n_chains, the chain's position,
+ * ld or how many workgroups ran (the rows are reduced in segments whose boundaries follow from n alone).
+ *
+ * Two deliberate deviations from mcmcstat, whose version is not pinned (this definition is pinned by its formulas
+ * alone, as tci_chainstats is):
+ *   1. iqr uses the project's one quantile definition (plims, interpolating at (n - 1) p + 1); mcmcstat's iqrange
+ *      interpolates at (n + 1) p.
+ *   2. the grid is always density.m's rule for n > 200 (the data's range widened by 8 % each side); its n <= 200
+ *      branch (mean +- 4 sd) is not restated: one rule keeps the grid bit-exact, and posterior chains are never
+ *      that short. */
+typedef struct {
+  int32_t n_grid;   /* G, 2 .. 256; default 100 (linspace's default in density.m) */
+  int32_t n_bins;   /* B, 1 .. 256; default 20 */
+  double bw_scale;  /* finite and > 0; default 1.0 */
+} tci_chaindens_options;
+
+/* Host buffers (any pointer may be NULL). */
+typedef struct {
+  double* range;       /* [n_chains][2][ld]: xmin, xmax */
+  double* bw;          /* [n_chains][ld] */
+  double* dens;        /* [n_chains][n_grid][ld] */
+  int32_t* counts;     /* [n_chains][n_bins][ld] */
+  double* s2_range;    /* [n_chains][2]; the s2 twins are NaN / -1 without an s2 chain */
+  double* s2_bw;       /* [n_chains] */
+  double* s2_dens;     /* [n_chains][n_grid] */
+  int32_t* s2_counts;  /* [n_chains][n_bins] */
+  int64_t n_rows;      /* written: rows the estimate used */
+  double kernel_ms;    /* written: device time of the kernels (HIP events) */
+} tci_chaindens_outputs;
+
+int tci_chaindens_defaults(tci_chaindens_options* opt);
+
+/* The densities and histograms of a chain already on the host: chain is [n_rows][n_chains][ld], s2chain
+ * [n_rows][n_chains] or NULL, npar [n_chains] (NULL: ld for every chain; TCI_ERANGE outside [0, ld]). opt may be
+ * NULL (the defaults). TCI_EINVAL for a null argument, n_rows < 2 or an option out of range; TCI_ERANGE for
+ * n_rows above 2^30 or a launch grid above 2^31 workgroups; TCI_ENOMEM when the chain or the per-segment partial
+ * sums do not fit the device. */
+int tci_chaindens(tci_ctx* ctx, const tci_chaindens_options* opt, const double* chain, const double* s2chain,
+                  int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chaindens_outputs* out);
+
 /* The optional reductions of a run's device chain. Each *out that is NULL: that reduction is not run; each *opt
- * may be NULL (its defaults). */
+ * may be NULL (its defaults). A zero-initialised struct asks for none. */
 typedef struct {
   const tci_chainstats_options* sopt;
   tci_chainstats_outputs* sout;
@@ -390,13 +456,15 @@ typedef struct {
   tci_chaincov_outputs* cout;
   const tci_chainquant_options* qopt;
   tci_chainquant_outputs* qout;
+  const tci_chaindens_options* dopt;
+  tci_chaindens_outputs* dout;
 } tci_dram_reductions;
 
-/* tci_dram_run plus any of the three reductions, all over the same rows (the kept rows whose 1-based chain row is
+/* tci_dram_run plus any of the four reductions, all over the same rows (the kept rows whose 1-based chain row is
  * >= stats_from), taken from the device chain before any copy; the device chain exists for them alone when
  * out->chain is NULL. tci_dram_run_stats and tci_dram_run_cov are this call with the fields they name.
- * TCI_EINVAL for a null red, and, when a reduction is asked for, when opt->thin == 0 or no kept row (covariance:
- * fewer than 2) is in the range. */
+ * TCI_EINVAL for a null red, and, when a reduction is asked for, when opt->thin == 0 or no kept row (covariance
+ * and density: fewer than 2) is in the range. */
 int tci_dram_run_reduced(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
                          const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                          const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,

@@ -59,6 +59,15 @@
 //          plims(chain, probs) of every chain column (tci_chainquant; the definition is in include/tci.h),
 //          exact and selected on the device: chain and npar as for 'chainstats'; probs: 1 to 16 values in [0, 1].
 //          out: struct with q (P x numel(probs) x n; NaN past a chain's npar) and n_rows.
+//   out = tci_mex('chaindens', h, chain, s2chain, npar[, options])
+//          the marginal density (density.m's Gaussian kernel estimate) and histogram of every chain column
+//          (tci_chaindens; the definition is in include/tci.h), reduced on the device: chain, s2chain and npar as
+//          for 'chainstats', at least 2 rows; options: struct with n_grid (2..256, default 100), n_bins (1..256,
+//          default 20) and bw_scale (> 0, default 1), errors 'tci:opts'.
+//          out: struct with range (P x 2 x n: min, max), bw (P x n), dens and grid (P x n_grid x n: plot
+//          dens(j,:,k) over grid(j,:,k)), counts (P x n_bins x n, as doubles: bar them over n_bins equal bins of
+//          range; -1 and NaN past a chain's npar), s2_range (2 x n), s2_bw (1 x n), s2_dens, s2_grid (n_grid x n),
+//          s2_counts (n_bins x n) and n_rows.
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -673,6 +682,115 @@ void cmd_chainquant(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   plhs[0] = res;
 }
 
+// ---- 'chaindens': marginal density and histogram of every chain column --------------------------------
+
+// The density grid of include/tci.h from xmin and xmax: every operation rounded once (the volatile temporaries
+// keep a compiler that contracts by default from fusing the product into the sum).
+void dens_grid(double xmin, double xmax, int G, double* g, size_t stride) {
+  volatile double r = xmax - xmin;
+  volatile double w = 0.08 * r;
+  volatile double lo = xmin - w, hi = xmax + w;
+  volatile double d = hi - lo;
+  volatile double step = d / (double)(G - 1);
+  for (int k = 0; k < G; ++k) {
+    volatile double ks = (double)k * step;
+    g[(size_t)k * stride] = lo + ks;
+  }
+}
+
+void cmd_chaindens(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs < 5 || nrhs > 6) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chaindens', h, chain, s2chain, npar[, options])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  if (rows < 2) mexErrMsgIdAndTxt("tci:arg", "chain must have at least 2 rows");
+  const double* s2 = nullptr;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = no s2 chain
+    s2 = doubles(prhs[3], (long long)(n * rows), "s2chain");
+    if (mxGetNumberOfDimensions(prhs[3]) != 2 || mxGetM(prhs[3]) != n)
+      mexErrMsgIdAndTxt("tci:arg", "s2chain must be n x rows, as 'dram' returns it");
+  }
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[4]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[4], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  tci_chaindens_options opt;
+  tci_chaindens_defaults(&opt);
+  if (nrhs > 5 && mxGetNumberOfElements(prhs[5]) != 0) {
+    const mxArray* o = prhs[5];
+    if (!mxIsStruct(o) || mxGetNumberOfElements(o) != 1) mexErrMsgIdAndTxt("tci:opts", "options must be a 1x1 struct");
+    for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
+      const std::string fn = mxGetFieldNameByNumber(o, f);
+      if (fn != "n_grid" && fn != "n_bins" && fn != "bw_scale")
+        mexErrMsgIdAndTxt("tci:opts", "options.%s is not an option of tci_mex('chaindens')", fn.c_str());
+    }
+    const int64_t G = opt_int(o, "n_grid", opt.n_grid, 2), B = opt_int(o, "n_bins", opt.n_bins, 1);
+    if (G > 256) mexErrMsgIdAndTxt("tci:opts", "options.n_grid must be in [2, 256]");
+    if (B > 256) mexErrMsgIdAndTxt("tci:opts", "options.n_bins must be in [1, 256]");
+    opt.n_grid = (int32_t)G;
+    opt.n_bins = (int32_t)B;
+    opt.bw_scale = opt_num(o, "bw_scale", opt.bw_scale);
+    if (!(opt.bw_scale > 0.0 && opt.bw_scale <= 1.7976931348623157e308))
+      mexErrMsgIdAndTxt("tci:opts", "options.bw_scale must be finite and > 0");
+  }
+  const size_t G = (size_t)opt.n_grid, B = (size_t)opt.n_bins;
+  tci_ctx* ctx = handle_of(prhs[1]);
+  static const char* fields[] = {"range",    "bw",      "dens",      "counts",  "grid",  "s2_range",
+                                 "s2_bw",    "s2_dens", "s2_counts", "s2_grid", "n_rows"};
+  mxArray* res = mxCreateStructMatrix(1, 1, 11, fields);
+  // P x k x n == the ABI's [chain][k][P]; the s2 twins k x n == [chain][k]
+  const mwSize dr[3] = {(mwSize)P, 2, (mwSize)n}, dg[3] = {(mwSize)P, (mwSize)G, (mwSize)n},
+               db[3] = {(mwSize)P, (mwSize)B, (mwSize)n};
+  mxArray* range = mxCreateNumericArray(3, dr, mxDOUBLE_CLASS, mxREAL);
+  mxArray* bw = mxCreateDoubleMatrix(P, n, mxREAL);
+  mxArray* dens = mxCreateNumericArray(3, dg, mxDOUBLE_CLASS, mxREAL);
+  mxArray* counts = mxCreateNumericArray(3, db, mxDOUBLE_CLASS, mxREAL);  // as doubles; -1 = padding or non-finite
+  mxArray* grid = mxCreateNumericArray(3, dg, mxDOUBLE_CLASS, mxREAL);
+  mxArray* s2_range = mxCreateDoubleMatrix(2, n, mxREAL);
+  mxArray* s2_bw = mxCreateDoubleMatrix(1, n, mxREAL);
+  mxArray* s2_dens = mxCreateDoubleMatrix(G, n, mxREAL);
+  mxArray* s2_counts = mxCreateDoubleMatrix(B, n, mxREAL);
+  mxArray* s2_grid = mxCreateDoubleMatrix(G, n, mxREAL);
+  mxArray* vals[] = {range, bw, dens, counts, grid, s2_range, s2_bw, s2_dens, s2_counts, s2_grid};
+  for (int f = 0; f < 10; ++f) mxSetField(res, 0, fields[f], vals[f]);
+  std::vector<int32_t> cnt(n * B * P), s2cnt(n * B);
+  tci_chaindens_outputs out;
+  memset(&out, 0, sizeof out);
+  out.range = mxGetPr(range);
+  out.bw = mxGetPr(bw);
+  out.dens = mxGetPr(dens);
+  out.counts = cnt.data();
+  out.s2_range = mxGetPr(s2_range);
+  out.s2_bw = mxGetPr(s2_bw);
+  out.s2_dens = mxGetPr(s2_dens);
+  out.s2_counts = s2cnt.data();
+  const int rc = tci_chaindens(ctx, &opt, X, s2, (int64_t)rows, (int64_t)n, (int64_t)P, npar.empty() ? nullptr : npar.data(),
+                               &out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_chaindens");
+  }
+  std::copy(cnt.begin(), cnt.end(), mxGetPr(counts));
+  std::copy(s2cnt.begin(), s2cnt.end(), mxGetPr(s2_counts));
+  for (size_t c = 0; c < n; ++c) {
+    for (size_t j = 0; j < P; ++j)
+      dens_grid(out.range[(c * 2 + 0) * P + j], out.range[(c * 2 + 1) * P + j], (int)G, mxGetPr(grid) + c * G * P + j, P);
+    dens_grid(out.s2_range[c * 2 + 0], out.s2_range[c * 2 + 1], (int)G, mxGetPr(s2_grid) + c * G, 1);
+  }
+  mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+  plhs[0] = res;
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -692,6 +810,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chainstats") cmd_chainstats(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chaincov") cmd_chaincov(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainquant") cmd_chainquant(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chaindens") cmd_chaindens(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

@@ -99,10 +99,20 @@ class tci_chainquant_outputs(C.Structure):
     _fields_ = [("q", _dp), ("s2_q", _dp), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class tci_chaindens_options(C.Structure):
+    _fields_ = [("n_grid", C.c_int32), ("n_bins", C.c_int32), ("bw_scale", C.c_double)]
+
+
+class tci_chaindens_outputs(C.Structure):
+    _fields_ = [("range", _dp), ("bw", _dp), ("dens", _dp), ("counts", _i32p), ("s2_range", _dp), ("s2_bw", _dp),
+                ("s2_dens", _dp), ("s2_counts", _i32p), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 class tci_dram_reductions(C.Structure):
     _fields_ = [("sopt", C.POINTER(tci_chainstats_options)), ("sout", C.POINTER(tci_chainstats_outputs)),
                 ("copt", C.POINTER(tci_chaincov_options)), ("cout", C.POINTER(tci_chaincov_outputs)),
-                ("qopt", C.POINTER(tci_chainquant_options)), ("qout", C.POINTER(tci_chainquant_outputs))]
+                ("qopt", C.POINTER(tci_chainquant_options)), ("qout", C.POINTER(tci_chainquant_outputs)),
+                ("dopt", C.POINTER(tci_chaindens_options)), ("dout", C.POINTER(tci_chaindens_outputs))]
 
 
 # (name, restype, argtypes) for every symbol declared in include/tci.h
@@ -143,6 +153,9 @@ SIGNATURES = [
     ("tci_chainquant_defaults", C.c_int, [C.POINTER(tci_chainquant_options)]),
     ("tci_chainquant", C.c_int, [C.c_void_p, C.POINTER(tci_chainquant_options), _dp, _dp, C.c_int64, C.c_int64,
                                  C.c_int64, _i32p, C.POINTER(tci_chainquant_outputs)]),
+    ("tci_chaindens_defaults", C.c_int, [C.POINTER(tci_chaindens_options)]),
+    ("tci_chaindens", C.c_int, [C.c_void_p, C.POINTER(tci_chaindens_options), _dp, _dp, C.c_int64, C.c_int64,
+                                C.c_int64, _i32p, C.POINTER(tci_chaindens_outputs)]),
     ("tci_dram_run_reduced", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
                                        _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
                                        C.POINTER(tci_dram_reductions)]),

@@ -842,6 +842,99 @@ int chainquant_device(tci_ctx* ctx, const char* who, const double* d_chain, cons
   return TCI_OK;
 }
 
+// Checks of tci_chaindens_options and of the sizes before any device work; *G, *B, *bw_scale: the options to use (the
+// defaults for null), *scratch: the bytes launch_chaindens needs.
+int chaindens_opts(tci_ctx* ctx, const char* who, const tci_chaindens_options* dopt, int64_t n_rows, int64_t n_chains,
+                   int64_t ld, int32_t* G, int32_t* B, double* bw_scale, size_t* scratch) {
+  *G = dopt ? dopt->n_grid : 100;
+  *B = dopt ? dopt->n_bins : 20;
+  *bw_scale = dopt ? dopt->bw_scale : 1.0;
+  if (*G < 2 || *G > 256) return fail(ctx, TCI_EINVAL, std::string(who) + ": n_grid must be in [2, 256]");
+  if (*B < 1 || *B > 256) return fail(ctx, TCI_EINVAL, std::string(who) + ": n_bins must be in [1, 256]");
+  if (!(*bw_scale > 0.0) || !std::isfinite(*bw_scale))
+    return fail(ctx, TCI_EINVAL, std::string(who) + ": bw_scale must be finite and > 0");
+  if (n_rows < 2) return fail(ctx, TCI_EINVAL, std::string(who) + ": fewer than 2 rows (n_rows < 2)");
+  if (n_rows > ((int64_t)1 << 30) || n_chains > ((int64_t)1 << 30) || ld > ((int64_t)1 << 24))
+    return fail(ctx, TCI_ERANGE, std::string(who) + ": n_rows or n_chains above 2^30, or ld above 2^24");
+  const int rc = tci::chaindens_scratch_bytes(n_rows, n_chains, ld, *G, *B, scratch);
+  if (rc == TCI_ENOMEM)
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": the per-segment partial sums are larger than any device memory");
+  if (rc != TCI_OK)
+    return fail(ctx, TCI_ERANGE, std::string(who) + ": rows x chains x ld too large for one launch (2^31 workgroups)");
+  return TCI_OK;
+}
+
+// The density kernels on a device chain (launch_chaindens), timed with HIP events, and their results scattered
+// into the caller's host buffers (d_npar null: ld columns for every chain; d_s2 null: the s2 twins are NaN / -1).
+int chaindens_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                     int64_t n_chains, int64_t ld, const int32_t* d_npar, int32_t G, int32_t B, double bw_scale,
+                     size_t scratch, tci_chaindens_outputs* out) {
+  const size_t ldc = (size_t)ld + 1, n = (size_t)n_chains, L = (size_t)ld;
+  const size_t nd = n * (size_t)(G + 3) * ldc, nc = n * (size_t)B * ldc;
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  void* d_scratch = A.alloc<uint8_t>(scratch, &e);
+  double* d_d = e == hipSuccess ? A.alloc<double>(nd, &e) : nullptr;
+  int32_t* d_c = e == hipSuccess ? A.alloc<int32_t>(nc, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the densities (" +
+                                     std::to_string(scratch + nd * sizeof(double) + nc * sizeof(int32_t)) + " bytes) failed");
+  }
+  std::vector<double> hd;
+  std::vector<int32_t> hc;
+  try {
+    hd.resize(nd);
+    hc.resize(nc);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  hipStream_t s = ctx->stream;
+  hipEvent_t ev0, ev1;
+  TCI_HIP(ctx, hipEventCreate(&ev0));
+  e = hipEventCreate(&ev1);
+  if (e != hipSuccess) {
+    (void)hipEventDestroy(ev0);
+    return hip_fail(ctx, e, "hipEventCreate");
+  }
+  hipError_t e1 = hipEventRecord(ev0, s);
+  const int rc = tci::launch_chaindens(d_chain, d_s2, n_rows, n_chains, ld, d_npar, G, B, bw_scale,
+                                       std::pow((double)n_rows, -0.2), d_scratch, d_d, d_c, (void*)s);
+  if (e1 == hipSuccess) e1 = hipEventRecord(ev1, s);
+  if (rc == TCI_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(hd.data(), d_d, nd * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (rc == TCI_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(hc.data(), d_c, nc * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  float ms = 0.f;
+  if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "chain density kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "chain density kernels");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain density copy");
+  const size_t g = (size_t)G, b = (size_t)B;
+  for (size_t c = 0; c < n; ++c) {
+    const double* src = hd.data() + c * (g + 3) * ldc;  // G density rows, xmin, xmax, bw
+    for (size_t k = 0; k < g; ++k) {
+      if (out->dens) std::memcpy(out->dens + (c * g + k) * L, src + k * ldc, L * sizeof(double));
+      if (out->s2_dens) out->s2_dens[c * g + k] = src[k * ldc + L];
+    }
+    for (size_t k = 0; k < 2; ++k) {
+      if (out->range) std::memcpy(out->range + (c * 2 + k) * L, src + (g + k) * ldc, L * sizeof(double));
+      if (out->s2_range) out->s2_range[c * 2 + k] = src[(g + k) * ldc + L];
+    }
+    if (out->bw) std::memcpy(out->bw + c * L, src + (g + 2) * ldc, L * sizeof(double));
+    if (out->s2_bw) out->s2_bw[c] = src[(g + 2) * ldc + L];
+    for (size_t k = 0; k < b; ++k) {
+      if (out->counts) std::memcpy(out->counts + (c * b + k) * L, hc.data() + (c * b + k) * ldc, L * sizeof(int32_t));
+      if (out->s2_counts) out->s2_counts[c * b + k] = hc[(c * b + k) * ldc + L];
+    }
+  }
+  out->n_rows = n_rows;
+  out->kernel_ms = ms;
+  return TCI_OK;
+}
+
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
 // -> [window records] -> [adapt] -> step + 1.
 int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& p, hipStream_t s, bool with_stats,
@@ -893,7 +986,7 @@ namespace {
 
 // tci_dram_run, with the reductions of the kept rows that `red` asks for: red.sout the chain statistics
 // (tci_dram_run_stats), red.cout their mean, covariance and correlation (tci_dram_run_cov), red.qout their
-// quantiles (tci_dram_run_reduced).
+// quantiles and red.dout their densities and histograms (tci_dram_run_reduced).
 int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
                   const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                   const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
@@ -904,6 +997,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   const tci_chaincov_options* copt = red.copt;
   tci_chaincov_outputs* cvout = red.cout;
   tci_chainquant_outputs* qout = red.qout;
+  tci_chaindens_outputs* dout = red.dout;
   if (!opt || !out || n_chains <= 0 || !cell_id || !theta0 || !lower || !upper || !prior_mu || !prior_sig ||
       !qcov_diag || !sigma2_0)
     return fail(ctx, TCI_EINVAL, "tci_dram_run: null argument or no chains");
@@ -949,6 +1043,21 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
       return fail(ctx, TCI_EINVAL, "tci_dram_run_reduced: no kept row at or past stats_from (n_rows < 1)");
     const int rcq = chainquant_probs(ctx, "tci_dram_run_reduced", red.qopt, n_chains, ld, &q_probs, &q_nq);
     if (rcq != TCI_OK) return rcq;
+  }
+  int64_t d_k0 = 0, d_rows = 0;  // and so do the densities
+  int32_t d_G = 0, d_B = 0;
+  double d_bws = 0.0;
+  size_t d_scratch = 0;
+  if (dout) {
+    if (opt->thin <= 0)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_reduced: the densities need the kept rows (thin >= 1)");
+    const int64_t from = std::max<int64_t>(opt->stats_from, 1);
+    d_k0 = (from - 1 + opt->thin - 1) / opt->thin;
+    d_rows = (opt->n_steps + opt->thin - 1) / opt->thin - d_k0;
+    if (d_rows < 2)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_reduced: fewer than 2 kept rows at or past stats_from (n_rows < 2)");
+    const int rcd = chaindens_opts(ctx, "tci_dram_run_reduced", red.dopt, d_rows, n_chains, ld, &d_G, &d_B, &d_bws, &d_scratch);
+    if (rcd != TCI_OK) return rcd;
   }
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
@@ -1063,7 +1172,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   TCI_ALLOC(prof, int64_t, 32);
   TCI_HIP(ctx, hipMemsetAsync(st.prof, 0, 32 * sizeof(int64_t), ctx->stream));
 #endif
-  if (n_keep > 0 && (sout || cvout || qout) && !(out->chain || out->s2chain)) {
+  if (n_keep > 0 && (sout || cvout || qout || dout) && !(out->chain || out->s2chain)) {
     // the chain is kept on the device for the statistics alone: running out of memory is the caller's to handle
     st.chain_out = A.alloc<double>((size_t)n_keep * n * L, &e);
     if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
@@ -1326,9 +1435,14 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
                          cov_group, cvout);
     if (rc != TCI_OK) return rc;
   }
-  if (qout)
-    return chainquant_device(ctx, "tci_dram_run_reduced", st.chain_out + (size_t)q_k0 * n * L,
-                             st.s2_out + (size_t)q_k0 * n, q_rows, n_chains, ld, st.npar, q_probs, q_nq, qout);
+  if (qout) {
+    rc = chainquant_device(ctx, "tci_dram_run_reduced", st.chain_out + (size_t)q_k0 * n * L,
+                           st.s2_out + (size_t)q_k0 * n, q_rows, n_chains, ld, st.npar, q_probs, q_nq, qout);
+    if (rc != TCI_OK) return rc;
+  }
+  if (dout)
+    return chaindens_device(ctx, "tci_dram_run_reduced", st.chain_out + (size_t)d_k0 * n * L,
+                            st.s2_out + (size_t)d_k0 * n, d_rows, n_chains, ld, st.npar, d_G, d_B, d_bws, d_scratch, dout);
   return TCI_OK;
 }
 
@@ -1429,6 +1543,52 @@ int tci_chainquant(tci_ctx* ctx, const tci_chainquant_options* opt, const double
   if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
   if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
   return chainquant_device(ctx, "tci_chainquant", d_chain, d_s2, n_rows, n_chains, ld, d_npar, probs, nq, out);
+}
+
+int tci_chaindens_defaults(tci_chaindens_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  o->n_grid = 100;  // linspace's default in density.m
+  o->n_bins = 20;
+  o->bw_scale = 1.0;
+  return TCI_OK;
+}
+
+int tci_chaindens(tci_ctx* ctx, const tci_chaindens_options* opt, const double* chain, const double* s2chain,
+                  int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, tci_chaindens_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chaindens: null argument");
+  if (n_rows < 2) return fail(ctx, TCI_EINVAL, "tci_chaindens: n_rows must be >= 2");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chaindens: n_chains and ld must be >= 1");
+  int32_t G = 0, B = 0;
+  double bws = 0.0;
+  size_t scratch = 0;
+  const int rc = chaindens_opts(ctx, "tci_chaindens", opt, n_rows, n_chains, ld, &G, &B, &bws, &scratch);
+  if (rc != TCI_OK) return rc;
+  if (npar)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (npar[c] < 0 || npar[c] > ld)
+        return fail(ctx, TCI_ERANGE, "tci_chaindens: npar[" + std::to_string(c) + "] outside [0, ld]");
+  const size_t per_row = (size_t)n_chains * (size_t)ld;
+  if (per_row > (((size_t)1 << 46) / sizeof(double)) / (size_t)n_rows)
+    return fail(ctx, TCI_ENOMEM, "tci_chaindens: the chain is larger than any device memory");
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t nch = (size_t)n_rows * per_row, ns2 = (size_t)n_rows * (size_t)n_chains;
+  double* d_chain = A.alloc<double>(nch, &e);
+  double* d_s2 = e == hipSuccess && s2chain ? A.alloc<double>(ns2, &e) : nullptr;
+  int32_t* d_npar = e == hipSuccess && npar ? A.alloc<int32_t>((size_t)n_chains, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chaindens: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return chaindens_device(ctx, "tci_chaindens", d_chain, d_s2, n_rows, n_chains, ld, d_npar, G, B, bws, scratch, out);
 }
 
 int tci_chaincov_defaults(tci_chaincov_options* o) {

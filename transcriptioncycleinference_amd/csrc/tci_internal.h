@@ -117,4 +117,16 @@ int64_t chaincov_max_chains(int64_t ld);
 int launch_chainquant(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
                       const int32_t* npar, const double* probs, int32_t nq, double* out, void* stream);
 
+// Densities and histograms (tci_chaindens.hip) of every column of a device chain, laid out and padded as for
+// launch_chainquant; n_rows >= 2, 2 <= G <= 256, 1 <= B <= 256, npow = n_rows^(-1/5). scratch (device):
+// chaindens_scratch_bytes() bytes, 8-byte aligned. out_d (device): [n_chains][G + 3][ld + 1] doubles, per chain the
+// G density rows, then xmin, xmax and bw; out_c (device): [n_chains][B][ld + 1] counts. Padding, non-finite
+// columns and column ld without s2 are NaN / -1. Asynchronous on `stream`; launches launch_chainquant for the
+// quartiles. TCI_EINVAL on a bad size, TCI_ERANGE on a grid above 2^31 - 1 workgroups, TCI_EHIP on a HIP error.
+int launch_chaindens(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
+                     const int32_t* npar, int32_t G, int32_t B, double bw_scale, double npow, void* scratch,
+                     double* out_d, int32_t* out_c, void* stream);
+// The scratch launch_chaindens needs; TCI_ERANGE when the sizes do not fit the launch grid, TCI_ENOMEM above 2^46 bytes.
+int chaindens_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, int32_t G, int32_t B, size_t* bytes);
+
 }  // namespace tci

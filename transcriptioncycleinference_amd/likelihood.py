@@ -104,6 +104,79 @@ class ChainQuant:
         return _lib.tci_chainquant_outputs(P(self.q), P(self.s2_q), 0, 0.0)
 
 
+def dens_options(n_grid=100, n_bins=20, bw_scale=1.0):
+    """The three options of ``tci_chaindens_options``, checked: ``n_grid`` in 2..256, ``n_bins`` in 1..256,
+    ``bw_scale`` finite and > 0."""
+    G, B, s = int(n_grid), int(n_bins), float(bw_scale)
+    if G != n_grid or not 2 <= G <= 256:
+        raise ValueError("n_grid must be an integer in [2, 256]")
+    if B != n_bins or not 1 <= B <= 256:
+        raise ValueError("n_bins must be an integer in [1, 256]")
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError("bw_scale must be finite and > 0")
+    return G, B, s
+
+
+def dens_grid(lo_hi: np.ndarray, n_grid: int) -> np.ndarray:
+    """The density grid of ``include/tci.h`` from ``range``: ``lo_hi`` is ``[..., 2, m]`` (xmin, xmax), the result
+    ``[..., n_grid, m]``; ``lo = xmin - 0.08 r``, ``hi = xmax + 0.08 r``, ``step = (hi - lo) / (G - 1)``,
+    ``g_k = lo + k step``, every operation rounded once (numpy fuses nothing): the bits the device used."""
+    lo_hi = np.asarray(lo_hi, np.float64)
+    xmin, xmax = lo_hi[..., 0:1, :], lo_hi[..., 1:2, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = xmax - xmin
+        w = 0.08 * r
+        lo, hi = xmin - w, xmax + w
+        step = (hi - lo) / np.float64(n_grid - 1)
+        k = np.arange(n_grid, dtype=np.float64).reshape((n_grid, 1))
+        return lo + k * step
+
+
+@dataclasses.dataclass
+class ChainDens:
+    """Per-column marginal densities and histograms (``tci_chaindens_outputs``): ``range`` ``[n_chains, 2, ld]``
+    (xmin, xmax), ``bw`` ``[n_chains, ld]``, ``dens`` ``[n_chains, n_grid, ld]`` on :meth:`grid`, ``counts``
+    ``[n_chains, n_bins, ld]`` (int32) over ``n_bins`` equal bins of ``range``, and the same for s2 without the
+    last axis; padding is NaN (counts -1)."""
+
+    range: np.ndarray
+    bw: np.ndarray
+    dens: np.ndarray
+    counts: np.ndarray
+    s2_range: np.ndarray
+    s2_bw: np.ndarray
+    s2_dens: np.ndarray
+    s2_counts: np.ndarray
+    n_grid: int = 100
+    n_bins: int = 20
+    bw_scale: float = 1.0
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n: int, ld: int, n_grid=100, n_bins=20, bw_scale=1.0) -> "ChainDens":
+        G, B, s = dens_options(n_grid, n_bins, bw_scale)
+        d = lambda *sh: np.full(sh, np.nan)  # noqa: E731
+        w = lambda *sh: np.full(sh, -1, np.int32)  # noqa: E731
+        return cls(d(n, 2, ld), d(n, ld), d(n, G, ld), w(n, B, ld), d(n, 2), d(n), d(n, G), w(n, B), G, B, s)
+
+    def options(self) -> "_lib.tci_chaindens_options":
+        return _lib.tci_chaindens_options(int(self.n_grid), int(self.n_bins), float(self.bw_scale))
+
+    def to_c(self) -> "_lib.tci_chaindens_outputs":
+        P, W = (lambda a: _lib.ptr(a, _lib._dp)), (lambda a: _lib.ptr(a, _lib._i32p))  # noqa: E731
+        return _lib.tci_chaindens_outputs(P(self.range), P(self.bw), P(self.dens), W(self.counts), P(self.s2_range),
+                                          P(self.s2_bw), P(self.s2_dens), W(self.s2_counts), 0, 0.0)
+
+    def grid(self) -> np.ndarray:
+        """``[n_chains, n_grid, ld]``: the points ``dens`` is given at (:func:`dens_grid` of ``range``)."""
+        return dens_grid(self.range, self.n_grid)
+
+    def s2_grid(self) -> np.ndarray:
+        """``[n_chains, n_grid]``: the points of ``s2_dens``."""
+        return dens_grid(self.s2_range.T[None], self.n_grid)[0].T.copy()
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -320,6 +393,36 @@ class Likelihood:
                                              rows, n, ld, _lib.ptr(npr, _lib._i32p), C.byref(out)))
         cq.n_rows, cq.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return cq
+
+    def chaindens(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, n_grid: int = 100,
+                  n_bins: int = 20, bw_scale: float = 1.0) -> ChainDens:
+        """Marginal density and histogram of every column of a chain held on the host (mcmcstat's ``density.m``
+        Gaussian kernel estimate, as ``mcmcplot(chain, [], res, 'denspanel')`` draws it, and the ``histogram`` of
+        the reference's ``ApproveMCMCResults``), reduced on the device (``tci_chaindens``; the definition and its
+        two deviations from mcmcstat are in ``include/tci.h``). ``chain``, ``s2chain`` and ``npar`` as in
+        :meth:`chainstats`; at least 2 rows. ``n_grid``: 2 to 256 density points per column over its range
+        widened by 8 % each side; ``n_bins``: 1 to 256 equal bins over its range; ``bw_scale`` multiplies the
+        rule-of-thumb bandwidth. Returns a :class:`ChainDens`; padding is NaN (counts -1), and so is a column
+        holding a non-finite value; a constant column has bandwidth 0 and a NaN density."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = None
+        if s2chain is not None:
+            s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        cd = ChainDens.empty(n, ld, n_grid, n_bins, bw_scale)
+        opt, out = cd.options(), cd.to_c()
+        self._check(self._lib.tci_chaindens(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp),
+                                            rows, n, ld, _lib.ptr(npr, _lib._i32p), C.byref(out)))
+        cd.n_rows, cd.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return cd
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import ChainCov, ChainQuant, ChainStats
+from .likelihood import ChainCov, ChainDens, ChainQuant, ChainStats
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -45,6 +45,9 @@ DIAG_FIELDS = (tuple(f"{s}_{n}" for s in ("mcerr", "tau", "geweke_p") for n in _
 COV_FIELDS = ("mean", "cov", "corr", "n_rows", "cell_index")
 # MCMCquant (fit(..., quantiles=probs)): posterior quantiles per fitted cell, [nq] per parameter at `probs`
 QUANT_FIELDS = tuple("q_" + s for s in _SCALARS) + ("q_dR", "q_s2", "probs", "n_rows", "cell_index")
+# MCMCdens (fit(..., density=True)): marginal density and histogram per fitted cell, P + 1 = 7 + N + 1 columns wide
+# (theta order, s2 last): grid, dens [G, P + 1], counts [B, P + 1], range [2, P + 1], bw [P + 1]
+DENS_FIELDS = ("grid", "dens", "counts", "range", "bw", "n_rows", "cell_index")
 THETA_INDEX = {"v": 0, "tau": 1, "ton": 2, "MS2_basal": 3, "PP7_basal": 4, "A": 5, "R": 6}
 
 
@@ -99,6 +102,7 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    dens: Optional[ChainDens] = None              # dram_run(dens=True): densities / histograms of the kept rows
     quant: Optional[ChainQuant] = None            # dram_run(quant=probs): quantiles of the kept rows
     stats: Optional[ChainStats] = None            # dram_run(stats=True): diagnostics of the kept rows
     cov: Optional[ChainCov] = None                # dram_run(cov=True): mean / cov / corr of the same rows
@@ -107,7 +111,7 @@ class DramResult:
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
-             cov_scratch_bytes: int = 0, quant=None) -> DramResult:
+             cov_scratch_bytes: int = 0, quant=None, dens=None) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -119,7 +123,9 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     ``Likelihood.chaincov``); works with or without ``stats``. ``quant``: a sequence of 1 to 16 probabilities:
     also the exact quantiles of those same rows at them (``DramResult.quant``, as ``Likelihood.chainquant``
     gives), selected from the device chain; the run then goes through ``tci_dram_run_reduced``, which takes any
-    of the three reductions."""
+    of the reductions. ``dens``: ``True`` or a dict of ``n_grid`` / ``n_bins`` / ``bw_scale``: also the marginal
+    density and histogram of every column of those same rows, at least 2 of them (``DramResult.dens``, as
+    ``Likelihood.chaindens`` gives), through ``tci_dram_run_reduced`` too."""
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
     theta0, lower, upper, prior_mu, prior_sig, qcov_diag = map(f, (theta0, lower, upper, prior_mu, prior_sig,
                                                                     qcov_diag))
@@ -144,17 +150,23 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = cc = cq = None
+    cs = cc = cq = cd = None
     sopt = sout = None
     if quant is not None:
         cq = ChainQuant.empty(n, ld, quant)
+    if dens is not None and dens is not False:
+        cd = ChainDens.empty(n, ld, **({} if dens is True else dict(dens)))
     if stats:
         cs = ChainStats.empty(n, ld)
         sopt, sout = _lib.tci_chainstats_options(int(max_lag)), cs.to_c()
-    if cq is not None:
+    if cq is not None or cd is not None:
         red = _lib.tci_dram_reductions()
-        qopt, qout = cq.options(), cq.to_c()
-        red.qopt, red.qout = C.pointer(qopt), C.pointer(qout)
+        if cq is not None:
+            qopt, qout = cq.options(), cq.to_c()
+            red.qopt, red.qout = C.pointer(qopt), C.pointer(qout)
+        if cd is not None:
+            dopt, dout = cd.options(), cd.to_c()
+            red.dopt, red.dout = C.pointer(dopt), C.pointer(dout)
         if stats:
             red.sopt, red.sout = C.pointer(sopt), C.pointer(sout)
         if cov:
@@ -162,7 +174,10 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
             copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
             red.copt, red.cout = C.pointer(copt), C.pointer(cout)
         lk._check(lk._lib.tci_dram_run_reduced(*args, C.byref(red)))
-        cq.n_rows, cq.kernel_ms = int(qout.n_rows), float(qout.kernel_ms)
+        if cq is not None:
+            cq.n_rows, cq.kernel_ms = int(qout.n_rows), float(qout.kernel_ms)
+        if cd is not None:
+            cd.n_rows, cd.kernel_ms = int(dout.n_rows), float(dout.kernel_ms)
         if cov:
             cc.n_rows, cc.kernel_ms = int(cout.n_rows), float(cout.kernel_ms)
     elif cov:
@@ -179,7 +194,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
         cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
                       kernel_ms=np.array(out.kernel_ms[:], np.float64),
-                      kernel_launches=np.array(out.kernel_launches[:], np.int64), quant=cq, stats=cs, cov=cc)
+                      kernel_launches=np.array(out.kernel_launches[:], np.int64), dens=cd, quant=cq, stats=cs, cov=cc)
 
 
 # ---------------------------------------------------------------------------
@@ -220,6 +235,7 @@ class FitResult:
     gather_bytes: int = 0                      # parallel.fit_sharded: bytes every rank receives in it
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
+    MCMCdens: Optional[List[Dict]] = None      # fit(..., density=True): DENS_FIELDS per fitted cell
     MCMCquant: Optional[List[Dict]] = None     # fit(..., quantiles=probs): QUANT_FIELDS per fitted cell
     MCMCdiag: Optional[List[Dict]] = None      # fit(..., diagnostics=True): DIAG_FIELDS per fitted cell
     MCMCcov: Optional[List[Dict]] = None       # fit(..., covariance=True): COV_FIELDS per fitted cell
@@ -318,7 +334,7 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
 def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 50.0, seed: int = 0,
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
-        max_lag: int = 0, covariance: bool = False, quantiles=None) -> FitResult:
+        max_lag: int = 0, covariance: bool = False, quantiles=None, density=None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -347,7 +363,12 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
 
     ``quantiles``: a sequence of 1 to 16 probabilities: also ``MCMCquant``, one dict of ``QUANT_FIELDS`` per
     fitted cell: the exact quantiles (mcmcstat's ``plims``: median, credible intervals) of every parameter and
-    of s2 over the rows ``MCMCchain`` keeps (needs ``thin >= 1``), selected on the device (:func:`quant_entry`)."""
+    of s2 over the rows ``MCMCchain`` keeps (needs ``thin >= 1``), selected on the device (:func:`quant_entry`).
+
+    ``density``: ``True`` or a dict of ``n_grid`` / ``n_bins`` / ``bw_scale``: also ``MCMCdens``, one dict of
+    ``DENS_FIELDS`` per fitted cell: the marginal density (mcmcstat's ``density.m``) and histogram of every
+    parameter and of s2 over the rows ``MCMCchain`` keeps (needs ``thin >= 1`` and 2 such rows), reduced on the
+    device (:func:`dens_entry`): what ``ApproveMCMCResults`` draws with ``histogram`` from the raw chains."""
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -363,7 +384,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
                    plan.qcov_diag, 1.0, o, chain_keys=np.array(keep, np.int64) + off,
                    **(dict(stats=True, max_lag=max_lag) if diagnostics else {}),
                    **(dict(cov=True) if covariance else {}),
-                   **(dict(quant=quantiles) if quantiles is not None else {}))
+                   **(dict(quant=quantiles) if quantiles is not None else {}),
+                   **(dict(dens=density) if density is not None and density is not False else {}))
     # forward model at the means on the raw times (:307-309)
     ms2, pp7 = lk.forward(res.mean, np.array(keep, np.int32), grid="raw")
     results, plots, chains = [], [], []
@@ -402,8 +424,23 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     quant = None
     if quantiles is not None:
         quant = [quant_entry(res.quant, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
+    dens = None
+    if res.dens is not None:
+        dens = [dens_entry(res.dens, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
     return FitResult(cl.name, results, plots, chains, res.accept_rate, int(res.n_evals.sum()), res.elapsed_ms,
-                     np.array(keep, np.int64) + off, res.final_theta, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+                     np.array(keep, np.int64) + off, res.final_theta, MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag,
+                     MCMCcov=cov)
+
+
+def dens_entry(cd: ChainDens, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCdens`` entry (``DENS_FIELDS``) from chain ``k`` of ``cd``, a cell of ``n`` points: the arrays
+    trimmed to the cell's ``P = 7 + n`` theta columns (order: ``THETA_INDEX``, then dR) with s2 appended as the
+    last column: ``grid`` and ``dens`` ``[G, P + 1]``, ``counts`` ``[B, P + 1]``, ``range`` ``[2, P + 1]``, ``bw`` ``[P + 1]``."""
+    P = 7 + n
+    join = lambda a, b: np.concatenate([a[k][..., :P], np.asarray(b[k])[..., None]], axis=-1)  # noqa: E731
+    return {"grid": join(cd.grid(), cd.s2_grid()), "dens": join(cd.dens, cd.s2_dens),
+            "counts": join(cd.counts, cd.s2_counts), "range": join(cd.range, cd.s2_range),
+            "bw": join(cd.bw, cd.s2_bw), "n_rows": int(cd.n_rows), "cell_index": int(cell_index)}
 
 
 def cov_entry(cc: ChainCov, k: int, n: int, cell_index: int) -> Dict:
@@ -546,6 +583,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCcov"] = _struct_array(fit_result.MCMCcov, COV_FIELDS)
     if fit_result.MCMCquant is not None:  # only a fit with quantiles=probs
         variables["MCMCquant"] = _struct_array(fit_result.MCMCquant, QUANT_FIELDS)
+    if fit_result.MCMCdens is not None:  # only a fit with density=True
+        variables["MCMCdens"] = _struct_array(fit_result.MCMCdens, DENS_FIELDS)
     sio.savemat(base + ".mat", variables)
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))

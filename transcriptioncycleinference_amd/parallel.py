@@ -281,7 +281,11 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
 
     ``quantiles=probs`` (passed on to :func:`mcmc.fit`): every rank's ``MCMCquant`` rows are gathered in an
     all-gather of their own (:func:`pack_quant`; ``gather_bytes`` counts it), so the gathered result carries
-    ``MCMCquant`` the way it carries ``MCMCdiag``."""
+    ``MCMCquant`` the way it carries ``MCMCdiag``.
+
+    ``density=True`` (or a dict of its options) is passed on to :func:`mcmc.fit` untouched, like
+    ``covariance=True``: every rank's ``local`` carries the ``MCMCdens`` of its own cells. The gathered result's
+    ``MCMCdens`` stays ``None``: the per-cell ``[n_grid, 7 + N + 1]`` blocks are not gathered."""
     import time
 
     import torch
