@@ -178,8 +178,9 @@ typedef struct {
  *            as a hipGraph per adaptation window: many chains, or cells too long for FUSED.
  *   WALK:    FUSED's draws pass, then ONE WAVEFRONT per chain walks the chunk (stage 2 evaluated
  *            only after a stage-1 rejection, no workgroup barriers): many chains (configs 4/5).
- *   AUTO:    FUSED whenever its draws pass fits a CU's LDS (P <= ~225), as WALK beyond two chains
- *            per CU; BATCHED otherwise. */
+ *   AUTO:    FUSED whenever the cells are register-resident in the chain kernel and its draws pass
+ *            fits a CU's LDS (cells of up to 513 points, P <= 520), as WALK beyond two chains per
+ *            CU; BATCHED otherwise (longer cells, which FUSED and WALK refuse with TCI_ERANGE). */
 #define TCI_DRAM_AUTO 0
 #define TCI_DRAM_FUSED 1
 #define TCI_DRAM_BATCHED 2

@@ -600,9 +600,10 @@ def test_engines_agree_on_the_two_segment_construct():
 
 @pytest.mark.parametrize("n", [293, 600])
 def test_very_long_cells_sample_and_adapt(n):
-    """Cells past the fused engine's LDS budget (P = 300: the batched engine; N = 600: the
-    long-cell likelihood kernel too, R read from global memory in the proposal products and the
-    generic adaptation): the chains stay in bounds, are deterministic per seed, and the adapted
+    """Very long cells (P = 300: RPL = 8, still within the fused engines' LDS budget, so AUTO runs
+    FUSED and the batched, fused and walk engines are compared; N = 600: past it, the batched engine
+    only, on the long-cell likelihood kernel; R read from global memory in the proposal products and
+    the generic adaptation): the chains stay in bounds, are deterministic per seed, and the adapted
     proposal is the scaled chain covariance (ConstantElongationSim.m:39-50 has no length cap)."""
     from transcriptioncycleinference_amd import Likelihood, from_lists
     from transcriptioncycleinference_amd.mcmc import DramOptions, dram_run
@@ -785,7 +786,7 @@ def _restatement_case(shape, c_oracle):
     from transcriptioncycleinference_amd.data import synthetic_cells
     from transcriptioncycleinference_amd.mcmc import DramOptions, plan_fit
 
-    n_cells, n_points, cname, seed = RESTATEMENT_SHAPES[shape]
+    n_cells, n_points, cname, seed = (RESTATEMENT_SHAPES.get(shape) or RESTATEMENT_LONG_SHAPES[shape][:4])
     cs = _restatement_construct(cname)
 
     def fwd(times, theta):
@@ -823,20 +824,7 @@ def test_gpu_chains_follow_the_cpu_restatement_at_config_shapes(c_oracle, shape,
     and the final proposal factor R within 1e-9. The short / edge / seg shapes (RESTATEMENT_SHAPES) put
     the in-kernel evaluation on RPL = 1 and on 3 and 4 segments, and the adaptation on each side of its
     two kernel switches (P = 144 | 145, 208 | 209), on one tile, a full last tile and a one-row last tile."""
-    from transcriptioncycleinference_amd import Likelihood
-    from transcriptioncycleinference_amd.mcmc import dram_run
-
-    cells, cs, plan, o, keys, c = _restatement_case(shape, c_oracle)
-    o = dataclasses.replace(o, engine=engine)
-    with Likelihood(cells, cs, device=0) as L:
-        rpl = L.info["rows_per_lane"]
-        g = dram_run(L, np.array(plan.cells, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu,
-                     plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys, want_qcov=True)
-    n = cells.lengths[plan.cells]
-    pmax, want_rpl, want_kernel = RESTATEMENT_EXPECT[shape]
-    assert int(7 + n.max()) == pmax
-    assert rpl == want_rpl
-    assert _adapt_kernel(int(7 + n.max())) == want_kernel
+    n = _follows_the_restatement(c_oracle, shape, engine, RESTATEMENT_EXPECT[shape])
     if shape == "mid":
         assert sorted(set(((7 + n + 15) // 16).tolist())) == [10, 11, 12]
     if shape == "short":  # P = 9, 16, 17, 47, 72: one to five tiles, a full and a one-row last tile
@@ -846,6 +834,42 @@ def test_gpu_chains_follow_the_cpu_restatement_at_config_shapes(c_oracle, shape,
         assert sorted(set((7 + n).tolist())) == [128, 129, 144]
     if shape == "edge208":
         assert sorted(set((7 + n).tolist())) == [145, 208]
+
+
+def _restatement_run(shape, c_oracle, engine, **opts):
+    """One GPU run of the shape's case (-> result, rows per lane of the context)."""
+    from transcriptioncycleinference_amd import Likelihood
+    from transcriptioncycleinference_amd.mcmc import dram_run
+
+    cells, cs, plan, o, keys, _ = _restatement_case(shape, c_oracle)
+    o = dataclasses.replace(o, engine=engine, **opts)
+    with Likelihood(cells, cs, device=0) as L:
+        rpl = L.info["rows_per_lane"]
+        g = dram_run(L, np.array(plan.cells, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu,
+                     plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys, want_qcov=True)
+    return g, rpl
+
+
+def _follows_the_restatement(c_oracle, shape, engine, expect):
+    """The assertions of test_gpu_chains_follow_the_cpu_restatement_at_config_shapes for one shape and
+    engine; expect = (largest P, rows per lane, adaptation kernel). Prints the worst row and R errors
+    before it asserts them. Returns the cell lengths."""
+    cells, cs, plan, o, keys, c = _restatement_case(shape, c_oracle)
+    g, rpl = _restatement_run(shape, c_oracle, engine)
+    n = cells.lengths[plan.cells]
+    pmax, want_rpl, want_kernel = expect
+    assert int(7 + n.max()) == pmax
+    assert rpl == want_rpl
+    assert _adapt_kernel(int(7 + n.max())) == want_kernel
+    row_err = r_err = 0.0
+    for k in range(len(plan.cells)):
+        P = 7 + int(n[k])
+        G, Cc = g.chain[:, k, :P], c["chain"][:, k, :P]
+        row_err = max(row_err, float(np.max(np.abs(G - Cc) / np.maximum(np.abs(Cc), 1.0))))
+        R, Rc = g.qcov_R[k, :P, :P], c["R"][k, :P, :P]
+        r_err = max(r_err, float(np.max(np.abs(R - Rc)) / np.abs(Rc).max()))
+    print(f"restatement {shape} {engine}: worst row error {row_err:.3e} (relative to max(|row|, 1)), "
+          f"worst R error {r_err:.3e} of max|R|")
     for k in range(len(plan.cells)):
         P = 7 + int(n[k])
         G, Cc = g.chain[:, k, :P], c["chain"][:, k, :P]
@@ -862,6 +886,117 @@ def test_gpu_chains_follow_the_cpu_restatement_at_config_shapes(c_oracle, shape,
         np.testing.assert_allclose(R, Rc, rtol=1e-9, atol=1e-9 * np.abs(Rc).max(), err_msg=f"{shape} chain {k}: R")
     moved = np.any(g.chain[1:] != g.chain[:-1], axis=2).mean(axis=0)
     assert np.median(moved) > 0.01, moved
+    return n
+
+
+# Cells of 258 to 578 points, two per shape (ld is a run's largest P, so every length is a run of its own):
+# (chains, points per cell, construct, data seed, engines).
+#   rpl8_first:        N = 258, P = 265: the first length of RPL = 8 (k_chain<8, 1, 1>, k_walk<8, 1>: 9 vector
+#                      entries per lane); the draws pass reads R from global memory; k_adapt_gt past P = 217;
+#   walk_wide_last:    N = 292, ld = 299: the last ld of WALK's 64-row draws kernel (draws_walk_wide);
+#   walk_narrow_first: N = 293, ld = 300: the first ld of the 32-row one;
+#   rpl8_two_segment:  N = 300 on the two-segment construct: k_chain<8, 2, 1>, k_walk<8, 2>;
+#   split_last:        N = 461, ld = 468: the last ld whose split draws fit a CU beside k_chain<8>'s static
+#                      LDS (103,712 B in the gfx950 code object + 128 ld + 128 <= 163,840);
+#   split_over:        N = 462, ld = 469: the first past it (163,872 B) -- the one-launch draws pass;
+#   rpl8_last:         N = 513, P = 520: the largest register-resident cell;
+#   tile_first:        N = 514: the long-cell likelihood kernel (rows_per_lane == 0), the batched engine only;
+#   tile_carry:        N = 578: S = N - 1 = 577 steps, one past a multiple of 64.
+_ALL_ENGINES = ("fused", "walk", "batched")
+RESTATEMENT_LONG_SHAPES = {
+    "rpl8_first": (2, 258, "builtin", 20201040, _ALL_ENGINES),
+    "walk_wide_last": (2, 292, "builtin", 20201041, _ALL_ENGINES),
+    "walk_narrow_first": (2, 293, "builtin", 20201042, _ALL_ENGINES),
+    "rpl8_two_segment": (2, 300, "two_segment", 20201043, _ALL_ENGINES),
+    "split_last": (2, 461, "builtin", 20201044, _ALL_ENGINES),
+    "split_over": (2, 462, "builtin", 20201045, _ALL_ENGINES),
+    "rpl8_last": (2, 513, "builtin", 20201046, _ALL_ENGINES),
+    "tile_first": (2, 514, "builtin", 20201047, ("batched",)),
+    "tile_carry": (2, 578, "builtin", 20201048, ("batched",)),
+}
+RESTATEMENT_LONG_EXPECT = {
+    "rpl8_first": (265, 8, "gt"), "walk_wide_last": (299, 8, "gt"), "walk_narrow_first": (300, 8, "gt"),
+    "rpl8_two_segment": (307, 8, "gt"), "split_last": (468, 8, "gt"), "split_over": (469, 8, "gt"),
+    "rpl8_last": (520, 8, "gt"), "tile_first": (521, 0, "gt"), "tile_carry": (585, 0, "gt"),
+}
+_OUTPUT_FIELDS = ("chain", "s2chain", "mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
+                  "qcov_R")
+
+
+def _assert_same_bits(a, b, what):
+    for f in _OUTPUT_FIELDS:
+        np.testing.assert_array_equal(getattr(a, f), getattr(b, f), err_msg=f"{what}: {f}")
+
+
+@pytest.mark.parametrize("shape,engine", [(s, e) for s in RESTATEMENT_LONG_SHAPES for e in RESTATEMENT_LONG_SHAPES[s][4]])
+def test_gpu_chains_follow_the_cpu_restatement_at_long_shapes(c_oracle, shape, engine):
+    """test_gpu_chains_follow_the_cpu_restatement_at_config_shapes's assertions and tolerances, unchanged, on
+    cells of 258 to 578 points (RESTATEMENT_LONG_SHAPES): the RPL = 8 instances of the in-kernel evaluation,
+    the draws pass with R read from global memory and k_adapt_gt up to P = 520, each side of WALK's switch
+    between its two draws kernels and of the split draws' LDS limit, and the batched engine on the long-cell
+    likelihood kernel."""
+    n = _follows_the_restatement(c_oracle, shape, engine, RESTATEMENT_LONG_EXPECT[shape])
+    assert np.all(n == RESTATEMENT_LONG_SHAPES[shape][1])
+    ld = int(7 + n.max())
+    walk_wide_lds = (2 * 8 * 4 * ld + 16) * 8  # draws_lds_bytes(ld, kDrawMTWalk); wide while <= 150 KiB
+    if shape == "walk_wide_last":
+        assert ld == 299 and walk_wide_lds == 153216 and walk_wide_lds <= 150 * 1024
+    if shape == "walk_narrow_first":
+        assert ld == 300 and walk_wide_lds == 153728 and walk_wide_lds > 150 * 1024
+    if shape == "rpl8_two_segment":
+        assert _restatement_case(shape, c_oracle)[1].n_seg == 2
+    if shape == "tile_carry":
+        assert (int(n.max()) - 1) % 64 == 1
+
+
+@pytest.mark.parametrize("shape", ["tile_first", "tile_carry"])
+def test_long_cell_shapes_refuse_the_fused_engines_and_auto_runs_batched(c_oracle, shape):
+    """Cells of 514 and more points (rows_per_lane == 0): FUSED and WALK are refused with TCI_ERANGE, and
+    AUTO gives the batched engine's bits (whose chains the restatement test pins)."""
+    from transcriptioncycleinference_amd import _lib
+
+    for engine in ("fused", "walk"):
+        with pytest.raises(_lib.TciError) as ei:
+            _restatement_run(shape, c_oracle, engine)
+        assert ei.value.code == _lib.TCI_ERANGE, engine
+    auto, rpl = _restatement_run(shape, c_oracle, "auto")
+    assert rpl == 0
+    _assert_same_bits(auto, _restatement_run(shape, c_oracle, "batched")[0], f"{shape}: auto against batched")
+
+
+@pytest.mark.parametrize("shape,split_ran", [("split_last", True), ("split_over", False), ("rpl8_last", False)])
+def test_split_draws_run_only_while_they_fit_beside_the_chain_kernel(c_oracle, shape, split_ran):
+    """FUSED draws the next chunk's normals with extra k_chain workgroups only while their
+    128 ld + 128 bytes of dynamic LDS fit a CU's 163,840 beside k_chain's static LDS (k_chain<8, *, 1>:
+    103,712 B in the gfx950 code object): ld = 468 is the last that fits (163,744), ld = 469 the first that
+    does not (163,872). k_draws_rng (launch class 3) runs only on the split path; past the limit the
+    one-launch draws pass runs instead of a launch that cannot be made. Timing the kernels changes no bit."""
+    ld = RESTATEMENT_LONG_EXPECT[shape][0]
+    assert (103712 + 128 * ld + 128 <= 160 * 1024) == split_ran
+    plain, _ = _restatement_run(shape, c_oracle, "fused")
+    timed, _ = _restatement_run(shape, c_oracle, "fused", kernel_times=True)
+    assert (timed.kernel_launches[3] > 0) == split_ran, timed.kernel_launches
+    assert timed.kernel_launches[0] > 0 and timed.kernel_launches[1] > 0 and timed.kernel_launches[2] > 0
+    _assert_same_bits(timed, plain, f"{shape}: kernel_times on against off")
+
+
+@pytest.mark.parametrize("engine", ["fused", "auto"])
+def test_split_draws_equal_the_one_launch_draws_at_the_last_ld_that_splits(c_oracle, monkeypatch, engine):
+    """test_split_draws_equal_the_one_launch_draws at ld = 468 (split_last), RPL = 8: TCI_DRAWS_SPLIT=1
+    against =0, every output bitwise equal, under FUSED and under AUTO (two chains: FUSED)."""
+    monkeypatch.setenv("TCI_DRAWS_SPLIT", "1")
+    a, _ = _restatement_run("split_last", c_oracle, engine)
+    monkeypatch.setenv("TCI_DRAWS_SPLIT", "0")
+    b, _ = _restatement_run("split_last", c_oracle, engine)
+    _assert_same_bits(a, b, f"split_last {engine}: split against one-launch draws")
+    assert np.median(a.accept_rate) > 0.01
+
+
+def test_auto_runs_past_the_split_limit_and_equals_fused(c_oracle):
+    """ld = 469 (split_over): AUTO (two chains: FUSED, its draws unsplit there) raises nothing and equals
+    engine="fused" bit for bit."""
+    auto, _ = _restatement_run("split_over", c_oracle, "auto")
+    _assert_same_bits(auto, _restatement_run("split_over", c_oracle, "fused")[0], "split_over: auto against fused")
 
 
 def test_output_padding_is_the_documented_contract(c_oracle):

@@ -1282,9 +1282,15 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     // extra workgroups of chunk i's k_chain launch in the CU slots its chains leave free; k_draws then
     // only multiplies by the adapted R. The first chunk's: one k_draws_rng launch.
     // Only while the chains leave slots free (at most two chain workgroups per CU, AUTO's FUSED range):
-    // past that the extra workgroups would wait behind the chains.
+    // past that the extra workgroups would wait behind the chains. And only while the units' dynamic LDS
+    // fits a CU beside k_chain's static __shared__ (k_chain<8>: 103,712 B, so up to ld = 468); longer
+    // rows keep the one-launch draws pass -- the same bits.
     const char* split_env = getenv("TCI_DRAWS_SPLIT");
     p.split = !p.walk && n_chains < 2 * (int64_t)std::max(n_cu, 1) && !(split_env && split_env[0] == '0') ? 1 : 0;
+    if (p.split) {
+      const int64_t chain_static = tci::dram_chain_static_lds_bytes(ctx->rpl, ctx->kp.n_seg);
+      if (chain_static < 0 || chain_static + tci::dram_draws_rng_lds_bytes(ld) > 160 * 1024) p.split = 0;
+    }
     double* dbuf[2] = {st.draws, st.draws};
     int rng_wgs = 0;
     if (p.split && !chunks.empty()) {

@@ -2613,6 +2613,25 @@ int dram_launch_draws_rng(const DramState& st, const DramParams& p, int64_t s_be
   return finish();
 }
 int64_t dram_draws_rng_lds_bytes(int64_t ld) { return draws_rng_lds_bytes(ld); }
+namespace {
+template <int RPL>
+const void* chain_kernel_r(int n_seg) {
+  switch (n_seg) {  // the instances launch_chain_t launches
+    case 1: return (const void*)k_chain<RPL, 1, (RPL <= 2 ? kChainEPW : 1)>;
+    case 2: return (const void*)k_chain<RPL, 2, (RPL <= 2 ? kChainEPW : 1)>;
+    case 3: return (const void*)k_chain<RPL, 3, (RPL <= 2 ? kChainEPW : 1)>;
+    case 4: return (const void*)k_chain<RPL, 4, (RPL <= 2 ? kChainEPW : 1)>;
+    default: return nullptr;
+  }
+}
+}  // namespace
+int64_t dram_chain_static_lds_bytes(int rpl, int n_seg) {
+  const void* k = rpl == 1 ? chain_kernel_r<1>(n_seg) : rpl == 2 ? chain_kernel_r<2>(n_seg)
+                : rpl == 4 ? chain_kernel_r<4>(n_seg) : rpl == 8 ? chain_kernel_r<8>(n_seg) : nullptr;
+  hipFuncAttributes a{};
+  if (k == nullptr || hipFuncGetAttributes(&a, k) != hipSuccess) return -1;
+  return (int64_t)a.sharedSizeBytes;
+}
 int dram_launch_chain(const DramState& st, const DramParams& p, const KParams& kp, int rpl, int64_t s_begin,
                       int64_t s_end, int with_records, void* stream, LaunchTimer* timer, const ChainNext* nx) {
   hipStream_t s = (hipStream_t)stream;

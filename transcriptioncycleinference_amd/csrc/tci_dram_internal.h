@@ -189,7 +189,13 @@ int64_t dram_chain_lds_bytes(int64_t ld, int rpl);
 // (ChainNext). Timer class 3.
 int dram_launch_draws_rng(const DramState& st, const DramParams& p, int64_t s_begin, int64_t s_end, int wgs,
                           void* stream, LaunchTimer* timer = nullptr);
-int64_t dram_draws_rng_lds_bytes(int64_t ld);  // LDS per workgroup of the fused engine
+// Dynamic LDS per workgroup of the split draws' units: k_draws_rng's whole LDS, and what a k_chain launch
+// that draws for the next chunk asks for on top of k_chain's static __shared__. tci_dram_run splits the
+// draws only while the two together fit a CU's 160 KiB.
+int64_t dram_draws_rng_lds_bytes(int64_t ld);
+// Static __shared__ of the k_chain instance dram_launch_chain runs for (rpl, n_seg), read from the code
+// object (hipFuncGetAttributes), so a change to the kernel's arrays is counted; -1 when it cannot be read.
+int64_t dram_chain_static_lds_bytes(int rpl, int n_seg);
 // LDS of the adaptation kernel dram_launch_adapt picks for (pmax, adaptint), dynamic plus the kernel's
 // static __shared__: the window's run table grows with adaptint (4 bytes per row), so tci_dram_run
 // refuses an adaptint past the CU's LDS before any launch.
