@@ -8,13 +8,17 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from transcriptioncycleinference_amd.build import FILE_FLAGS  # noqa: E402  (the per-source options of the build)
+
 args = [a for a in sys.argv[1:] if not a.startswith("-D")]
 defs = [a for a in sys.argv[1:] if a.startswith("-D")]
 src = args[0] if args and args[0] else f"{ROOT}/transcriptioncycleinference_amd/csrc/tci_dram.hip"
 filt = args[1] if len(args) > 1 else ""
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm",
        "-amdgpu-mfma-vgpr-form", "-fPIC", f"-I{ROOT}/include", f"-I{ROOT}/transcriptioncycleinference_amd/csrc",
-       "--cuda-device-only", "-c", src, "-o", "/tmp/_ru.o", "-Rpass-analysis=kernel-resource-usage", *defs]
+       "--cuda-device-only", "-c", src, "-o", "/tmp/_ru.o", "-Rpass-analysis=kernel-resource-usage", *defs,
+       *FILE_FLAGS.get(os.path.abspath(src), [])]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():

@@ -10,6 +10,7 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(PKG_DIR)
@@ -21,6 +22,11 @@ HEADERS = [os.path.join(REPO_ROOT, "include", "tci.h"), os.path.join(CSRC, "tci_
            os.path.join(CSRC, "tci_dram_internal.h"), os.path.join(CSRC, "tci_eval.h"), os.path.join(CSRC, "tci_csum.h"), os.path.join(CSRC, "tci_key.h")]
 LIB = os.path.join(PKG_DIR, "libtci.so")
 ARCH = "gfx950"  # CDNA4 only: the kernels use gfx950 instructions (v_bitop3_b32, permlane16/32 swaps)
+# Options of single sources (each compiled to an object of its own, then linked with the rest). The likelihood
+# kernels take their seven leading arguments (14 dwords: the row addressing, tci_kernels.hip) in user SGPRs at
+# wave launch instead of loading them from the kernarg segment. Only there: k_chain (tci_dram.hip) already spills
+# SGPRs, and the option would take 14 more from every kernel of a file.
+FILE_FLAGS = {os.path.join(CSRC, "tci_kernels.hip"): ["-mllvm", "-amdgpu-kernarg-preload-count=7"]}
 
 
 def hipcc() -> str:
@@ -43,13 +49,23 @@ def build_library(force: bool = False, verbose: bool = False, out: str = LIB, de
         return LIB
     # -amdgpu-mfma-vgpr-form: MFMA accumulators in VGPRs (the AGPR form made the compiler copy every
     # accumulator into AGPRs and back around each f64 MFMA of the draws pass and wait for it)
-    cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form",
-           "-fPIC", "-shared",
-           "-Wall", "-Wno-bitwise-instead-of-logical", "-Wno-pass-failed", "-I" + os.path.join(REPO_ROOT, "include"), "-I" + CSRC,
-           *[f"-D{d}" for d in (defines or [])], *SOURCES, "-o", out + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
+    base = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form",
+            "-fPIC",
+            "-Wall", "-Wno-bitwise-instead-of-logical", "-Wno-pass-failed", "-I" + os.path.join(REPO_ROOT, "include"), "-I" + CSRC,
+            *[f"-D{d}" for d in (defines or [])]]
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
+
+    with tempfile.TemporaryDirectory(prefix="tci_build_") as tmp:
+        objects = []
+        for src, flags in FILE_FLAGS.items():
+            obj = os.path.join(tmp, os.path.splitext(os.path.basename(src))[0] + ".o")
+            run([*base, *flags, "-c", src, "-o", obj])
+            objects.append(obj)
+        run([*base, "-shared", *objects, *[s for s in SOURCES if s not in FILE_FLAGS], "-o", out + ".tmp"])
     os.replace(out + ".tmp", out)
     return out
 

@@ -27,12 +27,29 @@ constexpr int waves_per_block() { return RPL <= 2 ? 1 : 4; }
 // 8; the LDS of a 4-wave block caps RPL = 4 at 4 waves/SIMD anyway).
 constexpr int lk_waves_per_eu(int rpl, int nseg) { return rpl * nseg <= 2 ? 8 : 6; }
 
-template <int RPL, int NSEG, int MODE>
-__global__ __launch_bounds__(64 * waves_per_block<RPL>()) __attribute__((amdgpu_waves_per_eu(lk_waves_per_eu(RPL, NSEG)))) void tci_cohort_kernel(const KParams kp, const double* __restrict__ theta,
-                                                         int64_t ld, const int32_t* __restrict__ cell_id,
-                                                         const uint8_t* __restrict__ active, int64_t B,
-                                                         double* __restrict__ out0, double* __restrict__ out1,
-                                                         int64_t ld_out, int64_t flag_words) {
+// Which variants take the row-addressing arguments first and in user SGPRs (kernarg preload: build.py
+// compiles this file with -amdgpu-kernarg-preload-count) and read everything else the prologue needs
+// in one round trip: the one-segment ones. From two segments up the variants sit at or near the 106
+// SGPRs a wave has, and 14 preloaded ones plus the entry loads added SGPR spills to half of them;
+// those keep KParams first -- a by-value struct ends the preloadable prefix, so nothing is preloaded
+// for them -- and the prologue as it was. (tci_tile_kernel keeps KParams first too: DESIGN.md §3.)
+constexpr bool lk_row_args_first(int nseg) { return nseg == 1; }
+
+// The rows of one likelihood launch. ENTRY (lk_row_args_first): the prologue is two round trips of
+// loads. At entry the row's cell id, its flag word and the KParams fields the evaluation addresses
+// with (cells, steps, points, thr, n_cells, cell_stride), all scalar loads issued together and waited
+// for once -- left alone, the compiler loads every kernel argument in the block that first uses it,
+// which made five dependent round trips of argument reads before the first record load. A
+// bounds-rejected row stores +Inf after that one wait. Then every other load of the evaluation at
+// once: records, meta and theta. (Vector loads issued ahead of the flag measured slower, 40.7 vs
+// 35.2 us; reading the theta scalars with the cell id fetched the theta lines of the rejected rows
+// too and was no faster: DESIGN.md §3, Appendix A.) Not ENTRY: cell id, then the flag, then the rest,
+// each argument read where it is first used.
+template <int RPL, int NSEG, int MODE, bool ENTRY>
+__device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __restrict__ theta, int64_t ld,
+                                            const int32_t* __restrict__ cell_id, const uint8_t* __restrict__ active,
+                                            int64_t B, double* __restrict__ out0, double* __restrict__ out1,
+                                            int64_t ld_out, int64_t flag_words) {
   constexpr int WAVE_DOUBLES = eval_lds_doubles<RPL>();  // {K,J} table / the two sim rows
   constexpr int kWavesPerBlock = waves_per_block<RPL>();
   __shared__ __attribute__((aligned(16))) double s_lds[kWavesPerBlock][WAVE_DOUBLES];
@@ -47,25 +64,47 @@ __global__ __launch_bounds__(64 * waves_per_block<RPL>()) __attribute__((amdgpu_
   return;
 #endif
 
-  // ---- the row's cell id and active flag, then every other load of the evaluation at once. (Also
-  //      reading the theta scalars with the cell id, one round trip earlier, measured no faster and
-  //      fetched the theta lines of the bounds-rejected rows too: DESIGN.md §3.)
-  const int c = __builtin_amdgcn_readfirstlane(cell_id[b]);
   // the flag through the scalar cache (one s_load_dword of its 4-byte word): a rejected row's wave
   // ends without queueing behind the other waves' vector loads (34.2 vs 35.4 us per bench launch,
   // r05h). flag_words: the rows whose whole word lies inside `active` (which is 4-byte aligned);
   // the last partial word and a misaligned array read the byte. (Evaluating only a list of the
   // in-bounds rows, built by a compaction kernel on the stream, measured slower: DESIGN.md
   // Appendix A, r06e/r06f.)
+  int c;
   bool act = true;
-  if (MODE == MODE_SS && active != nullptr)
-    act = b < flag_words ? ((reinterpret_cast<const uint32_t*>(active)[b >> 2] >> (8 * (b & 3))) & 0xffu) != 0
-                         : active[b] != 0;
+  int64_t n_cells = 0;
+  if (ENTRY) {
+    // the word is read beside the cell id, not after it: a row without a flag word reads its cell
+    // id's word there (an address that is always valid) and ignores it
+    const bool flagged = MODE == MODE_SS && active != nullptr;
+    const bool by_word = flagged && b < flag_words;
+    const uint32_t* wp = by_word ? reinterpret_cast<const uint32_t*>(active) + (b >> 2)
+                                 : reinterpret_cast<const uint32_t*>(cell_id + b);
+    c = __builtin_amdgcn_readfirstlane(cell_id[b]);
+    uint32_t w = MODE == MODE_SS ? __builtin_amdgcn_readfirstlane(*wp) : 0u;
+    const CellMeta* const k_cells = kp.cells;
+    const StepRec* const k_steps = MODE == MODE_FWD_RAW ? kp.steps_raw : kp.steps;
+    const PointRec* const k_points = kp.points;
+    const double* const k_thr = kp.thr;
+    const int64_t k_stride = kp.cell_stride;
+    n_cells = kp.n_cells;
+    // every scalar above is live here: the loads are issued before the first branch on any of them
+    // and share one wait (the compiler would sink each argument's load to its first use). Not
+    // volatile, and the cell id and the flag word pass through it: a volatile asm counts as a store,
+    // after which the compiler reads the cell's uniform records with vector loads.
+    asm("" : "+s"(c), "+s"(w) : "s"(k_cells), "s"(k_steps), "s"(k_points), "s"(k_thr), "s"(n_cells), "s"(k_stride));
+    if (flagged) act = by_word ? ((w >> (8 * (b & 3))) & 0xffu) != 0 : active[b] != 0;
+  } else {
+    c = __builtin_amdgcn_readfirstlane(cell_id[b]);
+    if (MODE == MODE_SS && active != nullptr)
+      act = b < flag_words ? ((reinterpret_cast<const uint32_t*>(active)[b >> 2] >> (8 * (b & 3))) & 0xffu) != 0
+                           : active[b] != 0;
+  }
   if (!act) {
     if (lane == 0) out0[b] = INFINITY;  // skipped proposal (bounds-rejected by the caller)
     return;
   }
-  if (c < 0 || ((kp.n_cells >> 31) == 0 && c >= (int)kp.n_cells)) {
+  if (c < 0 || (ENTRY ? (n_cells >> 31) == 0 && c >= (int)n_cells : (kp.n_cells >> 31) == 0 && c >= (int)kp.n_cells)) {
     write_nan<MODE>(lane, 0, b, out0, out1, ld_out);
     return;
   }
@@ -114,6 +153,25 @@ __global__ __launch_bounds__(64 * waves_per_block<RPL>()) __attribute__((amdgpu_
   if (MODE == MODE_SS && lane == 0) out0[b] = ss;
 }
 
+// Row-addressing arguments first (7 arguments, 14 dwords: what fits in user SGPRs beside the kernarg
+// pointer), KParams last.
+template <int RPL, int NSEG, int MODE>
+__global__ __launch_bounds__(64 * waves_per_block<RPL>()) __attribute__((amdgpu_waves_per_eu(lk_waves_per_eu(RPL, NSEG))))
+void tci_cohort_kernel(int64_t B, const int32_t* __restrict__ cell_id, const uint8_t* __restrict__ active,
+                       int64_t flag_words, const double* __restrict__ theta, int64_t ld, double* __restrict__ out0,
+                       double* __restrict__ out1, int64_t ld_out, const KParams kp) {
+  cohort_rows<RPL, NSEG, MODE, true>(kp, theta, ld, cell_id, active, B, out0, out1, ld_out, flag_words);
+}
+
+// KParams first: every argument from the kernarg segment (!lk_row_args_first).
+template <int RPL, int NSEG, int MODE>
+__global__ __launch_bounds__(64 * waves_per_block<RPL>()) __attribute__((amdgpu_waves_per_eu(lk_waves_per_eu(RPL, NSEG))))
+void tci_cohort_kernel_k(const KParams kp, const double* __restrict__ theta, int64_t ld,
+                         const int32_t* __restrict__ cell_id, const uint8_t* __restrict__ active, int64_t B,
+                         double* __restrict__ out0, double* __restrict__ out1, int64_t ld_out, int64_t flag_words) {
+  cohort_rows<RPL, NSEG, MODE, false>(kp, theta, ld, cell_id, active, B, out0, out1, ld_out, flag_words);
+}
+
 template <int RPL, int NSEG, int MODE>
 void launch_one(const KParams& kp, const double* theta, int64_t ld, const int32_t* cell_id, const uint8_t* active,
                 int64_t B, double* out0, double* out1, int64_t ld_out, hipStream_t stream) {
@@ -121,8 +179,12 @@ void launch_one(const KParams& kp, const double* theta, int64_t ld, const int32_
   const dim3 block(64 * kWavesPerBlock);
   const dim3 grid((unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock));
   const int64_t flag_words = active != nullptr && (reinterpret_cast<uintptr_t>(active) & 3) == 0 ? (B & ~(int64_t)3) : 0;
-  hipLaunchKernelGGL((tci_cohort_kernel<RPL, NSEG, MODE>), grid, block, 0, stream, kp, theta, ld, cell_id, active, B,
-                     out0, out1, ld_out, flag_words);
+  if constexpr (lk_row_args_first(NSEG))
+    hipLaunchKernelGGL((tci_cohort_kernel<RPL, NSEG, MODE>), grid, block, 0, stream, B, cell_id, active, flag_words,
+                       theta, ld, out0, out1, ld_out, kp);
+  else
+    hipLaunchKernelGGL((tci_cohort_kernel_k<RPL, NSEG, MODE>), grid, block, 0, stream, kp, theta, ld, cell_id, active,
+                       B, out0, out1, ld_out, flag_words);
 }
 
 template <int RPL, int NSEG>
