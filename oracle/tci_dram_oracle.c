@@ -61,6 +61,10 @@ typedef struct {
   double *chain;                                  /* [n_steps][n_chains][ld] or NULL */
   double *s2chain;                                /* [n_steps][n_chains] or NULL */
   double *R;                                      /* [n_chains][ld][ld] final proposal factor or NULL */
+  int64_t *dr_counts;                             /* [n_chains][4] delayed-rejection paths taken or NULL: stage 1 out of
+                                                   * bounds and stage 2 in bounds; stage 1 in bounds, rejected, and
+                                                   * stage 2 in bounds; stage 2 out of bounds; stage 2 accepted after
+                                                   * an out-of-bounds stage 1 */
 } or_dram_out;
 
 enum { P_NORM1 = 1, P_U1 = 2, P_NORM2 = 3, P_U2 = 4, P_GAMMA = 5 };
@@ -258,6 +262,7 @@ static int run_chain(const int64_t *offsets, const double *t, const double *ms2,
   int64_t nev = 1, nacc = 0, rej = 0, lasti = 0, nrows = 0;         /* rows: chain rows lasti+1 .. */
   double cw = 0.0;                                                  /* covupd's wsum (0: empty) */
   int64_t ns = 0;                                                   /* statistics rows so far */
+  int64_t drc[4] = {0, 0, 0, 0};                                    /* or_dram_out.dr_counts */
   double s2n = 0.0, s2sum = 0.0, qmean = 0.0, qm2 = 0.0;
   const double inv_ds = 1.0 / o->drscale;
   /* row 1: the initial state */
@@ -297,6 +302,8 @@ static int run_chain(const int64_t *offsets, const double *t, const double *ms2,
           w.y2[j] = th[j] + u;
           inb2 &= (w.y2[j] >= lo[j] && w.y2[j] <= hi[j]);
         }
+        if (!inb2) ++drc[2];
+        else ++drc[inb ? 1 : 0];
         if (inb2) {
           double ss2;
           if ((rc = oracle_ss_one(cs, tc, y1c, y2c, N, w.y2, sw, &ss2)) != 0) break;
@@ -317,6 +324,7 @@ static int run_chain(const int64_t *offsets, const double *t, const double *ms2,
             ss = ss2;
             pr = pr2;
             moved = 1;
+            if (!inb) ++drc[3];
           }
         }
       }
@@ -415,6 +423,8 @@ static int run_chain(const int64_t *offsets, const double *t, const double *ms2,
     out->sigma_std[c] = sqrt(qm2 / s2n);
     out->accept_rate[c] = o->n_steps > 1 ? (double)nacc / (double)(o->n_steps - 1) : 0.0;
     out->n_evals[c] = nev;
+    if (out->dr_counts)
+      for (int q = 0; q < 4; ++q) out->dr_counts[c * 4 + q] = drc[q];
     if (out->R) {
       double *Ro = out->R + (size_t)c * (size_t)ld * (size_t)ld;
       for (int64_t i = 0; i < ld * ld; ++i) Ro[i] = 0.0;

@@ -857,12 +857,22 @@ def _follows_the_restatement(c_oracle, shape, engine, expect):
     cells, cs, plan, o, keys, c = _restatement_case(shape, c_oracle)
     g, rpl = _restatement_run(shape, c_oracle, engine)
     n = cells.lengths[plan.cells]
+    _assert_follows_the_restatement(shape, engine, n, g, rpl, c, expect)
+    moved = np.any(g.chain[1:] != g.chain[:-1], axis=2).mean(axis=0)
+    assert np.median(moved) > 0.01, moved
+    return n
+
+
+def _assert_follows_the_restatement(shape, engine, n, g, rpl, c, expect):
+    """_follows_the_restatement's comparison of one GPU run g (rows per lane rpl) with the restatement's
+    outputs c for chains of n points each; shape and engine only label the messages
+    (tests/test_dram_options_gpu.py runs it on cases of its own)."""
     pmax, want_rpl, want_kernel = expect
     assert int(7 + n.max()) == pmax
     assert rpl == want_rpl
     assert _adapt_kernel(int(7 + n.max())) == want_kernel
     row_err = r_err = 0.0
-    for k in range(len(plan.cells)):
+    for k in range(len(n)):
         P = 7 + int(n[k])
         G, Cc = g.chain[:, k, :P], c["chain"][:, k, :P]
         row_err = max(row_err, float(np.max(np.abs(G - Cc) / np.maximum(np.abs(Cc), 1.0))))
@@ -870,7 +880,7 @@ def _follows_the_restatement(c_oracle, shape, engine, expect):
         r_err = max(r_err, float(np.max(np.abs(R - Rc)) / np.abs(Rc).max()))
     print(f"restatement {shape} {engine}: worst row error {row_err:.3e} (relative to max(|row|, 1)), "
           f"worst R error {r_err:.3e} of max|R|")
-    for k in range(len(plan.cells)):
+    for k in range(len(n)):
         P = 7 + int(n[k])
         G, Cc = g.chain[:, k, :P], c["chain"][:, k, :P]
         moved_g = np.any(G[1:] != G[:-1], axis=1)
@@ -884,9 +894,7 @@ def _follows_the_restatement(c_oracle, shape, engine, expect):
         np.testing.assert_allclose(g.sigma_mean[k], c["sigma_mean"][k], rtol=1e-9)
         R, Rc = g.qcov_R[k, :P, :P], c["R"][k, :P, :P]
         np.testing.assert_allclose(R, Rc, rtol=1e-9, atol=1e-9 * np.abs(Rc).max(), err_msg=f"{shape} chain {k}: R")
-    moved = np.any(g.chain[1:] != g.chain[:-1], axis=2).mean(axis=0)
-    assert np.median(moved) > 0.01, moved
-    return n
+    return row_err, r_err
 
 
 # Cells of 258 to 578 points, two per shape (ld is a run's largest P, so every length is a run of its own):
