@@ -35,14 +35,36 @@ constexpr int lk_waves_per_eu(int rpl, int nseg) { return rpl * nseg <= 2 ? 8 : 
 // for them -- and the prologue as it was. (tci_tile_kernel keeps KParams first too: DESIGN.md §3.)
 constexpr bool lk_row_args_first(int nseg) { return nseg == 1; }
 
+// Which variants also pin the launch constants of the evaluation beside round trip 2 (cohort_rows):
+// the one-wave-block ones among lk_row_args_first. With the pin tci_cohort_kernel<4,1,SS> took 130
+// instead of 98 VGPRs (3 waves per SIMD instead of 4), so RPL >= 4 keeps the prologue as it was.
+constexpr bool lk_pin_consts(int rpl, int nseg) { return lk_row_args_first(nseg) && rpl <= 2; }
+
+// The lanes' dR entries of a theta row for the pinned prologue (RPL <= 2), as cohort_rows loads them:
+// speculative (N unknown yet) and kept inside the row of ldi entries.
+template <int RPL>
+__device__ __forceinline__ void load_dr(const double* th, int ldi, int lane, double (&dr)[RPL]) {
+  typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+  const int g = RPL * lane;
+  if (RPL == 2 && 8 + g < ldi) {
+    const d2u x = *reinterpret_cast<const d2u*>(th + 7 + g);
+    dr[0] = x.x;
+    dr[1] = x.y;
+  } else {
+    dr[0] = 7 + g < ldi ? th[7 + g] : 0.0;
+    if (RPL == 2) dr[1] = 0.0;
+  }
+}
+
 // The rows of one likelihood launch. ENTRY (lk_row_args_first): the prologue is two round trips of
 // loads. At entry the row's cell id, its flag word and the KParams fields the evaluation addresses
 // with (cells, steps, points, thr, n_cells, cell_stride), all scalar loads issued together and waited
 // for once -- left alone, the compiler loads every kernel argument in the block that first uses it,
 // which made five dependent round trips of argument reads before the first record load. A
 // bounds-rejected row stores +Inf after that one wait. Then every other load of the evaluation at
-// once: records, meta and theta. (Vector loads issued ahead of the flag measured slower, 40.7 vs
-// 35.2 us; reading the theta scalars with the cell id fetched the theta lines of the rejected rows
+// once: records, meta and theta, and for RPL <= 2 (lk_pin_consts) the launch constants eval_wave
+// reads, so that no scalar load and no scalar wait is left inside the arithmetic. (Vector loads
+// issued ahead of the flag measured slower, 40.7 vs 35.2 us; reading the theta scalars with the cell id fetched the theta lines of the rejected rows
 // too and was no faster: DESIGN.md §3, Appendix A.) Not ENTRY: cell id, then the flag, then the rest,
 // each argument read where it is first used.
 template <int RPL, int NSEG, int MODE, bool ENTRY>
@@ -113,6 +135,9 @@ __device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __r
   // (scalar) compares instead of 64-bit vector ones
   const int ldi = (ld >> 31) != 0 ? 0x7fffffff : (int)ld;
   EvalIn<RPL> e;
+  constexpr bool PIN = ENTRY && lk_pin_consts(RPL, NSEG);
+  // PIN: the dR loads go ahead of the scalar loads, whose block the pin below ends with their wait
+  if constexpr (PIN) load_dr<RPL>(th, ldi, lane, e.dr);
   load_cell<RPL, MODE == MODE_FWD_RAW>(kp, c, lane, e);
   e.v = th[0];
   e.tau = th[1];
@@ -121,30 +146,48 @@ __device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __r
   e.b2 = th[4];
   e.A = th[5];
   e.R = th[6];
-  if (RPL >= 2) {
-    // dR pairs (8-B aligned 16-B loads): one load instruction per two entries where the pair is
-    // inside the row, entry by entry at the row's end (41.8 vs 42.3 us per bench launch, r03t)
-    typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+  if (!PIN) {
+    if (RPL >= 2) {
+      // dR pairs (8-B aligned 16-B loads): one load instruction per two entries where the pair is
+      // inside the row, entry by entry at the row's end (41.8 vs 42.3 us per bench launch, r03t)
+      typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
 #pragma unroll
-    for (int q = 0; q < RPL; q += 2) {
-      const int g = RPL * lane + q;
-      if (8 + g < ldi) {
-        const d2u x = *reinterpret_cast<const d2u*>(th + 7 + g);
-        e.dr[q] = x.x;
-        e.dr[q + 1] = x.y;
-      } else {
-        e.dr[q] = 7 + g < ldi ? th[7 + g] : 0.0;
-        e.dr[q + 1] = 0.0;
+      for (int q = 0; q < RPL; q += 2) {
+        const int g = RPL * lane + q;
+        if (8 + g < ldi) {
+          const d2u x = *reinterpret_cast<const d2u*>(th + 7 + g);
+          e.dr[q] = x.x;
+          e.dr[q + 1] = x.y;
+        } else {
+          e.dr[q] = 7 + g < ldi ? th[7 + g] : 0.0;
+          e.dr[q + 1] = 0.0;
+        }
       }
-    }
-  } else {
+    } else {
 #pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-      const int g = RPL * lane + q;
-      e.dr[q] = 7 + g < ldi ? th[7 + g] : 0.0;  // speculative (N unknown yet), kept inside the row
+      for (int q = 0; q < RPL; ++q) {
+        const int g = RPL * lane + q;
+        e.dr[q] = 7 + g < ldi ? th[7 + g] : 0.0;  // speculative (N unknown yet), kept inside the row
+      }
     }
   }
   const int N = e.cm.n;
+  if constexpr (PIN) {
+    // The launch constants eval_wave reads and the row's own scalars, all in flight with the records
+    // and theta and covered by the one wait before the row-length branch. Left to the compiler, the
+    // construct fields were loaded inside the counter scan and waited for before its branch: a
+    // third round trip, in the middle of the arithmetic (31.6 vs 32.5 us per bench launch,
+    // profiles/lk_wordstore/lk_levers_ab.json). The row's scalars pass through the pin too: with
+    // only some of the block's loads used here, the compiler sinks the others below the branch,
+    // into a round trip of their own.
+    static_assert(!PIN || NSEG == 1, "the pin lists the fields of one segment");
+    const SegParams& m = kp.ms2[0];
+    const SegParams& p = kp.pp7[0];
+    asm("" : : "s"(kp.force_exact), "s"(kp.L0), "s"(kp.emax), "s"(m.a), "s"(m.e), "s"(m.phi), "s"(m.k), "s"(m.ka),
+        "s"(p.a), "s"(p.e), "s"(p.phi), "s"(p.k), "s"(p.ka), "s"(e.v), "s"(e.tau), "s"(e.ton), "s"(e.b1), "s"(e.b2),
+        "s"(e.A), "s"(e.R), "s"(N), "s"(e.cm.d), "s"(e.cm.eps_v));
+    if (MODE != MODE_FWD_RAW) asm("" : : "s"(e.pt[RPL].w), "s"(e.pt[RPL].y1), "s"(e.pt[RPL].y2), "s"(e.pt[RPL].k));
+  }
   if (ldi < 7 + N) {  // a row shorter than 7 + N entries
     write_nan<MODE>(lane, N, b, out0, out1, ld_out);
     return;
