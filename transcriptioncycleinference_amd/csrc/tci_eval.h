@@ -52,10 +52,25 @@
 #include "tci_diag.h"
 #include "tci_internal.h"
 
+// Instruction diet of the one-segment RPL <= 2 likelihood kernels (eval_wave<.., LEAN>, cohort_rows): a mask
+// of levers, each of which leaves every decision and every SS bit as it was (DESIGN.md §3, Appendix A;
+// profiles/lk_valu/). The build ships the default; other values are the A/B builds of
+// scripts/lk_levers_ab.py. Every other variant, tci_tile_kernel and the chain kernels pass LEAN = 0.
+//   1  wave-uniform tests on the scalar unit: the theta exponent max, the prologue's 64-bit compares,
+//      the wave index of a one-wave block
+//   2  J table entries straight from the inclusive scan; the J scan's masked stages reuse the S scan's
+//      zeroed rows
+// Levers that were measured and not kept (votes on single compares in the distance cuts, scalar basal
+// operands, wave priority by phase): DESIGN.md Appendix A.
+#ifndef TCI_LK_VALU
+#define TCI_LK_VALU 3
+#endif
+
 namespace tci {
 
 namespace {
 
+constexpr int LK_SCALAR = 1, LK_SCANS = 2;
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_f64(double x) {
@@ -76,6 +91,29 @@ __device__ __forceinline__ double wave_incl_scan(double x) {
   x = x + dpp_f64<0x118, 0xF>(x);
   x = x + dpp_f64<0x142, 0xA>(x);
   x = x + dpp_f64<0x143, 0xC>(x);
+  return x;
+}
+
+// The destinations of a scan's two masked stages, kept for the next scan: row_bcast:15 writes rows 1 and
+// 3 of `a` and row_bcast:31 rows 2 and 3 of `b`, so rows 0 and 2 of `a` and rows 0 and 1 of `b` -- the
+// rows the same stages of the next scan leave alone and need zero -- still hold the zeros they started
+// with. A scan that takes them as its `old` operand needs no zero moves of its own (4 VALU).
+struct ScanOld {
+  int a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
+};
+
+// wave_incl_scan with the masked stages' destinations kept in z: the same adds in the same order
+__device__ __forceinline__ double wave_incl_scan(double x, ScanOld& z) {
+  x = x + dpp_f64<0x111, 0xF>(x);
+  x = x + dpp_f64<0x112, 0xF>(x);
+  x = x + dpp_f64<0x114, 0xF>(x);
+  x = x + dpp_f64<0x118, 0xF>(x);
+  z.a_lo = __builtin_amdgcn_update_dpp(z.a_lo, __double2loint(x), 0x142, 0xA, 0xF, true);
+  z.a_hi = __builtin_amdgcn_update_dpp(z.a_hi, __double2hiint(x), 0x142, 0xA, 0xF, true);
+  x = x + __hiloint2double(z.a_hi, z.a_lo);
+  z.b_lo = __builtin_amdgcn_update_dpp(z.b_lo, __double2loint(x), 0x143, 0xC, 0xF, true);
+  z.b_hi = __builtin_amdgcn_update_dpp(z.b_hi, __double2hiint(x), 0x143, 0xC, 0xF, true);
+  x = x + __hiloint2double(z.b_hi, z.b_lo);
   return x;
 }
 
@@ -162,6 +200,14 @@ __device__ __forceinline__ double max_f64(double a, double b) {
 // Exponent field of a double: all ones iff the value is +-Inf or NaN. The max over the
 // wave-uniform theta entries stays on the scalar unit (isfinite() would be a vector compare each).
 __device__ __forceinline__ unsigned exp_bits(double x) { return (unsigned)__double2hiint(x) & 0x7ff00000u; }
+
+// max of two wave-uniform words on the scalar unit, whatever the compiler would choose (it moved half
+// of the theta exponent max of eval_wave to v_max3_u32 and three moves)
+__device__ __forceinline__ unsigned smax_u32(unsigned a, unsigned b) {
+  unsigned r;
+  asm("s_max_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+  return r;
+}
 
 // Stem-loop occupancy of one polymerase at position p (GetFluorFromPolPos.m:50-52):
 //   phi                 if e < p < L
@@ -360,8 +406,8 @@ __device__ __forceinline__ void load_cell(const KParams& kp, int c, int lane, Ev
 // to out0/out1 row b) by one wavefront, on its LDS (2 * (2*64*RPL + 2*RPL) doubles). Needs
 // 2 <= N = e.cm.n <= 64*RPL + 1. aux (MODE_SS, optional): a per-lane partial on entry, its wave sum
 // (lane63(wave_incl_scan), the same bits) on return -- reduced together with the SS (the DRAM chain
-// kernel's prior).
-template <int RPL, int NSEG, int MODE>
+// kernel's prior). LEAN: the TCI_LK_VALU levers (RPL <= 2, one segment, theta in SGPRs; no aux).
+template <int RPL, int NSEG, int MODE, int LEAN = 0>
 __device__ __forceinline__ double eval_wave(const KParams& kp, const EvalIn<RPL>& e, int lane, double* lds,
                                             int64_t b, double* __restrict__ out0, double* __restrict__ out1,
                                             int64_t ld_out, double* aux = nullptr) {
@@ -393,8 +439,14 @@ __device__ __forceinline__ double eval_wave(const KParams& kp, const EvalIn<RPL>
 
   // ---- per-step setup: R_full = R + dR (SumofSquares...m:45); R<0 -> 0 (ConstantElongationSim.m:36)
   double prod[RPL];
-  const unsigned ebits = max(max(max(exp_bits(v), exp_bits(tau)), max(exp_bits(ton), exp_bits(b1))),
-                            max(max(exp_bits(b2), exp_bits(A)), exp_bits(R)));
+  static_assert(LEAN == 0 || (RPL <= 2 && NSEG == 1), "the levers are those of the one-segment RPL <= 2 kernels");
+  unsigned ebits;
+  if constexpr (LEAN & LK_SCALAR)
+    ebits = smax_u32(smax_u32(smax_u32(exp_bits(v), exp_bits(tau)), smax_u32(exp_bits(ton), exp_bits(b1))),
+                     smax_u32(smax_u32(exp_bits(b2), exp_bits(A)), exp_bits(R)));
+  else
+    ebits = max(max(max(exp_bits(v), exp_bits(tau)), max(exp_bits(ton), exp_bits(b1))),
+                max(max(exp_bits(b2), exp_bits(A)), exp_bits(R)));
   const bool fin = ebits != 0x7ff00000u;
   uint64_t nonfinite = 0;
 #pragma unroll
@@ -413,6 +465,7 @@ __device__ __forceinline__ double eval_wave(const KParams& kp, const EvalIn<RPL>
 
   // ---- loading counter (ConstantElongationSim.m:60-61): DPP prefix sum + exactness proof
   double K[RPL];
+  ScanOld scan_old;  // LK_SCANS: the S scan's masked-stage destinations, the J scan's `old`
   {
     double loc[RPL];
     double s = prod[0];  // (0.0 + prod[0] only turns a -0 into +0, which no count can see)
@@ -425,7 +478,7 @@ __device__ __forceinline__ double eval_wave(const KParams& kp, const EvalIn<RPL>
 #if TCI_ABLATE & 8
     const double excl = 0.0;
 #else
-    const double excl = wave_shr1(wave_incl_scan(s));
+    const double excl = wave_shr1((LEAN & LK_SCANS) ? wave_incl_scan(s, scan_old) : wave_incl_scan(s));
 #endif
     uint64_t amb = 0;
 #pragma unroll
@@ -502,13 +555,34 @@ __device__ __forceinline__ double eval_wave(const KParams& kp, const EvalIn<RPL>
           jloc[q] = js;
         }
       }
-      const double jexcl = wave_incl_scan(js) - js;  // integers < 2^53: exact, as a shifted scan
+      // integers < 2^53: exact in any order. jscan: the exclusive scan, as a shifted inclusive one; with
+      // LK_SCANS the inclusive scan itself
+      double jscan;
+      if constexpr ((LEAN & LK_SCANS) != 0)
+        jscan = wave_incl_scan(js, scan_old);
+      else
+        jscan = wave_incl_scan(js) - js;
       // KJ[i], i in [-SLOTS, SLOTS): the SLOTS entries below i = 0 are zeros (KJTable: transposed)
       KJTable<RPL> KJ(lds, lane);
+      if constexpr ((LEAN & LK_SCANS) != 0) {
+        // The lane's last entry IS the inclusive scan, and the ones before it take the later steps'
+        // terms off again: one exact fma per entry below the last, instead of a subtract for the
+        // exclusive scan and an add per entry (the same integers).
+        double Jq[RPL];
+        Jq[RPL - 1] = jscan;
 #pragma unroll
-      for (int q = 0; q < RPL; ++q) {
-        KJ.put(q, make_double2(K[q], jexcl + jloc[q]));
-        KJ.put(q - SLOTS, make_double2(0.0, 0.0));  // [-SLOTS, 0): every index a row reads
+        for (int q = RPL - 1; q >= 1; --q) Jq[q - 1] = fma(-(double)(RPL * lane + q), K[q] - K[q - 1], Jq[q]);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+          KJ.put(q, make_double2(K[q], Jq[q]));
+          KJ.put(q - SLOTS, make_double2(0.0, 0.0));
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+          KJ.put(q, make_double2(K[q], jscan + jloc[q]));
+          KJ.put(q - SLOTS, make_double2(0.0, 0.0));  // [-SLOTS, 0): every index a row reads
+        }
       }
       wave_sync();
       double kvdM[NSEG], kaM[NSEG], kvdP[NSEG], kaP[NSEG];

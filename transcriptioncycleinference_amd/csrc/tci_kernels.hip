@@ -21,7 +21,7 @@ namespace {
 template <int RPL>
 constexpr int waves_per_block() { return RPL <= 2 ? 1 : 4; }
 
-// Waves per SIMD the register budget is set for: 8 while RPL * NSEG <= 2 (58 VGPRs at RPL = 2,
+// Waves per SIMD the register budget is set for: 8 while RPL * NSEG <= 2 (61 VGPRs at RPL = 2,
 // NSEG = 1, no spill; 34.4 vs 36.0 us per bench launch against 6 in one process,
 // profiles/r03_likelihood/r03occ1_ab.json; 7: 35.8), 6 above (RPL = 2 with two segments spills at
 // 8; the LDS of a 4-wave block caps RPL = 4 at 4 waves/SIMD anyway).
@@ -56,6 +56,23 @@ __device__ __forceinline__ void load_dr(const double* th, int ldi, int lane, dou
   }
 }
 
+// a < b for wave-uniform non-negative a, b (their difference cannot overflow): the sign of the
+// difference's high word, s_sub / s_subb / s_cmp, where a 64-bit order compare is a VALU one. The
+// barrier keeps the compiler from widening the test to the 64-bit difference again.
+__device__ __forceinline__ bool lk_lt(int64_t a, int64_t b) {
+  int32_t hi = (int32_t)(((uint64_t)a - (uint64_t)b) >> 32);
+  asm("" : "+s"(hi));
+  return hi < 0;
+}
+
+// 0 <= x < 2^31 for a wave-uniform x: the word above bit 30 is zero. The barrier keeps the compiler from
+// turning the test back into an order compare.
+__device__ __forceinline__ bool lk_fits31(int64_t x) {
+  uint64_t hi = (uint64_t)x >> 31;
+  asm("" : "+s"(hi));
+  return hi == 0;
+}
+
 // The rows of one likelihood launch. ENTRY (lk_row_args_first): the prologue is two round trips of
 // loads. At entry the row's cell id, its flag word and the KParams fields the evaluation addresses
 // with (cells, steps, points, thr, n_cells, cell_stride), all scalar loads issued together and waited
@@ -76,10 +93,17 @@ __device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __r
   constexpr int kWavesPerBlock = waves_per_block<RPL>();
   __shared__ __attribute__((aligned(16))) double s_lds[kWavesPerBlock][WAVE_DOUBLES];
 
+  // The levers of TCI_LK_VALU (tci_eval.h): the pinned variants only, so every other one compiles as it did.
+  constexpr int LEAN = ENTRY && lk_pin_consts(RPL, NSEG) ? TCI_LK_VALU : 0;
+  constexpr bool SCALAR = (LEAN & LK_SCALAR) != 0;
   const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // SCALAR: a one-wave block's wave index is 0 (no v_readfirstlane, no LDS offset to add per address)
+  const int wid = SCALAR && kWavesPerBlock == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + wid;
-  if (b >= B) return;
+  // SCALAR: the 64-bit order compares of wave-uniform values, which the scalar unit lacks and the
+  // compiler does with a move and a v_cmp each, as the sign of a difference or as a shifted word
+  // that is zero (lk_lt / lk_fits31).
+  if (SCALAR ? !lk_lt(b, B) : b >= B) return;
   double* lds = s_lds[wid];
 #if TCI_ABLATE & 32
   if (lane == 0) out0[b] = 1.0;  // launch floor (diagnostics only)
@@ -99,7 +123,7 @@ __device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __r
     // the word is read beside the cell id, not after it: a row without a flag word reads its cell
     // id's word there (an address that is always valid) and ignores it
     const bool flagged = MODE == MODE_SS && active != nullptr;
-    const bool by_word = flagged && b < flag_words;
+    const bool by_word = flagged && (SCALAR ? lk_lt(b, flag_words) : b < flag_words);
     const uint32_t* wp = by_word ? reinterpret_cast<const uint32_t*>(active) + (b >> 2)
                                  : reinterpret_cast<const uint32_t*>(cell_id + b);
     c = __builtin_amdgcn_readfirstlane(cell_id[b]);
@@ -126,14 +150,15 @@ __device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __r
     if (lane == 0) out0[b] = INFINITY;  // skipped proposal (bounds-rejected by the caller)
     return;
   }
-  if (c < 0 || (ENTRY ? (n_cells >> 31) == 0 && c >= (int)n_cells : (kp.n_cells >> 31) == 0 && c >= (int)kp.n_cells)) {
+  if (c < 0 || (SCALAR ? lk_fits31(n_cells) && c >= (int)n_cells
+                : ENTRY ? (n_cells >> 31) == 0 && c >= (int)n_cells : (kp.n_cells >> 31) == 0 && c >= (int)kp.n_cells)) {
     write_nan<MODE>(lane, 0, b, out0, out1, ld_out);
     return;
   }
   const double* th = theta + b * ld;
   // the row length in 32 bits (ld > 0): the lanes' index compares and the row check in 32-bit
   // (scalar) compares instead of 64-bit vector ones
-  const int ldi = (ld >> 31) != 0 ? 0x7fffffff : (int)ld;
+  const int ldi = (SCALAR ? !lk_fits31(ld) : (ld >> 31) != 0) ? 0x7fffffff : (int)ld;
   EvalIn<RPL> e;
   constexpr bool PIN = ENTRY && lk_pin_consts(RPL, NSEG);
   // PIN: the dR loads go ahead of the scalar loads, whose block the pin below ends with their wait
@@ -192,7 +217,7 @@ __device__ __forceinline__ void cohort_rows(const KParams& kp, const double* __r
     write_nan<MODE>(lane, N, b, out0, out1, ld_out);
     return;
   }
-  const double ss = eval_wave<RPL, NSEG, MODE>(kp, e, lane, lds, b, out0, out1, ld_out);
+  const double ss = eval_wave<RPL, NSEG, MODE, LEAN>(kp, e, lane, lds, b, out0, out1, ld_out);
   if (MODE == MODE_SS && lane == 0) out0[b] = ss;
 }
 
