@@ -121,7 +121,8 @@ int tci_ssfun(tci_ctx* ctx, int32_t cell, const double* theta, int64_t P, double
 /* Batched forward model, HOST pointers, synchronous: simulated MS2 (already x A) and
  * PP7 at the acquisition times of each row's cell. Row b writes N(cell) values at
  * ms2_out[b*ld_out] and pp7_out[b*ld_out] (ld_out >= N of the cell); NaN where the
- * grid does not cover a time (interp1 out of range). */
+ * grid does not cover a time (interp1 out of range). The entries from N to ld_out of a
+ * row are set to NaN. */
 int tci_forward(tci_ctx* ctx, const double* theta, int64_t ld_theta, const int32_t* cell_id, int64_t B,
                 int grid_mode, double* ms2_out, double* pp7_out, int64_t ld_out);
 

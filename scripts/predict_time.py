@@ -40,7 +40,7 @@ def host_route(lk, theta, cid, probs):
                 lo = int(np.floor(h))
                 f = h - lo
                 bands[:, q] = x[:, lo] + f * (x[:, lo + 1] - x[:, lo]) if lo + 1 < S else x[:, S - 1]
-        for k, c in enumerate(cid):   # tci_forward leaves the padding past a cell's N undefined; predict writes NaN
+        for k, c in enumerate(cid):   # NaN past a cell's N, as predict writes it
             bands[k, :, int(lk.lengths[c]):] = np.nan
         out.append(bands)
     return out

@@ -850,16 +850,20 @@ def _restatement_run(shape, c_oracle, engine, **opts):
     return g, rpl
 
 
-def _follows_the_restatement(c_oracle, shape, engine, expect):
+def _follows_the_restatement(c_oracle, shape, engine, expect, every_chain_moves=False):
     """The assertions of test_gpu_chains_follow_the_cpu_restatement_at_config_shapes for one shape and
     engine; expect = (largest P, rows per lane, adaptation kernel). Prints the worst row and R errors
-    before it asserts them. Returns the cell lengths."""
+    before it asserts them. every_chain_moves: each chain accepts more than 1 % of its steps, not only the
+    median chain (so a short chain frozen by a wrong proposal factor cannot pass). Returns the cell lengths."""
     cells, cs, plan, o, keys, c = _restatement_case(shape, c_oracle)
     g, rpl = _restatement_run(shape, c_oracle, engine)
     n = cells.lengths[plan.cells]
     _assert_follows_the_restatement(shape, engine, n, g, rpl, c, expect)
     moved = np.any(g.chain[1:] != g.chain[:-1], axis=2).mean(axis=0)
     assert np.median(moved) > 0.01, moved
+    if every_chain_moves:
+        print(f"restatement {shape} {engine}: share of steps that move, per chain: {np.round(moved, 3).tolist()}")
+        assert np.all(moved > 0.01), moved
     return n
 
 
@@ -910,6 +914,13 @@ def _assert_follows_the_restatement(shape, engine, n, g, rpl, c, expect):
 #   rpl8_last:         N = 513, P = 520: the largest register-resident cell;
 #   tile_first:        N = 514: the long-cell likelihood kernel (rows_per_lane == 0), the batched engine only;
 #   tile_carry:        N = 578: S = N - 1 = 577 steps, one past a multiple of 64.
+# Chains far narrower than ld, one cell per length (a tuple of lengths): ld is the run's largest P, the draws
+# pass computes z * R for every chain at that width with the draws kernel that ld picks, and the adaptation
+# kernel is picked from the largest P too, so the short chains run on kernels their own P never selects.
+#   ragged_rpl4:       N = 2 / 3 / 66 / 130 / 200 (P = 9 .. 207) on k_adapt_mfma<8, 13, 12>, an RPL = 4 context;
+#   ragged_rpl8:       N = 2 / 65 / 129 / 258 / 300: the P = 9 and P = 72 chains adapted by k_adapt_gt; ld = 307,
+#                      so WALK's narrow (32-row) draws kernel; an RPL = 8 context;
+#   ragged_tile:       N = 2 / 129 / 513 / 514: the long-cell likelihood kernel for every chain, batched only.
 _ALL_ENGINES = ("fused", "walk", "batched")
 RESTATEMENT_LONG_SHAPES = {
     "rpl8_first": (2, 258, "builtin", 20201040, _ALL_ENGINES),
@@ -921,11 +932,16 @@ RESTATEMENT_LONG_SHAPES = {
     "rpl8_last": (2, 513, "builtin", 20201046, _ALL_ENGINES),
     "tile_first": (2, 514, "builtin", 20201047, ("batched",)),
     "tile_carry": (2, 578, "builtin", 20201048, ("batched",)),
+    "ragged_rpl4": (1, (2, 3, 66, 130, 200), "builtin", 20201049, _ALL_ENGINES),
+    "ragged_rpl8": (1, (2, 65, 129, 258, 300), "builtin", 20201050, _ALL_ENGINES),
+    "ragged_tile": (1, (2, 129, 513, 514), "builtin", 20201051, ("batched",)),
 }
+RAGGED_SHAPES = ("ragged_rpl4", "ragged_rpl8", "ragged_tile")
 RESTATEMENT_LONG_EXPECT = {
     "rpl8_first": (265, 8, "gt"), "walk_wide_last": (299, 8, "gt"), "walk_narrow_first": (300, 8, "gt"),
     "rpl8_two_segment": (307, 8, "gt"), "split_last": (468, 8, "gt"), "split_over": (469, 8, "gt"),
     "rpl8_last": (520, 8, "gt"), "tile_first": (521, 0, "gt"), "tile_carry": (585, 0, "gt"),
+    "ragged_rpl4": (207, 4, "mfma<8,13,12>"), "ragged_rpl8": (307, 8, "gt"), "ragged_tile": (521, 0, "gt"),
 }
 _OUTPUT_FIELDS = ("chain", "s2chain", "mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
                   "qcov_R")
@@ -942,9 +958,13 @@ def test_gpu_chains_follow_the_cpu_restatement_at_long_shapes(c_oracle, shape, e
     cells of 258 to 578 points (RESTATEMENT_LONG_SHAPES): the RPL = 8 instances of the in-kernel evaluation,
     the draws pass with R read from global memory and k_adapt_gt up to P = 520, each side of WALK's switch
     between its two draws kernels and of the split draws' LDS limit, and the batched engine on the long-cell
-    likelihood kernel."""
-    n = _follows_the_restatement(c_oracle, shape, engine, RESTATEMENT_LONG_EXPECT[shape])
-    assert np.all(n == RESTATEMENT_LONG_SHAPES[shape][1])
+    likelihood kernel; and on runs whose chains are far narrower than ld (the ragged shapes, one cell per
+    length), where every chain must move as well."""
+    n = _follows_the_restatement(c_oracle, shape, engine, RESTATEMENT_LONG_EXPECT[shape],
+                                 every_chain_moves=shape in RAGGED_SHAPES)
+    n_cells, lengths = RESTATEMENT_LONG_SHAPES[shape][:2]
+    lengths = lengths if isinstance(lengths, tuple) else (lengths,)
+    assert n.tolist() == [npts for npts in lengths for _ in range(n_cells)]
     ld = int(7 + n.max())
     walk_wide_lds = (2 * 8 * 4 * ld + 16) * 8  # draws_lds_bytes(ld, kDrawMTWalk); wide while <= 150 KiB
     if shape == "walk_wide_last":
@@ -955,9 +975,16 @@ def test_gpu_chains_follow_the_cpu_restatement_at_long_shapes(c_oracle, shape, e
         assert _restatement_case(shape, c_oracle)[1].n_seg == 2
     if shape == "tile_carry":
         assert (int(n.max()) - 1) % 64 == 1
+    if shape == "ragged_rpl4":  # P = 9 .. 207, every chain on the kernel the P = 207 chain selects
+        assert (7 + n).tolist() == [9, 10, 73, 137, 207] and _adapt_kernel(9) != _adapt_kernel(207)
+    if shape == "ragged_rpl8":  # k_adapt_gt for chains of one and five tiles; WALK's narrow draws kernel
+        assert (7 + n).tolist() == [9, 72, 136, 265, 307] and _adapt_kernel(72) != "gt"
+        assert ld == 307 and walk_wide_lds > 150 * 1024
+    if shape == "ragged_tile":
+        assert (7 + n).tolist() == [9, 136, 520, 521]
 
 
-@pytest.mark.parametrize("shape", ["tile_first", "tile_carry"])
+@pytest.mark.parametrize("shape", ["tile_first", "tile_carry", "ragged_tile"])
 def test_long_cell_shapes_refuse_the_fused_engines_and_auto_runs_batched(c_oracle, shape):
     """Cells of 514 and more points (rows_per_lane == 0): FUSED and WALK are refused with TCI_ERANGE, and
     AUTO gives the batched engine's bits (whose chains the restatement test pins)."""

@@ -239,3 +239,74 @@ def test_oracles_agree_on_multi_segment_constructs(n, cname, c_oracle):
         mn, pn = O.forward_interp(ocs, t, r)
         np.testing.assert_array_equal(m, mn, err_msg=f"interp ms2 row {i}")
         np.testing.assert_array_equal(p, pn, err_msg=f"interp pp7 row {i}")
+
+
+def _ragged_reference(c_oracle, ctx, cname):
+    import ragged_cases as RC
+    import variant_rows as VR
+    from transcriptioncycleinference_amd import from_lists
+
+    k = RC.case(ctx, cname)
+    cells = from_lists(k.cl)
+    ocs = VR.oracle_construct(VR.matrix_constructs()[cname])
+    ss, st = c_oracle.ss_batch(cells.offsets, cells.t, cells.ms2, cells.pp7, ocs, k.theta, k.cid)
+    return k, cells, ocs, ss, st
+
+
+@pytest.mark.parametrize("ctx,cname", [("tile", "builtin"), ("rpl8", "two_segment"), ("rpl4", "seg4")])
+def test_oracles_agree_on_the_ragged_rows(ctx, cname, c_oracle):
+    """The C oracle's values on the ragged contexts' rows -- what tests/test_ragged_contexts_gpu.py trusts
+    -- pinned by the numpy restatement, bit for bit: one (context, construct) per construct, about 100 of
+    its finite rows (the first row of every family of every cell and every n-th row beside them), each row cut to its own 7 + N entries (the C oracle reads it inside a row of the context's ld)."""
+    k, cells, ocs, ss, st = _ragged_reference(c_oracle, ctx, cname)
+    fin = np.flatnonzero(k.finite)
+    first = {(int(k.cid[b]), k.what[b]): b for b in fin[::-1]}   # the first row of every family of every cell
+    pick = np.unique(np.concatenate([list(first.values()), fin[::max(1, len(fin) // 40)]]))
+    assert 80 <= len(pick) <= 130, len(pick)
+    assert set(k.n[pick].tolist()) == set(k.n.tolist())
+    assert set(k.what[pick].tolist()) == set(k.what[k.finite].tolist())
+    for b in pick:
+        c, n = int(k.cid[b]), int(k.n[b])
+        assert st[b] == 0
+        assert ss[b] == O.sum_of_squares(ocs, cells.data_struct(c), k.theta[b, :7 + n]), (b, n, k.what[b])
+
+
+def test_ragged_cases_hold_what_they_promise(c_oracle):
+    """tests/ragged_cases.py on the host: the class each context's longest cell selects (pick_rpl's table,
+    tci_api.cpp), the row caps, a 2-point cell without threshold rows, and the reference's share of
+    numbers -- the oracle's status is 0 and its SS finite on every row outside the non-finite families
+    (for a non-finite theta the oracle is no reference: MATLAB's nansum gives a number or the index
+    error there, where include/tci.h promises NaN), whose size is what the families imply. The oracle
+    reads nothing from the unused last rate on: garbage there changes no bit of it."""
+    import ragged_cases as RC
+
+    def rpl_of(n):  # pick_rpl: N <= 64 RPL + 1, else the long-cell kernel
+        return next((r for r in (1, 2, 4, 8) if n <= 64 * r + 1), 0)
+
+    assert len(RC.CASES) == 11
+    for ctx, cname in RC.CASES:
+        k, cells, ocs, ss, st = _ragged_reference(c_oracle, ctx, cname)
+        lengths, rpl = RC.CONTEXTS[ctx]
+        assert rpl_of(max(lengths)) == rpl == k.rpl and k.ld == 7 + max(lengths)
+        assert sorted(set(k.n.tolist())) == sorted(lengths)
+        assert len(k.cl) == len(lengths) + sum(n in RC.TWIN_LENGTHS for n in lengths)
+        per_cell = np.bincount(k.cid, minlength=len(k.cl))
+        assert per_cell.min() >= 16 and per_cell.max() <= RC.MAX_ROWS_PER_CELL
+        assert len(k.cid) <= RC.MAX_ROWS_PER_CASE
+        cut = np.isin(k.what, ("on a cut", "near a cut"))
+        assert not np.any(cut & (k.n == 2)) and not np.any(cut & (k.n == RC.LONG_CELL))
+        for c in range(len(k.cl)):
+            n = len(k.cl[c][0])
+            if n >= 3 and n != RC.LONG_CELL and not k.twin[c]:
+                assert 2 <= (cut & (k.cid == c)).sum() <= 2 * RC.MAX_CUT_ROWS
+            assert ((k.what == "integer counter") & (k.cid == c)).sum() == (29 if k.twin[c] else 0)
+        # 7 scalars and 2 values for each of the first and the last step's dR (one step at N = 2)
+        primary = [len(k.cl[c][0]) for c in range(len(k.cl)) if not k.twin[c] and len(k.cl[c][0]) != RC.LONG_CELL]
+        assert (~k.finite).sum() == sum(7 + (2 if n == 2 else 4) for n in primary)
+        assert np.all(st[k.finite] == 0), (ctx, cname, st[k.finite & (st != 0)][:5])
+        assert np.all(np.isfinite(ss[k.finite])), (ctx, cname)
+        g = RC.padding_garbage(k.theta, k.n)
+        x = g[np.arange(len(g)), 7 + k.n - 1]
+        assert np.all(np.isnan(x) | (x == np.inf) | (x == -1e300)) and np.array_equal(g[:, :8], k.theta[:, :8], equal_nan=True)
+        ss_g, _ = c_oracle.ss_batch(cells.offsets, cells.t, cells.ms2, cells.pp7, ocs, g, k.cid)
+        assert ss_g[k.finite].tobytes() == ss[k.finite].tobytes(), (ctx, cname)

@@ -135,6 +135,30 @@ def test_long_cell(construct):
         check(L, samples(rng, L.lengths, cid, 8), cid)
 
 
+def test_short_cells_in_an_eight_rows_per_lane_context():
+    """The cells of 2, 65 and 258 points of a context whose longest cell has 513 (tests/ragged_cases.py,
+    RPL = 8) in one call, S = 37, both grids: the forward kernel on padded records, ld_out = 258 with 256
+    and 193 NaN entries past the short cells' points, theta rows of 520 entries."""
+    import ragged_cases as RC
+    from transcriptioncycleinference_amd import Likelihood, from_lists
+
+    k = RC.case("rpl8", "builtin")
+    lengths = [len(c[0]) for c in k.cl]
+    cid = np.array([next(c for c in range(len(lengths)) if lengths[c] == n and not k.twin[c]) for n in (2, 258, 65)],
+                   np.int32)
+    with Likelihood(from_lists(k.cl), "P2P-MS2v5-LacZ-PP7v4") as L:
+        assert L.info["rows_per_lane"] == 8 and L.lengths[cid].tolist() == [2, 258, 65]
+        theta = samples(np.random.default_rng(258), L.lengths, cid, 37, ld=k.ld)
+        assert theta.shape == (3, 37, 520)
+        for grid in ("raw", "interp"):
+            gm, gp = check(L, theta, cid, grid=grid)
+            assert gm.shape == gp.shape == (3, len(PROBS), 258)
+            for i, n in enumerate((2, 258, 65)):
+                assert np.all(np.isnan(gm[i, :, n:])) and np.all(np.isnan(gp[i, :, n:]))
+                if grid == "raw":  # the raw grid covers every acquisition time
+                    assert np.all(np.isfinite(gm[i, :, :n])) and np.all(np.isfinite(gp[i, :, :n]))
+
+
 def test_four_segment_construct():
     from transcriptioncycleinference_amd import Likelihood, from_lists
     from transcriptioncycleinference_amd.construct import Construct

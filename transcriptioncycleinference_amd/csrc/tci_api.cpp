@@ -516,6 +516,10 @@ int tci_forward(tci_ctx* ctx, const double* theta, int64_t ld_theta, const int32
   hipStream_t st = ctx->stream;
   TCI_HIP(ctx, hipMemcpyAsync(ctx->d_theta, theta, nth * sizeof(double), hipMemcpyHostToDevice, st));
   TCI_HIP(ctx, hipMemcpyAsync(ctx->d_cell, cell_id, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  // a row's kernel writes its N values only and whole rows are copied back: without this the entries
+  // past N came back as whatever the scratch buffers held (earlier rows, SS values). All-ones is a NaN.
+  TCI_HIP(ctx, hipMemsetAsync(ctx->d_out0, 0xFF, nout * sizeof(double), st));
+  TCI_HIP(ctx, hipMemsetAsync(ctx->d_out1, 0xFF, nout * sizeof(double), st));
   rc = run(ctx, grid_mode == TCI_GRID_RAW ? tci::MODE_FWD_RAW : tci::MODE_FWD_INTERP, ctx->d_theta, ld_theta,
            ctx->d_cell, nullptr, B, ctx->d_out0, ctx->d_out1, ld_out, (void*)st);
   if (rc != TCI_OK) return rc;
