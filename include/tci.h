@@ -159,7 +159,9 @@ typedef struct {
                            adaptint, or the draws buffer's 2 GiB cap); same chains whatever it is */
   const int64_t* chain_keys; /* optional [n_chains]: chain c draws from RNG stream chain_keys[c]
                                 (NULL: stream c). Keying chains by their global cell index makes a
-                                shard of a run (its cells on one GPU) reproduce the unsharded chains */
+                                shard of a run (its cells on one GPU) reproduce the unsharded chains.
+                                A key is taken modulo 2^32: the generator's counter carries its low 32
+                                bits only, and two chains whose keys agree there draw the same numbers */
   int64_t adapt_pmax;   /* 0, or the largest P = 7 + N over every chain of a larger fit that this run is one
                            shard of: the covariance adaptation kernel is picked by the largest P
                            (k_adapt_gt past 208), so a shard passing the whole fit's value adapts with the
@@ -471,6 +473,81 @@ int tci_dram_run_reduced(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_ch
                          const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                          const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
                          tci_dram_outputs* out, const tci_dram_reductions* red);
+
+/* ---- Replicate chains compared: Gelman-Rubin's potential scale reduction factor (mcmcstat's psrf) ----
+ * The one reduction ACROSS chains. A group is the set of chains c with the same group[c], taken in ascending chain
+ * index; group[c] == -1: the chain belongs to no group. Per group and per column (the group's P = npar parameters;
+ * the chains' s2 is one more column), over the n = n_rows rows, all in FP64, reduced on the device so that the
+ * chains do not cross the bus. mcmcstat is not vendored: the formulas below (Gelman et al., Bayesian Data Analysis,
+ * 3rd ed., section 11.4) are the definition.
+ *   sequences   per chain of the group three: the whole chain, rows [0, n); half A, rows [0, h), h = floor(n / 2);
+ *               half B, rows [n - h, n). For an odd n the middle row belongs to no half.
+ *   mu, s2      per sequence of length L: mu = the Neumaier-compensated sum of its rows divided by L; a constant
+ *               sequence's mean is its value (as in tci_chaincov, so that its s2 is exactly 0);
+ *               s2 = sum_t (x_t - mu)^2 / (L - 1), two-pass and centred.
+ *   classic     the m = M whole chains of the group, L = n.
+ *   split       the m = 2 M halves, L = h, ordered A, B of the group's first chain, A, B of the next, and so on.
+ *   W = (sum_j s2_j) / m;  mubar = (sum_j mu_j) / m;  T = sum_j (mu_j - mubar)^2 / (m - 1);
+ *   rhat = sqrt((L - 1) / L + T / W)
+ *   pooled_mean = mubar of the whole chains
+ *   pooled_std  = sqrt(((n - 1) * sum_j s2_j + n * sum_j (mu_j - mubar)^2) / (M * n)) over the whole chains: the
+ *               std(., 1) of all M n rows, the divisor the reference uses for its sigma_*.
+ * Every sum over j runs in sequence order; every operation is rounded once, as written, never fused. One rule is
+ * added to the formulas: when all mu_j are equal, mubar is that value (what the constant-sequence rule is to mu),
+ * so that T is exactly 0. Consequences:
+ *   m == 1 (classic with one chain): NaN.  L < 2 (split for n < 4): NaN.
+ *   W == 0 and T == 0: NaN (0/0).  W == 0 and T > 0: +Inf.
+ *   identical chains: classic rhat is exactly sqrt((n - 1) / n).
+ * A non-finite entry (NaN or +-Inf) anywhere in a group's column makes all four outputs of that column NaN. Padding
+ * (j >= npar) is NaN, and so is every output of a group id no chain carries. All chains of a group must have the
+ * same npar (TCI_EINVAL, the group named in the message).
+ * An output's bits depend on the group's columns in chain order and on n alone: not on n_chains, where the chains
+ * sit, how groups interleave, ld or how many workgroups ran (the rows are reduced in 256-row segments whose
+ * boundaries follow from n alone, inside a segment in a fixed order, and the segments are combined in order).
+ * With u = 2^-53 and X = max|x| over the group's column, rhat is within
+ *   (L + 2 m + 16) u rhat  +  8 u X sqrt(T) / (W rhat)  +  (m^2 + 32) (u X)^2 (rhat + 1 / rhat) / W
+ * of the formulas evaluated without rounding: a relative term, the cancellation in mu_j - mubar (it grows when the
+ * chains sit far from 0 relative to their spread, as a hierarchical fit's v does) and its second-order companion.
+ * pooled_mean is within (m + 4) u X and pooled_std within (n + m + 10) u pooled_std + 8 u X (DESIGN.md section 7f has
+ * the derivation).
+ *
+ * Deviations from mcmcstat's psrf.m, whose version is not pinned: psrf.m follows Brooks and Gelman (1998), whose
+ * estimate carries a sampling-variability correction in m on the between-chain term; the BDA3 form above has none,
+ * and the two agree as m grows. psrf.m has no split variant and no rule for non-finite or constant columns. */
+typedef struct {
+  int64_t flags;  /* reserved, must be 0 */
+} tci_chainrhat_options;
+
+/* Host buffers (any pointer may be NULL). Per-group vectors have stride ld. */
+typedef struct {
+  double *rhat, *rhat_split, *pooled_mean, *pooled_std;             /* [n_groups][ld] */
+  double *s2_rhat, *s2_rhat_split, *s2_pooled_mean, *s2_pooled_std; /* [n_groups]; NaN without an s2 chain */
+  int64_t n_rows;    /* written: rows the reduction used */
+  double kernel_ms;  /* written: device time of the kernels (HIP events) */
+} tci_chainrhat_outputs;
+
+int tci_chainrhat_defaults(tci_chainrhat_options* opt);
+
+/* The reduction of a chain already on the host: chain is [n_rows][n_chains][ld], s2chain [n_rows][n_chains] or
+ * NULL, npar [n_chains] (NULL: ld for every chain; TCI_ERANGE outside [0, ld]), group [n_chains] with values in
+ * [-1, n_groups) (NULL: every chain in group 0; TCI_ERANGE outside). opt may be NULL (the defaults). TCI_EINVAL for
+ * a null argument, n_rows < 1, n_groups outside [1, n_chains], flags != 0 or a group of mixed npar; TCI_ENOMEM when the chain does not
+ * fit the device. */
+int tci_chainrhat(tci_ctx* ctx, const tci_chainrhat_options* opt, const double* chain, const double* s2chain,
+                  int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, const int32_t* group,
+                  int64_t n_groups, tci_chainrhat_outputs* out);
+
+/* tci_dram_run_reduced plus the group reduction over the same rows (the kept rows whose 1-based chain row is >=
+ * stats_from), taken from the device chain before any copy. red may be NULL (no per-chain reduction); rout is
+ * required; ropt may be NULL; group and n_groups as in tci_chainrhat (npar is the cells': 7 + N). TCI_EINVAL when
+ * opt->thin == 0, fewer than 2 kept rows are in the range or n_groups is outside [1, n_chains]. For replicate chains
+ * of one cell to be independent their chain_keys must differ modulo 2^32 (tci_dram_options). Every engine gives the same chain bits, hence the same
+ * bits here. */
+int tci_dram_run_rhat(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                      const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                      const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                      tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout);
 
 const char* tci_version(void);
 

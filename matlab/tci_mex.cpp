@@ -68,6 +68,12 @@
 //          dens(j,:,k) over grid(j,:,k)), counts (P x n_bins x n, as doubles: bar them over n_bins equal bins of
 //          range; -1 and NaN past a chain's npar), s2_range (2 x n), s2_bw (1 x n), s2_dens, s2_grid (n_grid x n),
 //          s2_counts (n_bins x n) and n_rows.
+//   out = tci_mex('chainrhat', h, chain, npar, group)
+//          Gelman-Rubin's potential scale reduction factor across replicate chains (mcmcstat's psrf; tci_chainrhat,
+//          the definition is in include/tci.h), reduced on the device: chain and npar as for 'chainstats';
+//          group: 1 x n, the 1-based group of every chain (0 = in no group), or []: all chains form one group.
+//          out: struct with rhat, rhat_split, pooled_mean, pooled_std (P x n_groups, n_groups = max(group); NaN
+//          past a group's npar) and n_rows.
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -791,6 +797,66 @@ void cmd_chaindens(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = res;
 }
 
+// ---- 'chainrhat': R-hat and pooled moments of every group of replicate chains --------------------------
+
+void cmd_chainrhat(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs != 5) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chainrhat', h, chain, npar, group)");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[3], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  std::vector<int32_t> group;  // 0-based for the ABI; MATLAB's 0 (no group) becomes -1
+  size_t ng = 1;
+  if (mxGetNumberOfElements(prhs[4]) != 0) {  // [] = one group of all chains
+    const double* gp = doubles(prhs[4], (long long)n, "group");
+    group.resize(n);
+    ng = 0;
+    for (size_t b = 0; b < n; ++b) {
+      if (!(gp[b] >= 0 && gp[b] <= (double)n) || gp[b] != (double)(int64_t)gp[b])
+        mexErrMsgIdAndTxt("tci:arg", "group(%d) must be an integer in [0, n]", (int)b + 1);
+      group[b] = (int32_t)gp[b] - 1;
+      ng = std::max(ng, (size_t)gp[b]);
+    }
+    if (ng < 1) mexErrMsgIdAndTxt("tci:arg", "group names no group (all zero)");
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  static const char* fields[] = {"rhat", "rhat_split", "pooled_mean", "pooled_std", "n_rows"};
+  mxArray* res = mxCreateStructMatrix(1, 1, 5, fields);
+  mxArray* vals[4];
+  for (int f = 0; f < 4; ++f) {
+    vals[f] = mxCreateDoubleMatrix(P, ng, mxREAL);  // P x n_groups == the ABI's [group][P]
+    mxSetField(res, 0, fields[f], vals[f]);
+  }
+  tci_chainrhat_outputs out;
+  memset(&out, 0, sizeof out);
+  out.rhat = mxGetPr(vals[0]);
+  out.rhat_split = mxGetPr(vals[1]);
+  out.pooled_mean = mxGetPr(vals[2]);
+  out.pooled_std = mxGetPr(vals[3]);
+  const int rc = tci_chainrhat(ctx, nullptr, X, nullptr, (int64_t)rows, (int64_t)n, (int64_t)P,
+                               npar.empty() ? nullptr : npar.data(), group.empty() ? nullptr : group.data(), (int64_t)ng,
+                               &out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_chainrhat");
+  }
+  mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+  plhs[0] = res;
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -811,6 +877,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chaincov") cmd_chaincov(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainquant") cmd_chainquant(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chaindens") cmd_chaindens(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chainrhat") cmd_chainrhat(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

@@ -115,6 +115,16 @@ class tci_dram_reductions(C.Structure):
                 ("dopt", C.POINTER(tci_chaindens_options)), ("dout", C.POINTER(tci_chaindens_outputs))]
 
 
+class tci_chainrhat_options(C.Structure):
+    _fields_ = [("flags", C.c_int64)]
+
+
+class tci_chainrhat_outputs(C.Structure):
+    _fields_ = [("rhat", _dp), ("rhat_split", _dp), ("pooled_mean", _dp), ("pooled_std", _dp), ("s2_rhat", _dp),
+                ("s2_rhat_split", _dp), ("s2_pooled_mean", _dp), ("s2_pooled_std", _dp), ("n_rows", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -159,6 +169,13 @@ SIGNATURES = [
     ("tci_dram_run_reduced", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
                                        _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
                                        C.POINTER(tci_dram_reductions)]),
+    ("tci_chainrhat_defaults", C.c_int, [C.POINTER(tci_chainrhat_options)]),
+    ("tci_chainrhat", C.c_int, [C.c_void_p, C.POINTER(tci_chainrhat_options), _dp, _dp, C.c_int64, C.c_int64,
+                                C.c_int64, _i32p, _i32p, C.c_int64, C.POINTER(tci_chainrhat_outputs)]),
+    ("tci_dram_run_rhat", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                    _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                    C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
+                                    C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -939,6 +939,125 @@ int chaindens_device(tci_ctx* ctx, const char* who, const double* d_chain, const
   return TCI_OK;
 }
 
+// The groups of a tci_chainrhat call, checked before any device work: group (null: every chain in group 0) as the
+// per-chain vector the kernels skip by, and its CSR form (the chains of a group ascending). npar (host, may be null =
+// ld): the chains of a group must have one npar.
+struct RhatGroups {
+  std::vector<int32_t> group, off, list;
+  size_t scratch = 0;
+};
+int chainrhat_groups(tci_ctx* ctx, const char* who, const tci_chainrhat_options* ropt, int64_t n_rows, int64_t n_chains,
+                     int64_t ld, const int32_t* npar, const int32_t* group, int64_t n_groups, RhatGroups* G) {
+  if (ropt && ropt->flags != 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": flags is reserved and must be 0");
+  if (n_groups < 1) return fail(ctx, TCI_EINVAL, std::string(who) + ": n_groups must be >= 1");
+  if (n_rows > ((int64_t)1 << 30) || n_chains > ((int64_t)1 << 30) || ld > ((int64_t)1 << 24))
+    return fail(ctx, TCI_ERANGE, std::string(who) + ": n_rows or n_chains above 2^30, or ld above 2^24");
+  if (group)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (group[c] < -1 || group[c] >= n_groups)
+        return fail(ctx, TCI_ERANGE, std::string(who) + ": group[" + std::to_string(c) + "] = " +
+                                         std::to_string(group[c]) + " outside [-1, n_groups)");
+  try {
+    G->group.assign((size_t)n_chains, 0);
+    if (group) std::copy(group, group + n_chains, G->group.begin());
+    G->off.assign((size_t)n_groups + 1, 0);
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (G->group[(size_t)c] >= 0) ++G->off[(size_t)G->group[(size_t)c] + 1];
+    for (int64_t g = 0; g < n_groups; ++g) G->off[(size_t)g + 1] += G->off[(size_t)g];
+    G->list.assign((size_t)std::max<int32_t>(G->off[(size_t)n_groups], 1), 0);
+    std::vector<int32_t> fill(G->off.begin(), G->off.end() - 1);
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (G->group[(size_t)c] >= 0) G->list[(size_t)fill[(size_t)G->group[(size_t)c]]++] = (int32_t)c;
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  if (npar)
+    for (int64_t g = 0; g < n_groups; ++g)
+      for (int32_t k = G->off[(size_t)g] + 1; k < G->off[(size_t)g + 1]; ++k)
+        if (npar[G->list[(size_t)k]] != npar[G->list[(size_t)G->off[(size_t)g]]])
+          return fail(ctx, TCI_EINVAL, std::string(who) + ": group " + std::to_string(g) + " has chains of different npar (" +
+                                           std::to_string(npar[G->list[(size_t)G->off[(size_t)g]]]) + " and " +
+                                           std::to_string(npar[G->list[(size_t)k]]) + ")");
+  const int rc = tci::chainrhat_scratch_bytes(n_rows, n_chains, ld, n_groups, &G->scratch);
+  if (rc == TCI_ENOMEM)
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": the per-segment partial sums are larger than any device memory");
+  if (rc != TCI_OK)
+    return fail(ctx, TCI_ERANGE, std::string(who) + ": rows x chains x ld too large for one launch (2^31 workgroups)");
+  return TCI_OK;
+}
+
+// The group kernels on a device chain (launch_chainrhat), timed with HIP events, and their results scattered into
+// the caller's host buffers (d_npar null: ld columns for every chain; d_s2 null: the s2 twins are NaN).
+int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                     int64_t n_chains, int64_t ld, const int32_t* d_npar, const RhatGroups& G, int64_t n_groups,
+                     tci_chainrhat_outputs* out) {
+  const size_t ldc = (size_t)ld + 1, L = (size_t)ld, ng = (size_t)n_groups, plane = ng * ldc;
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  void* d_scratch = A.alloc<uint8_t>(G.scratch, &e);
+  double* d_o = e == hipSuccess ? A.alloc<double>(4 * plane, &e) : nullptr;
+  int32_t* d_group = e == hipSuccess ? A.alloc<int32_t>(G.group.size(), &e) : nullptr;
+  int32_t* d_off = e == hipSuccess ? A.alloc<int32_t>(G.off.size(), &e) : nullptr;
+  int32_t* d_list = e == hipSuccess ? A.alloc<int32_t>(G.list.size(), &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the group reduction (" +
+                                     std::to_string(G.scratch + 4 * plane * sizeof(double)) + " bytes) failed");
+  }
+  std::vector<double> ho;
+  try {
+    ho.resize(4 * plane);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  hipStream_t s = ctx->stream;
+  hipEvent_t ev0, ev1;
+  TCI_HIP(ctx, hipEventCreate(&ev0));
+  e = hipEventCreate(&ev1);
+  if (e != hipSuccess) {
+    (void)hipEventDestroy(ev0);
+    return hip_fail(ctx, e, "hipEventCreate");
+  }
+  // from here every path reaches the hipStreamSynchronize below: G's vectors outlive their uploads
+  e = hipMemcpyAsync(d_group, G.group.data(), G.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_off, G.off.data(), G.off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_list, G.list.data(), G.list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  hipError_t e1 = e == hipSuccess ? hipEventRecord(ev0, s) : e;
+  const int rc = e != hipSuccess ? TCI_OK
+                                 : tci::launch_chainrhat(d_chain, d_s2, n_rows, n_chains, ld, d_npar, d_group, n_groups,
+                                                         d_off, d_list, d_scratch, d_o, (void*)s);
+  if (e1 == hipSuccess) e1 = hipEventRecord(ev1, s);
+  if (rc == TCI_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(ho.data(), d_o, 4 * plane * sizeof(double), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  float ms = 0.f;
+  if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "chain R-hat kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "chain R-hat kernels");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain R-hat copy");
+  double* const dst[4] = {out->rhat, out->rhat_split, out->pooled_mean, out->pooled_std};
+  double* const dst2[4] = {out->s2_rhat, out->s2_rhat_split, out->s2_pooled_mean, out->s2_pooled_std};
+  for (size_t t = 0; t < 4; ++t)
+    for (size_t g = 0; g < ng; ++g) {
+      const double* src = ho.data() + (t * ng + g) * ldc;
+      if (dst[t]) std::memcpy(dst[t] + g * L, src, L * sizeof(double));
+      if (dst2[t]) dst2[t][g] = src[L];
+    }
+  out->n_rows = n_rows;
+  out->kernel_ms = ms;
+  return TCI_OK;
+}
+
+// What tci_dram_run_rhat adds to a run: the groups of its chains and where the group reduction goes.
+struct RhatAsk {
+  const tci_chainrhat_options* ropt;
+  const int32_t* group;
+  int64_t n_groups;
+  tci_chainrhat_outputs* rout;
+};
+
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
 // -> [window records] -> [adapt] -> step + 1.
 int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& p, hipStream_t s, bool with_stats,
@@ -990,11 +1109,12 @@ namespace {
 
 // tci_dram_run, with the reductions of the kept rows that `red` asks for: red.sout the chain statistics
 // (tci_dram_run_stats), red.cout their mean, covariance and correlation (tci_dram_run_cov), red.qout their
-// quantiles and red.dout their densities and histograms (tci_dram_run_reduced).
+// quantiles and red.dout their densities and histograms (tci_dram_run_reduced); rhat: the reduction across the
+// chains of every group over the same rows (tci_dram_run_rhat).
 int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
                   const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                   const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
-                  tci_dram_outputs* out, const tci_dram_reductions& red) {
+                  tci_dram_outputs* out, const tci_dram_reductions& red, const RhatAsk* rhat = nullptr) {
   if (!ctx) return TCI_EINVAL;
   const tci_chainstats_options* sopt = red.sopt;
   tci_chainstats_outputs* sout = red.sout;
@@ -1063,6 +1183,16 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     const int rcd = chaindens_opts(ctx, "tci_dram_run_reduced", red.dopt, d_rows, n_chains, ld, &d_G, &d_B, &d_bws, &d_scratch);
     if (rcd != TCI_OK) return rcd;
   }
+  int64_t r_k0 = 0, r_rows = 0;  // and so does the group reduction
+  if (rhat) {
+    if (opt->thin <= 0)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_rhat: the group reduction needs the kept rows (thin >= 1)");
+    const int64_t from = std::max<int64_t>(opt->stats_from, 1);
+    r_k0 = (from - 1 + opt->thin - 1) / opt->thin;
+    r_rows = (opt->n_steps + opt->thin - 1) / opt->thin - r_k0;
+    if (r_rows < 2)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_rhat: fewer than 2 kept rows at or past stats_from (n_rows < 2)");
+  }
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
   if (ld > TCI_MAX_POINTS + 7) return fail(ctx, TCI_ERANGE, "tci_dram_run: ld too large");
@@ -1078,6 +1208,12 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
         return fail(ctx, TCI_EINVAL, "tci_dram_run: chain " + std::to_string(c) + " starts outside its bounds");
       if (!(qcov_diag[c * L + j] > 0)) return fail(ctx, TCI_EINVAL, "tci_dram_run: qcov_diag must be > 0");
     }
+  }
+  RhatGroups r_groups;
+  if (rhat) {
+    rc = chainrhat_groups(ctx, "tci_dram_run_rhat", rhat->ropt, r_rows, n_chains, ld, npar.data(), rhat->group,
+                          rhat->n_groups, &r_groups);
+    if (rc != TCI_OK) return rc;
   }
   // the P the adaptation kernel is picked for (> 208: k_adapt_gt and its tile grid): this run's largest,
   // or the whole fit's when this run is a shard of it (adapt_pmax)
@@ -1176,13 +1312,13 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   TCI_ALLOC(prof, int64_t, 32);
   TCI_HIP(ctx, hipMemsetAsync(st.prof, 0, 32 * sizeof(int64_t), ctx->stream));
 #endif
-  if (n_keep > 0 && (sout || cvout || qout || dout) && !(out->chain || out->s2chain)) {
+  if (n_keep > 0 && (sout || cvout || qout || dout || rhat) && !(out->chain || out->s2chain)) {
     // the chain is kept on the device for the statistics alone: running out of memory is the caller's to handle
     st.chain_out = A.alloc<double>((size_t)n_keep * n * L, &e);
     if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : cvout ? "tci_dram_run_cov" : "tci_dram_run_reduced") +
+      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : cvout ? "tci_dram_run_cov" : rhat ? "tci_dram_run_rhat" : "tci_dram_run_reduced") +
                                        ": the device chain (" +
                                        std::to_string((size_t)n_keep * n * L * sizeof(double)) + " bytes) does not fit");
     }
@@ -1450,9 +1586,15 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
                            st.s2_out + (size_t)q_k0 * n, q_rows, n_chains, ld, st.npar, q_probs, q_nq, qout);
     if (rc != TCI_OK) return rc;
   }
-  if (dout)
-    return chaindens_device(ctx, "tci_dram_run_reduced", st.chain_out + (size_t)d_k0 * n * L,
-                            st.s2_out + (size_t)d_k0 * n, d_rows, n_chains, ld, st.npar, d_G, d_B, d_bws, d_scratch, dout);
+  if (dout) {
+    rc = chaindens_device(ctx, "tci_dram_run_reduced", st.chain_out + (size_t)d_k0 * n * L,
+                          st.s2_out + (size_t)d_k0 * n, d_rows, n_chains, ld, st.npar, d_G, d_B, d_bws, d_scratch, dout);
+    if (rc != TCI_OK) return rc;
+  }
+  if (rhat)
+    return chainrhat_device(ctx, "tci_dram_run_rhat", st.chain_out + (size_t)r_k0 * n * L,
+                            st.s2_out + (size_t)r_k0 * n, r_rows, n_chains, ld, st.npar, r_groups, rhat->n_groups,
+                            rhat->rout);
   return TCI_OK;
 }
 
@@ -1599,6 +1741,64 @@ int tci_chaindens(tci_ctx* ctx, const tci_chaindens_options* opt, const double* 
   if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
   if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
   return chaindens_device(ctx, "tci_chaindens", d_chain, d_s2, n_rows, n_chains, ld, d_npar, G, B, bws, scratch, out);
+}
+
+int tci_dram_run_rhat(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                      const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                      const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                      tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout) {
+  if (!ctx) return TCI_EINVAL;
+  if (!rout) return fail(ctx, TCI_EINVAL, "tci_dram_run_rhat: null group reduction outputs");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_dram_run_rhat: n_groups must be in [1, n_chains]");
+  const RhatAsk ask{ropt, group, n_groups, rout};
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, red ? *red : tci_dram_reductions{}, &ask);
+}
+
+int tci_chainrhat_defaults(tci_chainrhat_options* o) {
+  if (!o) return TCI_EINVAL;
+  o->flags = 0;
+  return TCI_OK;
+}
+
+int tci_chainrhat(tci_ctx* ctx, const tci_chainrhat_options* opt, const double* chain, const double* s2chain,
+                  int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, const int32_t* group,
+                  int64_t n_groups, tci_chainrhat_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chainrhat: null argument");
+  if (n_rows < 1) return fail(ctx, TCI_EINVAL, "tci_chainrhat: n_rows must be >= 1");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chainrhat: n_chains and ld must be >= 1");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_chainrhat: n_groups must be in [1, n_chains]");
+  if (npar)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (npar[c] < 0 || npar[c] > ld)
+        return fail(ctx, TCI_ERANGE, "tci_chainrhat: npar[" + std::to_string(c) + "] outside [0, ld]");
+  RhatGroups G;
+  const int rc = chainrhat_groups(ctx, "tci_chainrhat", opt, n_rows, n_chains, ld, npar, group, n_groups, &G);
+  if (rc != TCI_OK) return rc;
+  const size_t per_row = (size_t)n_chains * (size_t)ld;
+  if (per_row > (((size_t)1 << 46) / sizeof(double)) / (size_t)n_rows)
+    return fail(ctx, TCI_ENOMEM, "tci_chainrhat: the chain is larger than any device memory");
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t nch = (size_t)n_rows * per_row, ns2 = (size_t)n_rows * (size_t)n_chains;
+  double* d_chain = A.alloc<double>(nch, &e);
+  double* d_s2 = e == hipSuccess && s2chain ? A.alloc<double>(ns2, &e) : nullptr;
+  int32_t* d_npar = e == hipSuccess && npar ? A.alloc<int32_t>((size_t)n_chains, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chainrhat: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return chainrhat_device(ctx, "tci_chainrhat", d_chain, d_s2, n_rows, n_chains, ld, d_npar, G, n_groups, out);
 }
 
 int tci_chaincov_defaults(tci_chaincov_options* o) {

@@ -129,4 +129,18 @@ int launch_chaindens(const double* chain, const double* s2, int64_t n_rows, int6
 // The scratch launch_chaindens needs; TCI_ERANGE when the sizes do not fit the launch grid, TCI_ENOMEM above 2^46 bytes.
 int chaindens_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, int32_t G, int32_t B, size_t* bytes);
 
+// Classic and split R-hat, pooled mean and pooled standard deviation (tci_chainrhat.hip) of every group of chains of
+// a device chain, laid out and padded as for launch_chainquant; n_rows >= 1. group (device): [n_chains], the group
+// of every chain, < 0 = none; g_off (device): [n_groups + 1] and g_list (device): the chains of group g, ascending,
+// at g_list[g_off[g] .. g_off[g + 1]) (the CSR form of `group`, built by the host); the chains of a group have one
+// npar. scratch (device): chainrhat_scratch_bytes() bytes, 8-byte aligned. out (device): [4][n_groups][ld + 1] =
+// rhat, rhat_split, pooled_mean, pooled_std; padding, non-finite columns, column ld without s2 and empty groups are
+// NaN. Asynchronous on `stream`. TCI_EINVAL on a bad size, TCI_ERANGE on a grid above 2^31 - 1 workgroups, TCI_EHIP
+// on a HIP error.
+int launch_chainrhat(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
+                     const int32_t* npar, const int32_t* group, int64_t n_groups, const int32_t* g_off,
+                     const int32_t* g_list, void* scratch, double* out, void* stream);
+// The scratch launch_chainrhat needs; TCI_ERANGE when the sizes do not fit the launch grid, TCI_ENOMEM above 2^46 bytes.
+int chainrhat_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups, size_t* bytes);
+
 }  // namespace tci

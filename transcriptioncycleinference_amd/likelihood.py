@@ -177,6 +177,59 @@ class ChainDens:
         return dens_grid(self.s2_range.T[None], self.n_grid)[0].T.copy()
 
 
+def rhat_groups(group, n: int, npar=None):
+    """``group`` as the int32 vector ``tci_chainrhat`` takes and the number of groups: None = all ``n`` chains in
+    group 0; else one id per chain, -1 = no group, and ``n_groups = max id + 1`` (at least 1). ``npar`` (one per
+    chain, when given): the chains of a group must have one."""
+    if group is None:
+        g = np.zeros(n, np.int32)
+    else:
+        g = np.asarray(group)
+        if g.shape != (n,) or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("group must hold one integer id per chain")
+        if g.min() < -1 or g.max() >= n:
+            raise ValueError("group ids must be in [-1, n_chains)")
+        g = np.ascontiguousarray(g, np.int32)
+    if npar is not None:
+        for k in np.unique(g[g >= 0]):
+            if len(np.unique(np.asarray(npar)[g == k])) > 1:
+                raise ValueError(f"group {int(k)} has chains of different npar")
+    return g, max(int(g.max()) + 1, 1)
+
+
+@dataclasses.dataclass
+class ChainRhat:
+    """Per-group convergence across replicate chains (``tci_chainrhat_outputs``): the classic and the split
+    potential scale reduction factor and the pooled posterior mean and standard deviation, ``[n_groups, ld]`` for the
+    parameters and ``[n_groups]`` for s2; padding is NaN."""
+
+    rhat: np.ndarray
+    rhat_split: np.ndarray
+    pooled_mean: np.ndarray
+    pooled_std: np.ndarray
+    s2_rhat: np.ndarray
+    s2_rhat_split: np.ndarray
+    s2_pooled_mean: np.ndarray
+    s2_pooled_std: np.ndarray
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n_groups: int, ld: int) -> "ChainRhat":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        g = int(n_groups)
+        return cls(d(g, ld), d(g, ld), d(g, ld), d(g, ld), d(g), d(g), d(g), d(g))
+
+    def options(self) -> "_lib.tci_chainrhat_options":
+        return _lib.tci_chainrhat_options(0)
+
+    def to_c(self) -> "_lib.tci_chainrhat_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        return _lib.tci_chainrhat_outputs(P(self.rhat), P(self.rhat_split), P(self.pooled_mean), P(self.pooled_std),
+                                          P(self.s2_rhat), P(self.s2_rhat_split), P(self.s2_pooled_mean),
+                                          P(self.s2_pooled_std), 0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -423,6 +476,36 @@ class Likelihood:
                                             rows, n, ld, _lib.ptr(npr, _lib._i32p), C.byref(out)))
         cd.n_rows, cd.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return cd
+
+    def chainrhat(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, group=None) -> ChainRhat:
+        """Gelman-Rubin's potential scale reduction factor across replicate chains held on the host (mcmcstat's
+        ``psrf``), classic and split, with the pooled posterior mean and standard deviation, reduced on the device
+        (``tci_chainrhat``; the definition is in ``include/tci.h``). ``chain``, ``s2chain`` and ``npar`` as in
+        :meth:`chainstats`; ``group``: one id per chain, the chains of equal id form a group (taken in chain order),
+        -1 = in no group; None = all chains form one group. The chains of a group must have one ``npar``. Returns a
+        :class:`ChainRhat` of ``max id + 1`` groups; padding is NaN, and so is every output of a column holding a
+        non-finite value in any chain of the group, and the classic factor of a group of one chain."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = None
+        if s2chain is not None:
+            s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        grp, ng = rhat_groups(group, n, npr)
+        cr = ChainRhat.empty(ng, ld)
+        opt, out = cr.options(), cr.to_c()
+        self._check(self._lib.tci_chainrhat(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp),
+                                            rows, n, ld, _lib.ptr(npr, _lib._i32p), _lib.ptr(grp, _lib._i32p), ng,
+                                            C.byref(out)))
+        cr.n_rows, cr.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return cr
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import ChainCov, ChainDens, ChainQuant, ChainStats
+from .likelihood import ChainCov, ChainDens, ChainQuant, ChainRhat, ChainStats, rhat_groups
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -48,6 +48,17 @@ QUANT_FIELDS = tuple("q_" + s for s in _SCALARS) + ("q_dR", "q_s2", "probs", "n_
 # MCMCdens (fit(..., density=True)): marginal density and histogram per fitted cell, P + 1 = 7 + N + 1 columns wide
 # (theta order, s2 last): grid, dens [G, P + 1], counts [B, P + 1], range [2, P + 1], bw [P + 1]
 DENS_FIELDS = ("grid", "dens", "counts", "range", "bw", "n_rows", "cell_index")
+# MCMCrhat (fit(..., replicates=M) or fit(..., rhat=True)): convergence across the M replicate chains of a fitted cell,
+# P + 1 = 7 + N + 1 columns wide (theta order, s2 last): rhat, rhat_split, pooled_mean, pooled_std [P + 1];
+# mean_rep [M, P] and accept_rep [M]: every replicate's posterior means and acceptance rate; rhat_max: the largest
+# classic or split factor of the cell
+RHAT_FIELDS = ("rhat", "rhat_split", "pooled_mean", "pooled_std", "mean_rep", "accept_rep", "rhat_max", "n_rows",
+               "n_chains", "cell_index")
+# RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
+# carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
+# sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
+REPLICATE_KEY_STRIDE = 1 << 24
+MAX_REPLICATES = 1 << 8
 THETA_INDEX = {"v": 0, "tau": 1, "ton": 2, "MS2_basal": 3, "PP7_basal": 4, "A": 5, "R": 6}
 
 
@@ -102,6 +113,7 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    rhat: Optional[ChainRhat] = None              # dram_run(group=ids): R-hat / pooled moments of every group of chains
     dens: Optional[ChainDens] = None              # dram_run(dens=True): densities / histograms of the kept rows
     quant: Optional[ChainQuant] = None            # dram_run(quant=probs): quantiles of the kept rows
     stats: Optional[ChainStats] = None            # dram_run(stats=True): diagnostics of the kept rows
@@ -111,7 +123,7 @@ class DramResult:
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
-             cov_scratch_bytes: int = 0, quant=None, dens=None) -> DramResult:
+             cov_scratch_bytes: int = 0, quant=None, dens=None, group=None) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -125,7 +137,10 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     gives), selected from the device chain; the run then goes through ``tci_dram_run_reduced``, which takes any
     of the reductions. ``dens``: ``True`` or a dict of ``n_grid`` / ``n_bins`` / ``bw_scale``: also the marginal
     density and histogram of every column of those same rows, at least 2 of them (``DramResult.dens``, as
-    ``Likelihood.chaindens`` gives), through ``tci_dram_run_reduced`` too."""
+    ``Likelihood.chaindens`` gives), through ``tci_dram_run_reduced`` too. ``group``: one id per chain (-1 = none):
+    also the classic and split R-hat and the pooled mean and standard deviation of every group of chains over those
+    same rows, at least 2 of them (``DramResult.rhat``, as ``Likelihood.chainrhat`` gives), reduced from the device
+    chain through ``tci_dram_run_rhat``, with any of the other reductions."""
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
     theta0, lower, upper, prior_mu, prior_sig, qcov_diag = map(f, (theta0, lower, upper, prior_mu, prior_sig,
                                                                     qcov_diag))
@@ -150,8 +165,11 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = cc = cq = cd = None
+    cs = cc = cq = cd = cr = None
     sopt = sout = None
+    if group is not None:
+        grp, ng = rhat_groups(group, n)
+        cr = ChainRhat.empty(ng, ld)
     if quant is not None:
         cq = ChainQuant.empty(n, ld, quant)
     if dens is not None and dens is not False:
@@ -159,7 +177,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     if stats:
         cs = ChainStats.empty(n, ld)
         sopt, sout = _lib.tci_chainstats_options(int(max_lag)), cs.to_c()
-    if cq is not None or cd is not None:
+    if cq is not None or cd is not None or cr is not None:
         red = _lib.tci_dram_reductions()
         if cq is not None:
             qopt, qout = cq.options(), cq.to_c()
@@ -173,7 +191,13 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
             cc = ChainCov.empty(n, ld)
             copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
             red.copt, red.cout = C.pointer(copt), C.pointer(cout)
-        lk._check(lk._lib.tci_dram_run_reduced(*args, C.byref(red)))
+        if cr is not None:
+            ropt, rout = cr.options(), cr.to_c()
+            lk._check(lk._lib.tci_dram_run_rhat(*args, C.byref(red), _lib.ptr(grp, _lib._i32p), ng, C.byref(ropt),
+                                                C.byref(rout)))
+            cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
+        else:
+            lk._check(lk._lib.tci_dram_run_reduced(*args, C.byref(red)))
         if cq is not None:
             cq.n_rows, cq.kernel_ms = int(qout.n_rows), float(qout.kernel_ms)
         if cd is not None:
@@ -194,7 +218,8 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
         cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
                       kernel_ms=np.array(out.kernel_ms[:], np.float64),
-                      kernel_launches=np.array(out.kernel_launches[:], np.int64), dens=cd, quant=cq, stats=cs, cov=cc)
+                      kernel_launches=np.array(out.kernel_launches[:], np.int64), rhat=cr, dens=cd, quant=cq, stats=cs,
+                      cov=cc)
 
 
 # ---------------------------------------------------------------------------
@@ -220,6 +245,23 @@ def cell_setup(t: np.ndarray, rng: np.random.Generator, ratePriorWidth: float = 
     return x0, lower, upper, mu, sig, J0
 
 
+def replicate_keys(cells_global, replicates: int) -> np.ndarray:
+    """The RNG stream keys of a replicate fit, replicate-major: ``g + r * REPLICATE_KEY_STRIDE`` for replicate ``r``
+    of dataset-wide cell ``g`` (replicate 0: ``g``, the one-chain fit's key). The keys are distinct modulo 2^32, which
+    is all of a key the sampler's generator sees; ValueError when that cannot be (more than ``MAX_REPLICATES``
+    replicates, or with replicates a cell index at or above ``REPLICATE_KEY_STRIDE``)."""
+    g = np.asarray(cells_global, np.int64).reshape(-1)
+    M = int(replicates)
+    if M != replicates or M < 1:
+        raise ValueError("replicates must be an integer >= 1")
+    if M > MAX_REPLICATES:
+        raise ValueError(f"replicates must be at most {MAX_REPLICATES}: a chain's RNG stream key has 32 bits")
+    if M > 1 and g.size and (g.min() < 0 or g.max() >= REPLICATE_KEY_STRIDE):
+        raise ValueError(f"replicates > 1 needs dataset-wide cell indices below {REPLICATE_KEY_STRIDE}: a chain's RNG "
+                         "stream key has 32 bits")
+    return np.concatenate([g + r * REPLICATE_KEY_STRIDE for r in range(M)])
+
+
 @dataclass
 class FitResult:
     DatasetName: str
@@ -235,6 +277,7 @@ class FitResult:
     gather_bytes: int = 0                      # parallel.fit_sharded: bytes every rank receives in it
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
+    MCMCrhat: Optional[List[Dict]] = None      # fit(..., replicates=M): RHAT_FIELDS per fitted cell
     MCMCdens: Optional[List[Dict]] = None      # fit(..., density=True): DENS_FIELDS per fitted cell
     MCMCquant: Optional[List[Dict]] = None     # fit(..., quantiles=probs): QUANT_FIELDS per fitted cell
     MCMCdiag: Optional[List[Dict]] = None      # fit(..., diagnostics=True): DIAG_FIELDS per fitted cell
@@ -273,6 +316,7 @@ class FitPlan:
     prior_sig: np.ndarray
     qcov_diag: np.ndarray
     approved: List[int]       # MCMCresults.ApprovedFits per fitted cell (:345-350)
+    replicates: int = 1       # chains per cell; the rows are replicate-major: row r * len(cells) + k is cell k's r-th
 
 
 def _previous(v0, approved, g: int):
@@ -297,7 +341,7 @@ def kept_cells(cl: Cells, ids: Sequence[int], v0=None, cell_offset: int = 0) -> 
 
 
 def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 50.0, v0=None,
-             approved=None, cell_offset: int = 0) -> FitPlan:
+             approved=None, cell_offset: int = 0, replicates: int = 1) -> FitPlan:
     """The parfor body's per-cell setup for the cells ``ids`` (host only, no GPU).
 
     ``v0`` (loadPrevious, :193-198) and ``approved`` are per-cell inputs read by cell, never by
@@ -307,7 +351,15 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
     (``continue``, :196-198) and so pruned from the outputs (:359-369). ``ApprovedFits`` is the
     previous fit's when v0 came from one (:345-347) unless ``approved`` overrides it; 0 otherwise
     (:349). ``cell_offset``: the dataset-wide index of ``cl``'s cell 0 (``cl`` holds one shard of a
-    larger dataset): x0 and the per-cell inputs are keyed by the dataset-wide index."""
+    larger dataset): x0 and the per-cell inputs are keyed by the dataset-wide index.
+
+    ``replicates``: chains per cell. Replicate 0 of dataset-wide cell ``g`` draws x0 from ``default_rng([seed, g])``
+    (what a one-chain fit draws), replicate ``r >= 1`` from ``default_rng([seed, g, r])``; bounds, priors, J0 and a
+    hierarchical v0 are the cell's own for every replicate. The rows are replicate-major, so the first
+    ``len(cells)`` rows are exactly the one-chain plan."""
+    M = int(replicates)
+    if M != replicates or M < 1:
+        raise ValueError("replicates must be an integer >= 1")
     rows, keep, appr = [], [], []
     for c in ids:
         c = int(c)
@@ -319,6 +371,11 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
         rows.append(cell_setup(t, np.random.default_rng([int(seed), g]), ratePriorWidth, vv))
         keep.append(c)
         appr.append(a)
+    for r in range(1, M):
+        for c in keep:
+            g = int(cell_offset) + c
+            rows.append(cell_setup(cl.cell(c)[0], np.random.default_rng([int(seed), g, r]), ratePriorWidth,
+                                   _previous(v0, approved, g)[1]))
     ld = max((len(r[0]) for r in rows), default=7)
 
     def stack(i, fill):
@@ -328,13 +385,14 @@ def plan_fit(cl: Cells, ids: Sequence[int], seed: int, ratePriorWidth: float = 5
         return out
 
     return FitPlan(keep, stack(0, 0.0), stack(1, -np.inf), stack(2, np.inf), stack(3, 0.0), stack(4, np.inf),
-                   stack(5, 1.0), appr)
+                   stack(5, 1.0), appr, M)
 
 
 def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 50.0, seed: int = 0,
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
-        max_lag: int = 0, covariance: bool = False, quantiles=None, density=None) -> FitResult:
+        max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
+        rhat: Optional[bool] = None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -368,26 +426,49 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     ``density``: ``True`` or a dict of ``n_grid`` / ``n_bins`` / ``bw_scale``: also ``MCMCdens``, one dict of
     ``DENS_FIELDS`` per fitted cell: the marginal density (mcmcstat's ``density.m``) and histogram of every
     parameter and of s2 over the rows ``MCMCchain`` keeps (needs ``thin >= 1`` and 2 such rows), reduced on the
-    device (:func:`dens_entry`): what ``ApproveMCMCResults`` draws with ``histogram`` from the raw chains."""
+    device (:func:`dens_entry`): what ``ApproveMCMCResults`` draws with ``histogram`` from the raw chains.
+
+    ``replicates``: M chains per cell instead of one, from different starts (:func:`plan_fit`); replicate ``r >= 1``
+    of cell ``g`` runs on RNG stream ``g + r * 2**24`` (:func:`replicate_keys`; the generator sees a key's low 32 bits,
+    so at most 256 replicates and cell indices below 2**24). The chains are ordered replicate-major, and the engines and
+    reductions do not depend on a chain's position: ``MCMCresults``, ``MCMCplot``, ``MCMCchain``, ``accept_rate``,
+    ``final_theta`` and the four optional per-cell lists are replicate 0's, bit for bit those of ``replicates=1``
+    (``n_evals`` counts every replicate). ``rhat`` (default: ``replicates > 1``): also ``MCMCrhat``, one dict of
+    ``RHAT_FIELDS`` per fitted cell: Gelman-Rubin's classic and split potential scale reduction factor and the pooled
+    posterior mean and standard deviation of every parameter and of s2 across the cell's replicates, over the rows
+    ``MCMCchain`` keeps (needs ``thin >= 1`` and 2 such rows), reduced on the device (:func:`rhat_entry`).
+    ``rhat=True`` with one replicate gives the split factor alone (the classic one is NaN). With ``thin >= 1`` the
+    kept rows of every replicate are copied to the host, M times the one-chain fit's copy, though ``MCMCchain`` keeps
+    replicate 0's alone (``tci_dram_outputs.chain`` is all chains or none)."""
+    M = int(replicates)
+    if M != replicates or M < 1:
+        raise ValueError("replicates must be an integer >= 1")
+    want_rhat = M > 1 if rhat is None else bool(rhat)
+    if want_rhat and int(thin) < 1:
+        raise ValueError("MCMCrhat is reduced from the kept rows: replicates > 1 (or rhat=True) needs thin >= 1; "
+                         "pass rhat=False to run the replicates without it")
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
-    plan = plan_fit(cl, ids, seed, ratePriorWidth, v0, approved, cell_offset=off)
+    plan = plan_fit(cl, ids, seed, ratePriorWidth, v0, approved, cell_offset=off, replicates=M)
     keep = plan.cells
+    K = len(keep)
     if not keep:
         return FitResult(cl.name, [], [], [], np.zeros(0), 0, 0.0)
     # a private copy: the caller's options object is never modified
     o = dataclasses.replace(opts) if opts is not None else DramOptions()
     o.n_steps, o.burnintime, o.stats_from, o.thin = int(n_steps), int(n_burn), int(max(n_burn, 1)), int(thin)
     o.seed = int(seed) * 1000003 + 20201028
-    res = dram_run(lk, np.array(keep, np.int32), plan.x0, plan.lower, plan.upper, plan.prior_mu, plan.prior_sig,
-                   plan.qcov_diag, 1.0, o, chain_keys=np.array(keep, np.int64) + off,
+    keys = replicate_keys(np.array(keep, np.int64) + off, M)
+    res = dram_run(lk, np.tile(np.array(keep, np.int32), M), plan.x0, plan.lower, plan.upper, plan.prior_mu,
+                   plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys,
+                   **(dict(group=np.tile(np.arange(K, dtype=np.int32), M)) if want_rhat else {}),
                    **(dict(stats=True, max_lag=max_lag) if diagnostics else {}),
                    **(dict(cov=True) if covariance else {}),
                    **(dict(quant=quantiles) if quantiles is not None else {}),
                    **(dict(dens=density) if density is not None and density is not False else {}))
     # forward model at the means on the raw times (:307-309)
-    ms2, pp7 = lk.forward(res.mean, np.array(keep, np.int32), grid="raw")
+    ms2, pp7 = lk.forward(res.mean[:K], np.array(keep, np.int32), grid="raw")
     results, plots, chains = [], [], []
     for k, c in enumerate(keep):
         t, m, p = cl.cell(c)
@@ -427,9 +508,32 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     dens = None
     if res.dens is not None:
         dens = [dens_entry(res.dens, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
-    return FitResult(cl.name, results, plots, chains, res.accept_rate, int(res.n_evals.sum()), res.elapsed_ms,
-                     np.array(keep, np.int64) + off, res.final_theta, MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag,
-                     MCMCcov=cov)
+    rh = None
+    if res.rhat is not None:
+        rh = [rhat_entry(res.rhat, k, int(cl.lengths[c]), off + c + 1, res.mean[k::K], res.accept_rate[k::K])
+              for k, c in enumerate(keep)]
+    return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
+                     res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMCrhat=rh,
+                     MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+
+
+def rhat_entry(cr: ChainRhat, k: int, n: int, cell_index: int, mean_rep: np.ndarray, accept_rep: np.ndarray) -> Dict:
+    """One ``MCMCrhat`` entry (``RHAT_FIELDS``) from group ``k`` of ``cr``, a cell of ``n`` points: the four vectors
+    trimmed to the cell's ``P = 7 + n`` theta columns (order: ``THETA_INDEX``, then dR) with s2 appended as the last
+    column, as :func:`dens_entry` lays columns out. ``mean_rep`` ``[M, >= P]`` and ``accept_rep`` ``[M]``: the
+    replicates' posterior means and acceptance rates. ``rhat_max``: the largest classic or split factor over the
+    ``P + 1`` columns, NaN left out (NaN when there is none)."""
+    P = 7 + n
+    join = lambda a, b: np.concatenate([a[k, :P], [b[k]]])  # noqa: E731
+    d = {"rhat": join(cr.rhat, cr.s2_rhat), "rhat_split": join(cr.rhat_split, cr.s2_rhat_split),
+         "pooled_mean": join(cr.pooled_mean, cr.s2_pooled_mean), "pooled_std": join(cr.pooled_std, cr.s2_pooled_std),
+         "mean_rep": np.array(mean_rep[:, :P]), "accept_rep": np.array(accept_rep)}
+    both = np.concatenate([d["rhat"], d["rhat_split"]])
+    d["rhat_max"] = float(np.max(both[~np.isnan(both)])) if not np.all(np.isnan(both)) else float("nan")
+    d["n_rows"] = int(cr.n_rows)
+    d["n_chains"] = int(len(d["accept_rep"]))
+    d["cell_index"] = int(cell_index)
+    return {f: d[f] for f in RHAT_FIELDS}
 
 
 def dens_entry(cd: ChainDens, k: int, n: int, cell_index: int) -> Dict:
@@ -583,6 +687,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCcov"] = _struct_array(fit_result.MCMCcov, COV_FIELDS)
     if fit_result.MCMCquant is not None:  # only a fit with quantiles=probs
         variables["MCMCquant"] = _struct_array(fit_result.MCMCquant, QUANT_FIELDS)
+    if fit_result.MCMCrhat is not None:  # only a fit with replicates > 1 or rhat=True
+        variables["MCMCrhat"] = _struct_array(fit_result.MCMCrhat, RHAT_FIELDS)
     if fit_result.MCMCdens is not None:  # only a fit with density=True
         variables["MCMCdens"] = _struct_array(fit_result.MCMCdens, DENS_FIELDS)
     sio.savemat(base + ".mat", variables)

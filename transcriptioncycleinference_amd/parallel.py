@@ -285,7 +285,12 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
 
     ``density=True`` (or a dict of its options) is passed on to :func:`mcmc.fit` untouched, like
     ``covariance=True``: every rank's ``local`` carries the ``MCMCdens`` of its own cells. The gathered result's
-    ``MCMCdens`` stays ``None``: the per-cell ``[n_grid, 7 + N + 1]`` blocks are not gathered."""
+    ``MCMCdens`` stays ``None``: the per-cell ``[n_grid, 7 + N + 1]`` blocks are not gathered.
+
+    ``replicates=M`` / ``rhat=...`` are passed on to :func:`mcmc.fit` untouched too: every rank runs the M chains
+    of its own cells (a replicate's x0 and RNG stream are keyed by the dataset-wide cell index and the replicate, :func:`mcmc.replicate_keys`), the
+    gathered ``MCMCresults`` / ``MCMCplot`` are replicate 0's, and every rank's ``local`` carries the ``MCMCrhat`` of
+    its own cells. The gathered result's ``MCMCrhat`` stays ``None``."""
     import time
 
     import torch
