@@ -549,6 +549,93 @@ int tci_dram_run_rhat(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chain
                       tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
                       const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout);
 
+/* ---- Replicate chains pooled: the multi-chain effective sample size (the n_eff of BDA3 section 11.5) ----
+ * What the pooled posterior of a group of chains is worth in independent draws, with the between-chain variance
+ * charged to the autocorrelation (Gelman et al., BDA3 section 11.5; Geyer 1992), and the pooled mean's Monte-Carlo
+ * standard error. mcmcstat has no such function: the formulas below are the definition. The group, the column, the s2
+ * column and the sequences are tci_chainrhat's: a group's chains in ascending chain index; the whole chain, rows
+ * [0, n); half A, rows [0, h), and half B, rows [n - h, n), h = floor(n / 2); `classic` uses the m = M whole chains,
+ * L = n; `split` the m = 2 M halves, L = h, ordered A, B per chain. All in FP64, every operation rounded once as
+ * written, never fused, except the lag sums (below).
+ *   mu_j, s2_j, W, mubar (with the equal-means rule) and T are exactly tci_chainrhat's (the same bits), but m == 1
+ *   is allowed here (the single-chain estimate) with T = 0.
+ *   vplus = ((L - 1) / L) * W + T
+ *   y_j[t] = x_j[t] - mu_j
+ *   c_j(k) = sum_{t = 0}^{L - 1 - k} y_j[t] * y_j[t + k]: linear, not circular as tci_chainstats' c(k) is. Summed
+ *            in increasing t from 0.0, each product fused into the sum: acc = fma(y_j[t], y_j[t + k], acc). The order
+ *            follows from L and k alone.
+ *   a(k)   = (sum_j (c_j(k) / L)) / m: every c_j(k) divided by L, the quotients added in sequence order from 0.0, the
+ *            sum divided by m.
+ *   rho(0) = 1;  rho(k) = 1 - (W - a(k)) / vplus for k >= 1
+ *   K      = L - 1 if max_lag == 0, else min(max_lag, L - 1)
+ *   P_i    = rho(2 i) + rho(2 i + 1) for i = 0, 1, .. while 2 i + 1 <= K
+ *   s      the least i >= 1 for which P_i > 0 is false (a NaN stops); if the pairs run out first, their count
+ *   Q_0 = P_0;  Q_i = (P_i < Q_{i-1} ? P_i : Q_{i-1}): Geyer's initial monotone sequence (a NaN Q_0 stays)
+ *   tau    = -1 + 2 * sum_{i < s} Q_i, summed in order from Q_0
+ *   cap    = (m L) * log10(m L), log10 computed once per group on the host
+ *   ess    = tau > 0 ? min((m L) / tau, cap) : cap; NaN when tau is NaN
+ *   window = 2 s, the lags summed
+ *   mcse   = pooled_std / sqrt(ess), pooled_std tci_chainrhat's; classic only
+ * Consequences:
+ *   L < 2: tau, ess and mcse are NaN and window is 0. So split is NaN for n < 4; n = 2 and n = 3 have P_0 only.
+ *   No pair stopped and K < L - 1 (max_lag ended it): tau = +Inf, ess = 0, window = 2 s: tci_chainstats' convention.
+ *     Running out of lags at K = L - 1 is a finite result.
+ *   vplus == 0 (W = T = 0, a constant column): tau, ess and mcse are NaN (0/0); window = 2 s as the NaN stops it.
+ *   W == 0 < T (each chain constant, at different values): every a(k) is 0 and every rho is 1 by the formula; nothing
+ *     is special-cased: no pair stops.
+ *   A non-finite entry (NaN or +-Inf) anywhere in a group's column: every output of that column is NaN and its
+ *     windows are -1, as in tci_chainrhat; such a column is flagged before the lag loop and never enters it.
+ *   Padding (j >= npar) and every output of a group id no chain carries: NaN / -1. All chains of a group must have
+ *     the same npar (TCI_EINVAL, the group named in the message).
+ *   Every device loop over lags is bounded by K; none ends on a floating comparison alone. The stop is a
+ *     discontinuous decision: the device takes it on its own FP64 values, with no tolerance.
+ * Bits. An output's bits depend on the group's columns in chain order, on n and on max_lag alone: not on n_chains,
+ * where the chains sit, how groups interleave, ld or how many workgroups ran (the moments are tci_chainrhat's; one
+ * lane sums a lag in the order above whatever the tiles are).
+ * Error bound. With u = 2^-53, X = max|x| over the group's column, lambda = L / (L - 1), and for the same stop s:
+ *   E_a  = 8 u X sqrt(W) + (L + m + 6) u W + 36 (u X)^2                       |a(k) - exact|
+ *   E_Wa = E_a + (L + m + 5) u W + 32 (u X)^2                                 |(W - a(k)) - exact|
+ *   E_v  = (L + 2 m + 10) u vplus + 12 u X sqrt(T) + (2 m^2 + 96) (u X)^2     |vplus - exact|
+ *   E_rho = (E_Wa + 2 lambda E_v) / vplus + (4 lambda + 1) u
+ *   E_P  = 2 E_rho + (2 + 4 lambda) u
+ *   |tau - exact| <= E_tau = 2 s E_P + (s + 2) u (|tau| + 1)
+ *   |ess - exact| <= 4 u cap + 1.01 ess E_tau / |tau|   (the second term where (m L) / tau <= 2 cap)
+ *   |mcse - exact| <= mcse (E_std / pooled_std + 0.505 E_ess / ess + 3 u), E_std tci_chainrhat's bound
+ * of the formulas evaluated without rounding: the roundings of the L - k products and their sum, the cancellation in
+ * y = x - mu_j (the 8 u X sqrt(W) term), in W - a(k) and in mu_j - mubar (12 u X sqrt(T)), and the sum of s pairs
+ * (DESIGN.md section 7g and tests/chainess_oracle.py have the derivation). */
+typedef struct {
+  int64_t max_lag;  /* cap on the lags; 0 = none (L - 1) */
+  int64_t flags;    /* reserved, must be 0 */
+} tci_chainess_options;
+
+/* Host buffers (any pointer may be NULL). Per-group vectors have stride ld. */
+typedef struct {
+  double *ess, *ess_split, *tau, *tau_split, *mcse;                /* [n_groups][ld] */
+  int32_t *window, *window_split;                                  /* [n_groups][ld] */
+  double *s2_ess, *s2_ess_split, *s2_tau, *s2_tau_split, *s2_mcse; /* [n_groups]; NaN without an s2 chain */
+  int32_t *s2_window, *s2_window_split;                            /* [n_groups]; -1 without an s2 chain */
+  int64_t n_rows;    /* written: rows the reduction used */
+  double kernel_ms;  /* written: device time of the kernels (HIP events), the moments' kernels included */
+} tci_chainess_outputs;
+
+int tci_chainess_defaults(tci_chainess_options* opt);
+
+/* The reduction of a chain already on the host; arguments, rules and error codes as for tci_chainrhat, plus
+ * TCI_EINVAL for max_lag < 0. */
+int tci_chainess(tci_ctx* ctx, const tci_chainess_options* opt, const double* chain, const double* s2chain,
+                 int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, const int32_t* group,
+                 int64_t n_groups, tci_chainess_outputs* out);
+
+/* tci_dram_run_rhat plus the effective sample size of the same groups over the same rows, both taken from the device
+ * chain before any copy. rout may be NULL here (no R-hat outputs); eout is required; ropt and eopt may be NULL. */
+int tci_dram_run_ess(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                     const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                     const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                     tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                     const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                     tci_chainess_outputs* eout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -74,6 +74,11 @@
 //          group: 1 x n, the 1-based group of every chain (0 = in no group), or []: all chains form one group.
 //          out: struct with rhat, rhat_split, pooled_mean, pooled_std (P x n_groups, n_groups = max(group); NaN
 //          past a group's npar) and n_rows.
+//   out = tci_mex('chainess', h, chain, npar, group[, max_lag])
+//          the multi-chain effective sample size of replicate chains (BDA3 11.5; tci_chainess, the definition is in
+//          include/tci.h), reduced on the device: arguments as for 'chainrhat'; max_lag: cap on the lags (default 0 =
+//          none). out: struct with ess, ess_split, tau, tau_split, mcse, window, window_split (P x n_groups; the
+//          windows as doubles; NaN / -1 past a group's npar) and n_rows.
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -857,6 +862,82 @@ void cmd_chainrhat(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = res;
 }
 
+// ---- 'chainess': the multi-chain effective sample size of every group of replicate chains ---------------
+
+void cmd_chainess(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs != 5 && nrhs != 6) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chainess', h, chain, npar, group[, max_lag])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[3], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  std::vector<int32_t> group;  // 0-based for the ABI; MATLAB's 0 (no group) becomes -1
+  size_t ng = 1;
+  if (mxGetNumberOfElements(prhs[4]) != 0) {  // [] = one group of all chains
+    const double* gp = doubles(prhs[4], (long long)n, "group");
+    group.resize(n);
+    ng = 0;
+    for (size_t b = 0; b < n; ++b) {
+      if (!(gp[b] >= 0 && gp[b] <= (double)n) || gp[b] != (double)(int64_t)gp[b])
+        mexErrMsgIdAndTxt("tci:arg", "group(%d) must be an integer in [0, n]", (int)b + 1);
+      group[b] = (int32_t)gp[b] - 1;
+      ng = std::max(ng, (size_t)gp[b]);
+    }
+    if (ng < 1) mexErrMsgIdAndTxt("tci:arg", "group names no group (all zero)");
+  }
+  tci_chainess_options opt;
+  tci_chainess_defaults(&opt);
+  if (nrhs == 6) {
+    const double* ml = doubles(prhs[5], 1, "max_lag");
+    if (!(ml[0] >= 0 && ml[0] <= 1073741824.0) || ml[0] != (double)(int64_t)ml[0])
+      mexErrMsgIdAndTxt("tci:arg", "max_lag must be an integer in [0, 2^30]");
+    opt.max_lag = (int64_t)ml[0];
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  static const char* fields[] = {"ess", "ess_split", "tau", "tau_split", "mcse", "window", "window_split", "n_rows"};
+  mxArray* res = mxCreateStructMatrix(1, 1, 8, fields);
+  mxArray* vals[7];
+  for (int f = 0; f < 7; ++f) {
+    vals[f] = mxCreateDoubleMatrix(P, ng, mxREAL);  // P x n_groups == the ABI's [group][P]
+    mxSetField(res, 0, fields[f], vals[f]);
+  }
+  std::vector<int32_t> win(2 * P * ng);
+  tci_chainess_outputs out;
+  memset(&out, 0, sizeof out);
+  out.ess = mxGetPr(vals[0]);
+  out.ess_split = mxGetPr(vals[1]);
+  out.tau = mxGetPr(vals[2]);
+  out.tau_split = mxGetPr(vals[3]);
+  out.mcse = mxGetPr(vals[4]);
+  out.window = win.data();
+  out.window_split = win.data() + P * ng;
+  const int rc = tci_chainess(ctx, &opt, X, nullptr, (int64_t)rows, (int64_t)n, (int64_t)P,
+                              npar.empty() ? nullptr : npar.data(), group.empty() ? nullptr : group.data(), (int64_t)ng,
+                              &out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_chainess");
+  }
+  for (int f = 0; f < 2; ++f) {
+    double* w = mxGetPr(vals[5 + f]);
+    for (size_t e = 0; e < P * ng; ++e) w[e] = (double)win[f * P * ng + e];
+  }
+  mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+  plhs[0] = res;
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -878,6 +959,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chainquant") cmd_chainquant(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chaindens") cmd_chaindens(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainrhat") cmd_chainrhat(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chainess") cmd_chainess(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

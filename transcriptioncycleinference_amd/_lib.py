@@ -125,6 +125,17 @@ class tci_chainrhat_outputs(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class tci_chainess_options(C.Structure):
+    _fields_ = [("max_lag", C.c_int64), ("flags", C.c_int64)]
+
+
+class tci_chainess_outputs(C.Structure):
+    _fields_ = [("ess", _dp), ("ess_split", _dp), ("tau", _dp), ("tau_split", _dp), ("mcse", _dp), ("window", _i32p),
+                ("window_split", _i32p), ("s2_ess", _dp), ("s2_ess_split", _dp), ("s2_tau", _dp), ("s2_tau_split", _dp),
+                ("s2_mcse", _dp), ("s2_window", _i32p), ("s2_window_split", _i32p), ("n_rows", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -176,6 +187,14 @@ SIGNATURES = [
                                     _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
                                     C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
                                     C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs)]),
+    ("tci_chainess_defaults", C.c_int, [C.POINTER(tci_chainess_options)]),
+    ("tci_chainess", C.c_int, [C.c_void_p, C.POINTER(tci_chainess_options), _dp, _dp, C.c_int64, C.c_int64,
+                               C.c_int64, _i32p, _i32p, C.c_int64, C.POINTER(tci_chainess_outputs)]),
+    ("tci_dram_run_ess", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                   _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                   C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
+                                   C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                   C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

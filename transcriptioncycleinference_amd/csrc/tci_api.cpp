@@ -990,11 +990,15 @@ int chainrhat_groups(tci_ctx* ctx, const char* who, const tci_chainrhat_options*
 // the caller's host buffers (d_npar null: ld columns for every chain; d_s2 null: the s2 twins are NaN).
 int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
                      int64_t n_chains, int64_t ld, const int32_t* d_npar, const RhatGroups& G, int64_t n_groups,
-                     tci_chainrhat_outputs* out) {
+                     tci_chainrhat_outputs* out, int64_t max_lag = 0, tci_chainess_outputs* eout = nullptr) {
   const size_t ldc = (size_t)ld + 1, L = (size_t)ld, ng = (size_t)n_groups, plane = ng * ldc;
   DevAllocs A;
   hipError_t e = hipSuccess;
   void* d_scratch = A.alloc<uint8_t>(G.scratch, &e);
+  // the effective sample size (eout): five more planes of doubles, two of windows and the groups' caps
+  double* d_ed = e == hipSuccess && eout ? A.alloc<double>(5 * plane, &e) : nullptr;
+  int32_t* d_ew = e == hipSuccess && eout ? A.alloc<int32_t>(2 * plane, &e) : nullptr;
+  double* d_cap = e == hipSuccess && eout ? A.alloc<double>(2 * ng, &e) : nullptr;
   double* d_o = e == hipSuccess ? A.alloc<double>(4 * plane, &e) : nullptr;
   int32_t* d_group = e == hipSuccess ? A.alloc<int32_t>(G.group.size(), &e) : nullptr;
   int32_t* d_off = e == hipSuccess ? A.alloc<int32_t>(G.off.size(), &e) : nullptr;
@@ -1004,9 +1008,22 @@ int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const
     return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the group reduction (" +
                                      std::to_string(G.scratch + 4 * plane * sizeof(double)) + " bytes) failed");
   }
-  std::vector<double> ho;
+  std::vector<double> ho, he, hcap;
+  std::vector<int32_t> hw;
   try {
     ho.resize(4 * plane);
+    if (eout) {
+      he.resize(5 * plane);
+      hw.resize(2 * plane);
+      hcap.assign(2 * ng, 0.0);
+      const int64_t h = n_rows / 2;
+      for (size_t g = 0; g < ng; ++g) {  // cap = (m L) log10(m L): classic m = M, L = n; split m = 2 M, L = h
+        const int64_t M = G.off[g + 1] - G.off[g];
+        const double tc = (double)(M * n_rows), ts = (double)(2 * M * h);
+        hcap[g] = tc > 0 ? tc * std::log10(tc) : 0.0;
+        hcap[ng + g] = ts > 0 ? ts * std::log10(ts) : 0.0;
+      }
+    }
   } catch (const std::bad_alloc&) {
     return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
   }
@@ -1022,12 +1039,17 @@ int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const
   e = hipMemcpyAsync(d_group, G.group.data(), G.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_off, G.off.data(), G.off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_list, G.list.data(), G.list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && eout) e = hipMemcpyAsync(d_cap, hcap.data(), hcap.size() * sizeof(double), hipMemcpyHostToDevice, s);
   hipError_t e1 = e == hipSuccess ? hipEventRecord(ev0, s) : e;
   const int rc = e != hipSuccess ? TCI_OK
-                                 : tci::launch_chainrhat(d_chain, d_s2, n_rows, n_chains, ld, d_npar, d_group, n_groups,
-                                                         d_off, d_list, d_scratch, d_o, (void*)s);
+                 : eout ? tci::launch_chainess(d_chain, d_s2, n_rows, n_chains, ld, d_npar, d_group, n_groups, d_off,
+                                               d_list, max_lag, d_cap, d_scratch, d_o, d_ed, d_ew, (void*)s)
+                        : tci::launch_chainrhat(d_chain, d_s2, n_rows, n_chains, ld, d_npar, d_group, n_groups,
+                                                d_off, d_list, d_scratch, d_o, (void*)s);
   if (e1 == hipSuccess) e1 = hipEventRecord(ev1, s);
   if (rc == TCI_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(ho.data(), d_o, 4 * plane * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (rc == TCI_OK && e1 == hipSuccess && eout) e1 = hipMemcpyAsync(he.data(), d_ed, 5 * plane * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (rc == TCI_OK && e1 == hipSuccess && eout) e1 = hipMemcpyAsync(hw.data(), d_ew, 2 * plane * sizeof(int32_t), hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);
   float ms = 0.f;
   if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
@@ -1037,16 +1059,38 @@ int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const
   if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
   if (e2 != hipSuccess) return hip_fail(ctx, e2, "chain R-hat kernels");
   if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain R-hat copy");
-  double* const dst[4] = {out->rhat, out->rhat_split, out->pooled_mean, out->pooled_std};
-  double* const dst2[4] = {out->s2_rhat, out->s2_rhat_split, out->s2_pooled_mean, out->s2_pooled_std};
-  for (size_t t = 0; t < 4; ++t)
+  if (out) {
+    double* const dst[4] = {out->rhat, out->rhat_split, out->pooled_mean, out->pooled_std};
+    double* const dst2[4] = {out->s2_rhat, out->s2_rhat_split, out->s2_pooled_mean, out->s2_pooled_std};
+    for (size_t t = 0; t < 4; ++t)
+      for (size_t g = 0; g < ng; ++g) {
+        const double* src = ho.data() + (t * ng + g) * ldc;
+        if (dst[t]) std::memcpy(dst[t] + g * L, src, L * sizeof(double));
+        if (dst2[t]) dst2[t][g] = src[L];
+      }
+    out->n_rows = n_rows;
+    out->kernel_ms = ms;
+  }
+  if (eout) {
+    double* const dst[5] = {eout->ess, eout->ess_split, eout->tau, eout->tau_split, eout->mcse};
+    double* const dst2[5] = {eout->s2_ess, eout->s2_ess_split, eout->s2_tau, eout->s2_tau_split, eout->s2_mcse};
+    int32_t* const wdst[2] = {eout->window, eout->window_split};
+    int32_t* const wdst2[2] = {eout->s2_window, eout->s2_window_split};
     for (size_t g = 0; g < ng; ++g) {
-      const double* src = ho.data() + (t * ng + g) * ldc;
-      if (dst[t]) std::memcpy(dst[t] + g * L, src, L * sizeof(double));
-      if (dst2[t]) dst2[t][g] = src[L];
+      for (size_t t = 0; t < 5; ++t) {
+        const double* src = he.data() + (t * ng + g) * ldc;
+        if (dst[t]) std::memcpy(dst[t] + g * L, src, L * sizeof(double));
+        if (dst2[t]) dst2[t][g] = src[L];
+      }
+      for (size_t t = 0; t < 2; ++t) {
+        const int32_t* src = hw.data() + (t * ng + g) * ldc;
+        if (wdst[t]) std::memcpy(wdst[t] + g * L, src, L * sizeof(int32_t));
+        if (wdst2[t]) wdst2[t][g] = src[L];
+      }
     }
-  out->n_rows = n_rows;
-  out->kernel_ms = ms;
+    eout->n_rows = n_rows;
+    eout->kernel_ms = ms;
+  }
   return TCI_OK;
 }
 
@@ -1056,6 +1100,9 @@ struct RhatAsk {
   const int32_t* group;
   int64_t n_groups;
   tci_chainrhat_outputs* rout;
+  const char* who = "tci_dram_run_rhat";
+  const tci_chainess_options* eopt = nullptr;  // tci_dram_run_ess: the effective sample size too (rout may be null)
+  tci_chainess_outputs* eout = nullptr;
 };
 
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
@@ -1186,12 +1233,16 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   int64_t r_k0 = 0, r_rows = 0;  // and so does the group reduction
   if (rhat) {
     if (opt->thin <= 0)
-      return fail(ctx, TCI_EINVAL, "tci_dram_run_rhat: the group reduction needs the kept rows (thin >= 1)");
+      return fail(ctx, TCI_EINVAL, std::string(rhat->who) + ": the group reduction needs the kept rows (thin >= 1)");
     const int64_t from = std::max<int64_t>(opt->stats_from, 1);
     r_k0 = (from - 1 + opt->thin - 1) / opt->thin;
     r_rows = (opt->n_steps + opt->thin - 1) / opt->thin - r_k0;
     if (r_rows < 2)
-      return fail(ctx, TCI_EINVAL, "tci_dram_run_rhat: fewer than 2 kept rows at or past stats_from (n_rows < 2)");
+      return fail(ctx, TCI_EINVAL, std::string(rhat->who) + ": fewer than 2 kept rows at or past stats_from (n_rows < 2)");
+    if (rhat->eout && rhat->eopt && rhat->eopt->max_lag < 0)
+      return fail(ctx, TCI_EINVAL, std::string(rhat->who) + ": max_lag must be >= 0");
+    if (rhat->eout && rhat->eopt && rhat->eopt->flags != 0)
+      return fail(ctx, TCI_EINVAL, std::string(rhat->who) + ": flags is reserved and must be 0");
   }
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
@@ -1211,7 +1262,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   }
   RhatGroups r_groups;
   if (rhat) {
-    rc = chainrhat_groups(ctx, "tci_dram_run_rhat", rhat->ropt, r_rows, n_chains, ld, npar.data(), rhat->group,
+    rc = chainrhat_groups(ctx, rhat->who, rhat->ropt, r_rows, n_chains, ld, npar.data(), rhat->group,
                           rhat->n_groups, &r_groups);
     if (rc != TCI_OK) return rc;
   }
@@ -1318,7 +1369,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : cvout ? "tci_dram_run_cov" : rhat ? "tci_dram_run_rhat" : "tci_dram_run_reduced") +
+      return fail(ctx, TCI_ENOMEM, std::string(sout ? "tci_dram_run_stats" : cvout ? "tci_dram_run_cov" : rhat ? rhat->who : "tci_dram_run_reduced") +
                                        ": the device chain (" +
                                        std::to_string((size_t)n_keep * n * L * sizeof(double)) + " bytes) does not fit");
     }
@@ -1592,9 +1643,9 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     if (rc != TCI_OK) return rc;
   }
   if (rhat)
-    return chainrhat_device(ctx, "tci_dram_run_rhat", st.chain_out + (size_t)r_k0 * n * L,
+    return chainrhat_device(ctx, rhat->who, st.chain_out + (size_t)r_k0 * n * L,
                             st.s2_out + (size_t)r_k0 * n, r_rows, n_chains, ld, st.npar, r_groups, rhat->n_groups,
-                            rhat->rout);
+                            rhat->rout, rhat->eout && rhat->eopt ? rhat->eopt->max_lag : 0, rhat->eout);
   return TCI_OK;
 }
 
@@ -1755,6 +1806,69 @@ int tci_dram_run_rhat(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chain
   const RhatAsk ask{ropt, group, n_groups, rout};
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
                        out, red ? *red : tci_dram_reductions{}, &ask);
+}
+
+int tci_dram_run_ess(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                     const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                     const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                     tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                     const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                     tci_chainess_outputs* eout) {
+  if (!ctx) return TCI_EINVAL;
+  if (!eout) return fail(ctx, TCI_EINVAL, "tci_dram_run_ess: null effective sample size outputs");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_dram_run_ess: n_groups must be in [1, n_chains]");
+  const RhatAsk ask{ropt, group, n_groups, rout, "tci_dram_run_ess", eopt, eout};
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, red ? *red : tci_dram_reductions{}, &ask);
+}
+
+int tci_chainess_defaults(tci_chainess_options* o) {
+  if (!o) return TCI_EINVAL;
+  o->max_lag = 0;  // L - 1: the pairs are summed until Geyer's sequence stops
+  o->flags = 0;
+  return TCI_OK;
+}
+
+int tci_chainess(tci_ctx* ctx, const tci_chainess_options* opt, const double* chain, const double* s2chain,
+                 int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, const int32_t* group,
+                 int64_t n_groups, tci_chainess_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chainess: null argument");
+  if (n_rows < 1) return fail(ctx, TCI_EINVAL, "tci_chainess: n_rows must be >= 1");
+  if (opt && opt->max_lag < 0) return fail(ctx, TCI_EINVAL, "tci_chainess: max_lag must be >= 0");
+  if (opt && opt->flags != 0) return fail(ctx, TCI_EINVAL, "tci_chainess: flags is reserved and must be 0");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chainess: n_chains and ld must be >= 1");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_chainess: n_groups must be in [1, n_chains]");
+  if (npar)
+    for (int64_t c = 0; c < n_chains; ++c)
+      if (npar[c] < 0 || npar[c] > ld)
+        return fail(ctx, TCI_ERANGE, "tci_chainess: npar[" + std::to_string(c) + "] outside [0, ld]");
+  RhatGroups G;
+  const int rc = chainrhat_groups(ctx, "tci_chainess", nullptr, n_rows, n_chains, ld, npar, group, n_groups, &G);
+  if (rc != TCI_OK) return rc;
+  const size_t per_row = (size_t)n_chains * (size_t)ld;
+  if (per_row > (((size_t)1 << 46) / sizeof(double)) / (size_t)n_rows)
+    return fail(ctx, TCI_ENOMEM, "tci_chainess: the chain is larger than any device memory");
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t nch = (size_t)n_rows * per_row, ns2 = (size_t)n_rows * (size_t)n_chains;
+  double* d_chain = A.alloc<double>(nch, &e);
+  double* d_s2 = e == hipSuccess && s2chain ? A.alloc<double>(ns2, &e) : nullptr;
+  int32_t* d_npar = e == hipSuccess && npar ? A.alloc<int32_t>((size_t)n_chains, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chainess: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_s2) TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  return chainrhat_device(ctx, "tci_chainess", d_chain, d_s2, n_rows, n_chains, ld, d_npar, G, n_groups, nullptr,
+                          opt ? opt->max_lag : 0, out);
 }
 
 int tci_chainrhat_defaults(tci_chainrhat_options* o) {

@@ -26,6 +26,7 @@
 
 #include <cmath>
 
+#include "tci_chainrhat_dev.h"
 #include "tci_csum.h"
 #include "tci_internal.h"
 
@@ -38,9 +39,7 @@ constexpr int kCrWaves = 4;   // wavefronts per workgroup
 constexpr int kCrRU = 8;      // rows a wavefront loads together
 constexpr int kCrSeg = 256;   // rows per segment
 constexpr int kCrThreads = kCrCols * kCrWaves;
-constexpr int kCrSeq = 3;     // sequences per chain column: whole, half A, half B
 
-enum : int32_t { CR_PAD = 0, CR_OK = 1, CR_BAD = 2 };
 enum : uint32_t { CR_F_BAD = 1u };  // bit 1 + q: sequence q is not constant
 
 struct CrView {
@@ -50,17 +49,6 @@ struct CrView {
   const int32_t* group;  // [n_chains]; < 0: the chain belongs to no group
   int64_t n_chains, ld;
 };
-
-// The scratch of one call, carved from one allocation (8-byte items first).
-struct CrScratch {
-  double *p_s, *p_c;  // [S][kCrSeq][ncol] compensated sums (pass 1); p_s again: centred squares (pass 2)
-  double* mu;         // [kCrSeq][ncol]
-  double* var;        // [kCrSeq][ncol]
-  uint32_t* p_f;      // [S][ncol] flags
-  int32_t* state;     // [ncol]
-};
-
-__device__ __forceinline__ double cr_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 __device__ __forceinline__ bool cr_live(const CrView& v, int64_t c, int64_t j) {
   return j < v.ld ? j < (v.npar ? (int64_t)v.npar[c] : v.ld) : (j == v.ld && v.s2 != nullptr);
@@ -241,39 +229,6 @@ __global__ __launch_bounds__(kCrThreads) void k_cr_var(CrView v, int64_t n, int6
   }
 }
 
-// The m sequences of one group column, in order: sequence k is sequence q0 + k % nq of the group's chain k / nq.
-struct CrSeqs {
-  const double *mu, *var;  // CrScratch's
-  const int32_t* list;     // the group's chains
-  int64_t ldc, ncol, j;
-  int q0, nq;
-  __device__ __forceinline__ int64_t at(int64_t k) const {
-    return (int64_t)(q0 + (int)(k % nq)) * ncol + (int64_t)list[k / nq] * ldc + j;
-  }
-};
-
-// sum_v = sum_k s2_k, mubar and dev = sum_k (mu_k - mubar)^2 of the sequences; equal means: mubar is their value.
-__device__ __forceinline__ void cr_between(const CrSeqs& q, int64_t m, double* sum_v, double* mubar, double* dev) {
-  double sv = 0.0, sm = 0.0;
-  const double first = q.mu[q.at(0)];
-  bool same = true;
-  for (int64_t k = 0; k < m; ++k) {
-    const double mu = q.mu[q.at(k)];
-    sv += q.var[q.at(k)];
-    sm += mu;
-    same &= mu == first;
-  }
-  const double mb = same ? first : sm / (double)m;
-  double dv = 0.0;
-  for (int64_t k = 0; k < m; ++k) {
-    const double d = q.mu[q.at(k)] - mb;
-    dv += d * d;
-  }
-  *sum_v = sv;
-  *mubar = mb;
-  *dev = dv;
-}
-
 __device__ __forceinline__ double cr_rhat(double sum_v, double dev, int64_t m, int64_t L) {
   if (m < 2 || L < 2) return cr_nan();
   const double W = sum_v / (double)m;
@@ -337,7 +292,34 @@ int cr_sizes(int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups, CrS
   return TCI_OK;
 }
 
+// The scratch's arrays.
+CrScratch cr_carve(void* scratch, const CrSizes& z) {
+  const size_t sn = (size_t)z.S * (size_t)z.ncol, nc = (size_t)z.ncol;
+  CrScratch sc;
+  double* p8 = (double*)scratch;
+  sc.p_s = p8;
+  sc.p_c = p8 + kCrSeq * sn;
+  sc.mu = p8 + 2 * kCrSeq * sn;
+  sc.var = sc.mu + kCrSeq * nc;
+  uint32_t* p4 = (uint32_t*)(p8 + z.items8);
+  sc.p_f = p4;
+  sc.state = (int32_t*)(p4 + sn);
+  return sc;
+}
+
 }  // namespace
+
+int chainrhat_scratch_moments(void* scratch, int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups,
+                              const double** mu, const double** var, const int32_t** state) {
+  CrSizes z;
+  const int rc = cr_sizes(n_rows, n_chains, ld, n_groups, &z);
+  if (rc != TCI_OK) return rc;
+  const CrScratch sc = cr_carve(scratch, z);
+  *mu = sc.mu;
+  *var = sc.var;
+  *state = sc.state;
+  return TCI_OK;
+}
 
 int chainrhat_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups, size_t* bytes) {
   CrSizes z;
@@ -354,16 +336,7 @@ int launch_chainrhat(const double* chain, const double* s2, int64_t n_rows, int6
   CrSizes z;
   const int rc = cr_sizes(n_rows, n_chains, ld, n_groups, &z);
   if (rc != TCI_OK) return rc;
-  const size_t sn = (size_t)z.S * (size_t)z.ncol, nc = (size_t)z.ncol;
-  CrScratch sc;
-  double* p8 = (double*)scratch;
-  sc.p_s = p8;
-  sc.p_c = p8 + kCrSeq * sn;
-  sc.mu = p8 + 2 * kCrSeq * sn;
-  sc.var = sc.mu + kCrSeq * nc;
-  uint32_t* p4 = (uint32_t*)(p8 + z.items8);
-  sc.p_f = p4;
-  sc.state = (int32_t*)(p4 + sn);
+  const CrScratch sc = cr_carve(scratch, z);
   const CrView v{chain, s2, npar, group, n_chains, ld};
   const int64_t h = n_rows / 2;
   hipStream_t st = (hipStream_t)stream;

@@ -142,5 +142,21 @@ int launch_chainrhat(const double* chain, const double* s2, int64_t n_rows, int6
                      const int32_t* g_list, void* scratch, double* out, void* stream);
 // The scratch launch_chainrhat needs; TCI_ERANGE when the sizes do not fit the launch grid, TCI_ENOMEM above 2^46 bytes.
 int chainrhat_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups, size_t* bytes);
+// Where launch_chainrhat left the per-sequence moments in its scratch: mu, var [3][n_chains * (ld + 1)] (whole chain,
+// half A, half B) and state [n_chains * (ld + 1)] (tci_chainrhat_dev.h). Same codes as chainrhat_scratch_bytes.
+int chainrhat_scratch_moments(void* scratch, int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups,
+                              const double** mu, const double** var, const int32_t** state);
+
+// Multi-chain effective sample size (tci_chainess.hip) of every group of chains of a device chain; arguments as for
+// launch_chainrhat, which it launches first for the moments (scratch: chainrhat_scratch_bytes() bytes; rhat_out
+// (device): launch_chainrhat's out, its pooled_std feeds mcse). max_lag >= 0 (0 = no cap); cap (device):
+// [2][n_groups] = (m L) log10(m L) of the classic and of the split statistic of every group. out_d (device):
+// [5][n_groups][ld + 1] = ess, ess_split, tau, tau_split, mcse; out_w (device): [2][n_groups][ld + 1] = window,
+// window_split. Padding, non-finite columns, column ld without s2 and empty groups are NaN / -1. Asynchronous on
+// `stream`. TCI_EINVAL on a bad size, TCI_ERANGE on a grid above 2^31 - 1 workgroups, TCI_EHIP on a HIP error.
+int launch_chainess(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
+                    const int32_t* npar, const int32_t* group, int64_t n_groups, const int32_t* g_off,
+                    const int32_t* g_list, int64_t max_lag, const double* cap, void* scratch, double* rhat_out,
+                    double* out_d, int32_t* out_w, void* stream);
 
 }  // namespace tci

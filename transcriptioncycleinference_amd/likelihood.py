@@ -230,6 +230,56 @@ class ChainRhat:
                                           P(self.s2_pooled_std), 0, 0.0)
 
 
+ESS_OUTPUTS = ("ess", "ess_split", "tau", "tau_split", "mcse")
+ESS_WINDOWS = ("window", "window_split")
+
+
+@dataclasses.dataclass
+class ChainEss:
+    """Per-group effective sample size across replicate chains (``tci_chainess_outputs``): the multi-chain ESS and
+    autocorrelation time, classic and split, the pooled mean's Monte-Carlo standard error and the lags summed,
+    ``[n_groups, ld]`` for the parameters and ``[n_groups]`` for s2; padding is NaN / -1."""
+
+    ess: np.ndarray
+    ess_split: np.ndarray
+    tau: np.ndarray
+    tau_split: np.ndarray
+    mcse: np.ndarray
+    window: np.ndarray
+    window_split: np.ndarray
+    s2_ess: np.ndarray
+    s2_ess_split: np.ndarray
+    s2_tau: np.ndarray
+    s2_tau_split: np.ndarray
+    s2_mcse: np.ndarray
+    s2_window: np.ndarray
+    s2_window_split: np.ndarray
+    max_lag: int = 0
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n_groups: int, ld: int, max_lag: int = 0) -> "ChainEss":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        w = lambda *s: np.full(s, -1, np.int32)  # noqa: E731
+        g = int(n_groups)
+        if int(max_lag) != max_lag or int(max_lag) < 0:
+            raise ValueError("max_lag must be an integer >= 0")
+        return cls(d(g, ld), d(g, ld), d(g, ld), d(g, ld), d(g, ld), w(g, ld), w(g, ld), d(g), d(g), d(g), d(g), d(g),
+                   w(g), w(g), int(max_lag))
+
+    def options(self) -> "_lib.tci_chainess_options":
+        return _lib.tci_chainess_options(self.max_lag, 0)
+
+    def to_c(self) -> "_lib.tci_chainess_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        I = lambda a: _lib.ptr(a, _lib._i32p)  # noqa: E731,E741
+        return _lib.tci_chainess_outputs(P(self.ess), P(self.ess_split), P(self.tau), P(self.tau_split), P(self.mcse),
+                                         I(self.window), I(self.window_split), P(self.s2_ess), P(self.s2_ess_split),
+                                         P(self.s2_tau), P(self.s2_tau_split), P(self.s2_mcse), I(self.s2_window),
+                                         I(self.s2_window_split), 0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -506,6 +556,37 @@ class Likelihood:
                                             C.byref(out)))
         cr.n_rows, cr.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return cr
+
+    def chainess(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, group=None,
+                 max_lag: int = 0) -> ChainEss:
+        """The multi-chain effective sample size of replicate chains held on the host (BDA3 11.5, Geyer's initial
+        monotone sequence; the ``n_eff`` beside R-hat), classic and split, with its autocorrelation time, the lags
+        summed and the pooled mean's Monte-Carlo standard error, reduced on the device (``tci_chainess``; the
+        definition is in ``include/tci.h``). Arguments as in :meth:`chainrhat`; a group of one chain gives the
+        single-chain estimate. ``max_lag``: cap on the lags (0 = none); a column the cap ends before its sequence
+        stops has ``tau = inf`` and ``ess = 0``. Returns a :class:`ChainEss`; padding and columns with a non-finite
+        entry are NaN / -1."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = None
+        if s2chain is not None:
+            s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        grp, ng = rhat_groups(group, n, npr)
+        ce = ChainEss.empty(ng, ld, max_lag)
+        opt, out = ce.options(), ce.to_c()
+        self._check(self._lib.tci_chainess(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp),
+                                           rows, n, ld, _lib.ptr(npr, _lib._i32p), _lib.ptr(grp, _lib._i32p), ng,
+                                           C.byref(out)))
+        ce.n_rows, ce.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return ce
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import ChainCov, ChainDens, ChainQuant, ChainRhat, ChainStats, rhat_groups
+from .likelihood import ChainCov, ChainDens, ChainEss, ChainQuant, ChainRhat, ChainStats, rhat_groups
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -54,6 +54,11 @@ DENS_FIELDS = ("grid", "dens", "counts", "range", "bw", "n_rows", "cell_index")
 # classic or split factor of the cell
 RHAT_FIELDS = ("rhat", "rhat_split", "pooled_mean", "pooled_std", "mean_rep", "accept_rep", "rhat_max", "n_rows",
                "n_chains", "cell_index")
+# MCMCess (fit(..., replicates=M, ess=True)): the multi-chain effective sample size of a fitted cell, P + 1 = 7 + N + 1
+# columns wide (theta order, s2 last): ess, ess_split, tau, tau_split, mcse [P + 1] doubles, window, window_split
+# [P + 1] int32; ess_min: the smallest classic or split ess of the cell; max_lag: the cap the fit passed (0 = none)
+ESS_FIELDS = ("ess", "ess_split", "tau", "tau_split", "mcse", "window", "window_split", "ess_min", "max_lag", "n_rows",
+              "n_chains", "cell_index")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -113,6 +118,7 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    ess: Optional[ChainEss] = None                # dram_run(group=ids, ess=True): effective sample size of every group
     rhat: Optional[ChainRhat] = None              # dram_run(group=ids): R-hat / pooled moments of every group of chains
     dens: Optional[ChainDens] = None              # dram_run(dens=True): densities / histograms of the kept rows
     quant: Optional[ChainQuant] = None            # dram_run(quant=probs): quantiles of the kept rows
@@ -123,7 +129,7 @@ class DramResult:
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
-             cov_scratch_bytes: int = 0, quant=None, dens=None, group=None) -> DramResult:
+             cov_scratch_bytes: int = 0, quant=None, dens=None, group=None, ess: bool = False) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -140,7 +146,11 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     ``Likelihood.chaindens`` gives), through ``tci_dram_run_reduced`` too. ``group``: one id per chain (-1 = none):
     also the classic and split R-hat and the pooled mean and standard deviation of every group of chains over those
     same rows, at least 2 of them (``DramResult.rhat``, as ``Likelihood.chainrhat`` gives), reduced from the device
-    chain through ``tci_dram_run_rhat``, with any of the other reductions."""
+    chain through ``tci_dram_run_rhat``, with any of the other reductions. ``ess`` (needs ``group``): also the
+    multi-chain effective sample size of every group over those rows (``DramResult.ess``, as ``Likelihood.chainess``
+    gives, with ``max_lag`` as its cap on the lags), through ``tci_dram_run_ess``."""
+    if ess and group is None:
+        raise ValueError("ess=True needs group: the effective sample size is a statistic of groups of chains")
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
     theta0, lower, upper, prior_mu, prior_sig, qcov_diag = map(f, (theta0, lower, upper, prior_mu, prior_sig,
                                                                     qcov_diag))
@@ -165,11 +175,13 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = cc = cq = cd = cr = None
+    cs = cc = cq = cd = cr = ce = None
     sopt = sout = None
     if group is not None:
         grp, ng = rhat_groups(group, n)
         cr = ChainRhat.empty(ng, ld)
+        if ess:
+            ce = ChainEss.empty(ng, ld, max_lag)
     if quant is not None:
         cq = ChainQuant.empty(n, ld, quant)
     if dens is not None and dens is not False:
@@ -193,8 +205,14 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
             red.copt, red.cout = C.pointer(copt), C.pointer(cout)
         if cr is not None:
             ropt, rout = cr.options(), cr.to_c()
-            lk._check(lk._lib.tci_dram_run_rhat(*args, C.byref(red), _lib.ptr(grp, _lib._i32p), ng, C.byref(ropt),
-                                                C.byref(rout)))
+            if ce is not None:
+                eopt, eout = ce.options(), ce.to_c()
+                lk._check(lk._lib.tci_dram_run_ess(*args, C.byref(red), _lib.ptr(grp, _lib._i32p), ng, C.byref(ropt),
+                                                   C.byref(rout), C.byref(eopt), C.byref(eout)))
+                ce.n_rows, ce.kernel_ms = int(eout.n_rows), float(eout.kernel_ms)
+            else:
+                lk._check(lk._lib.tci_dram_run_rhat(*args, C.byref(red), _lib.ptr(grp, _lib._i32p), ng, C.byref(ropt),
+                                                    C.byref(rout)))
             cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
         else:
             lk._check(lk._lib.tci_dram_run_reduced(*args, C.byref(red)))
@@ -218,7 +236,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
         cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
                       kernel_ms=np.array(out.kernel_ms[:], np.float64),
-                      kernel_launches=np.array(out.kernel_launches[:], np.int64), rhat=cr, dens=cd, quant=cq, stats=cs,
+                      kernel_launches=np.array(out.kernel_launches[:], np.int64), ess=ce, rhat=cr, dens=cd, quant=cq, stats=cs,
                       cov=cc)
 
 
@@ -277,6 +295,7 @@ class FitResult:
     gather_bytes: int = 0                      # parallel.fit_sharded: bytes every rank receives in it
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
+    MCMCess: Optional[List[Dict]] = None       # fit(..., replicates=M, ess=True): ESS_FIELDS per fitted cell
     MCMCrhat: Optional[List[Dict]] = None      # fit(..., replicates=M): RHAT_FIELDS per fitted cell
     MCMCdens: Optional[List[Dict]] = None      # fit(..., density=True): DENS_FIELDS per fitted cell
     MCMCquant: Optional[List[Dict]] = None     # fit(..., quantiles=probs): QUANT_FIELDS per fitted cell
@@ -392,7 +411,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
-        rhat: Optional[bool] = None) -> FitResult:
+        rhat: Optional[bool] = None, ess: bool = False) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -439,7 +458,12 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     ``MCMCchain`` keeps (needs ``thin >= 1`` and 2 such rows), reduced on the device (:func:`rhat_entry`).
     ``rhat=True`` with one replicate gives the split factor alone (the classic one is NaN). With ``thin >= 1`` the
     kept rows of every replicate are copied to the host, M times the one-chain fit's copy, though ``MCMCchain`` keeps
-    replicate 0's alone (``tci_dram_outputs.chain`` is all chains or none)."""
+    replicate 0's alone (``tci_dram_outputs.chain`` is all chains or none).
+
+    ``ess`` (needs ``MCMCrhat``, i.e. replicates or ``rhat=True``): also ``MCMCess``, one dict of ``ESS_FIELDS`` per
+    fitted cell: the multi-chain effective sample size (BDA3 11.5) and autocorrelation time, classic and split, the
+    lags summed and the pooled mean's Monte-Carlo standard error, over the same rows and reduced on the device
+    (:func:`ess_entry`); ``max_lag`` caps its lags as it caps the diagnostics'. Nothing else in the result changes."""
     M = int(replicates)
     if M != replicates or M < 1:
         raise ValueError("replicates must be an integer >= 1")
@@ -447,6 +471,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     if want_rhat and int(thin) < 1:
         raise ValueError("MCMCrhat is reduced from the kept rows: replicates > 1 (or rhat=True) needs thin >= 1; "
                          "pass rhat=False to run the replicates without it")
+    if ess and not want_rhat:
+        raise ValueError("MCMCess is reduced with MCMCrhat: ess=True needs replicates > 1 or rhat=True")
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -463,7 +489,9 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     res = dram_run(lk, np.tile(np.array(keep, np.int32), M), plan.x0, plan.lower, plan.upper, plan.prior_mu,
                    plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys,
                    **(dict(group=np.tile(np.arange(K, dtype=np.int32), M)) if want_rhat else {}),
-                   **(dict(stats=True, max_lag=max_lag) if diagnostics else {}),
+                   **(dict(ess=True) if ess else {}),
+                   **(dict(stats=True) if diagnostics else {}),
+                   **(dict(max_lag=max_lag) if ess or diagnostics else {}),
                    **(dict(cov=True) if covariance else {}),
                    **(dict(quant=quantiles) if quantiles is not None else {}),
                    **(dict(dens=density) if density is not None and density is not False else {}))
@@ -512,9 +540,29 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     if res.rhat is not None:
         rh = [rhat_entry(res.rhat, k, int(cl.lengths[c]), off + c + 1, res.mean[k::K], res.accept_rate[k::K])
               for k, c in enumerate(keep)]
+    es = None
+    if res.ess is not None:
+        es = [ess_entry(res.ess, k, int(cl.lengths[c]), off + c + 1, M) for k, c in enumerate(keep)]
     return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
-                     res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMCrhat=rh,
+                     res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMCess=es, MCMCrhat=rh,
                      MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+
+
+def ess_entry(ce: ChainEss, k: int, n: int, cell_index: int, n_chains: int) -> Dict:
+    """One ``MCMCess`` entry (``ESS_FIELDS``) from group ``k`` of ``ce``, a cell of ``n`` points: the vectors trimmed
+    to the cell's ``P = 7 + n`` theta columns with s2 appended as the last column, as :func:`rhat_entry` lays columns
+    out. ``ess_min``: the smallest classic or split ess over the ``P + 1`` columns, NaN left out (NaN when there is
+    none)."""
+    P = 7 + n
+    d = {f: np.concatenate([getattr(ce, f)[k, :P], [getattr(ce, "s2_" + f)[k]]])
+         for f in ("ess", "ess_split", "tau", "tau_split", "mcse", "window", "window_split")}
+    both = np.concatenate([d["ess"], d["ess_split"]])
+    d["ess_min"] = float(np.min(both[~np.isnan(both)])) if not np.all(np.isnan(both)) else float("nan")
+    d["max_lag"] = int(ce.max_lag)
+    d["n_rows"] = int(ce.n_rows)
+    d["n_chains"] = int(n_chains)
+    d["cell_index"] = int(cell_index)
+    return {f: d[f] for f in ESS_FIELDS}
 
 
 def rhat_entry(cr: ChainRhat, k: int, n: int, cell_index: int, mean_rep: np.ndarray, accept_rep: np.ndarray) -> Dict:
@@ -689,6 +737,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCquant"] = _struct_array(fit_result.MCMCquant, QUANT_FIELDS)
     if fit_result.MCMCrhat is not None:  # only a fit with replicates > 1 or rhat=True
         variables["MCMCrhat"] = _struct_array(fit_result.MCMCrhat, RHAT_FIELDS)
+    if fit_result.MCMCess is not None:  # only a fit with ess=True
+        variables["MCMCess"] = _struct_array(fit_result.MCMCess, ESS_FIELDS)
     if fit_result.MCMCdens is not None:  # only a fit with density=True
         variables["MCMCdens"] = _struct_array(fit_result.MCMCdens, DENS_FIELDS)
     sio.savemat(base + ".mat", variables)

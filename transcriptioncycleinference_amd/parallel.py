@@ -290,7 +290,8 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
     ``replicates=M`` / ``rhat=...`` are passed on to :func:`mcmc.fit` untouched too: every rank runs the M chains
     of its own cells (a replicate's x0 and RNG stream are keyed by the dataset-wide cell index and the replicate, :func:`mcmc.replicate_keys`), the
     gathered ``MCMCresults`` / ``MCMCplot`` are replicate 0's, and every rank's ``local`` carries the ``MCMCrhat`` of
-    its own cells. The gathered result's ``MCMCrhat`` stays ``None``."""
+    its own cells. The gathered result's ``MCMCrhat`` stays ``None``. ``ess=True`` goes the same way: ``MCMCess`` is
+    on every rank's ``local``, and the gathered one stays ``None``."""
     import time
 
     import torch
