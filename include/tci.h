@@ -636,6 +636,88 @@ int tci_dram_run_ess(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains
                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
                      tci_chainess_outputs* eout);
 
+/* ---- Posterior predictive fit checks per cell (WAIC, PIT, coverage, reduced chi^2, Durbin-Watson) ----
+ * Does the fitted model describe a cell's data? Every observed MS2 and PP7 value is scored under the Gaussian-mixture
+ * posterior predictive distribution that S posterior samples (theta_s, sigma2_s) define: (1 / S) sum_s
+ * N(f_s, sigma2_s), f_s the simulated signal. Nothing is drawn: the mixture's density and CDF are evaluated in closed
+ * form, so everything is deterministic. The simulated rows stay in the device scratch, as in tci_predict; only the
+ * pointwise vectors come back. mcmcstat has no such function: the formulas below are the definition (WAIC: Gelman et
+ * al., BDA3 section 7.2, the variance form of the penalty).
+ * Inputs. For k in [0, n_sel): theta[(k*S + s)*ld_theta ..] holds the S posterior samples of cell cell_id[k], as for
+ *   tci_predict; s2[k*S + s] is the sigma2 of the same chain row.
+ * Forward model. Always TCI_GRID_INTERP: the signal the SS compares with the data (SumofSquares...m:49-61), MS2
+ *   already x A. There is no grid option.
+ * Data. The y1 / y2 (MS2 / PP7) of the cell as given to tci_create.
+ * Host, once per sample row, with the C library's sqrt and log:
+ *   sd_s = sqrt(s2_s);  lg_s = log(6.283185307179586 * s2_s);  logS = log((double)S), computed once.
+ * Scored points. A point (dye d, index j < N) is scored when its datum y is finite and every f_s, s in [0, S), is
+ *   finite. For a scored point, every operation rounded once, as written, never fused; exp, log and erfc are the
+ *   device library's (no fast-math variants):
+ *     r_s  = y - f_s;   z_s = r_s / sd_s;   ll_s = -0.5 * (lg_s + z_s * z_s)
+ *     m    = max_s ll_s
+ *     lppd = (m + log(SUM_s exp(ll_s - m))) - logS
+ *     lbar = (SUM_s ll_s) / S
+ *     p_waic = (SUM_s (ll_s - lbar)^2) / (S - 1)          NaN for S == 1 (0 / 0)
+ *     pit  = (SUM_s 0.5 * erfc(-z_s * 0.7071067811865476)) / S
+ *     resid = (SUM_s r_s) / S;   zbar = (SUM_s z_s) / S;   z2 = (SUM_s z_s * z_s) / S
+ *   Order of every SUM_s: the samples are taken in segments of 64 consecutive s (the boundaries follow from S alone);
+ *   inside a segment the terms are added in ascending s from 0.0; the segment partials are then added in ascending
+ *   order from 0.0. Nothing is special-cased: an overflowing z * z makes ll = -Inf and the formulas carry it.
+ * Unscored points and padding (j from N to ld_out): all six pointwise outputs are NaN.
+ * Per cell, computed on the host from the pointwise vectors; the points are visited in the order dye 0 ascending j,
+ *   then dye 1 ascending j, over scored points, sums from 0.0:
+ *     n_obs       the number of scored points
+ *     lppd        sum_i lppd_i;   p_waic = sum_i p_waic_i;   elpd_waic = lppd - p_waic (WAIC is -2 x this)
+ *     chi2        (sum_i z2_i) / n_obs: the reduced chi^2 (near 1 by construction when sigma2 is sampled)
+ *     coverage[l] #{i : lo_l <= pit_i <= hi_l} / n_obs, lo_l = (1 - level_l) / 2, hi_l = 1 - lo_l: the share of the
+ *                 data inside the central predictive interval of that level
+ *     dw[d]       per dye, (sum (zbar_j - zbar_{j-1})^2 over the pairs with j - 1 and j both scored) / (sum zbar_j^2
+ *                 over scored j): the Durbin-Watson statistic of the standardised residuals (2: uncorrelated; towards
+ *                 0: a systematic misfit)
+ *   n_obs == 0: every per-cell value is NaN and n_obs is 0.
+ * Bits. A cell's outputs depend on its samples in order, its data, S and the levels alone: not on n_sel, the cell's
+ * position, ld_theta, ld_out, scratch_bytes, the tile shape or how many workgroups ran.
+ * Error bound. resid, zbar and z2 use +, -, x and / in the stated order: a float64 restatement in that order gives
+ * the same bits. For the rest, against the formulas evaluated without rounding on the same f_s, sd_s and lg_s, with
+ * u = 2^-53, Z2 = max_s z_s^2, L = max_s |lg_s|, g = min(S, 64) + ceil(S / 64) (the terms one sum's value passes
+ * through), and the device functions within K_exp = 3, K_log = 3 and K_erfc = 16 ulp (1 ulp = 2 u):
+ *   E = u (4 Z2 + L)                                                            |ll_s - exact|
+ *   |lppd - exact|   <= 1.01 u (4 Z2 + L + 2 K_exp + g + (2 K_log + 4) log S + 2 |lppd|)
+ *   A = (L + Z2) / 2;   D = 2 E + (g + 3) u A                                   |(ll_s - lbar) - exact|
+ *   |p_waic - exact| <= 1.01 (2 D sqrt(S p_waic / (S - 1)) + S D^2 / (S - 1) + (g + 4) u p_waic)
+ *   |pit - exact|    <= 1.01 u (2 K_erfc + g + 4)
+ * The ROCm device-library documentation states no accuracy for these functions; K_exp, K_log and K_erfc are the
+ * limits of OpenCL's double-precision profile, which that library implements, and the largest deviation measured on
+ * the test inputs stays inside the bounds they give (DESIGN.md section 7h has the derivation and the measurement;
+ * tests/fitcheck_oracle.py restates the bound). */
+typedef struct {
+  int64_t scratch_bytes;  /* cap on the device scratch for simulated rows; 0 = default (1 GiB) */
+  int32_t n_levels;       /* 1 .. 8; default 2 */
+  double levels[8];       /* each strictly inside (0, 1); defaults {0.5, 0.95} */
+} tci_fitcheck_options;
+
+/* Host buffers (any pointer may be NULL). */
+typedef struct {
+  double *lppd_i, *p_waic_i, *pit, *resid, *zbar, *z2;  /* pointwise, each [n_sel][2][ld_out]: dye 0 = MS2, 1 = PP7 */
+  int32_t* n_obs;                                       /* [n_sel] */
+  double *lppd, *p_waic, *elpd_waic, *chi2;             /* [n_sel] */
+  double* coverage;                                     /* [n_sel][n_levels] */
+  double* dw;                                           /* [n_sel][2] */
+  double kernel_ms;   /* written: device time of the fit-check kernel (HIP events), summed over the chunks */
+  double forward_ms;  /* written: device time of the forward launches that fill the scratch */
+} tci_fitcheck_outputs;
+
+int tci_fitcheck_defaults(tci_fitcheck_options* opt);
+
+/* HOST pointers, synchronous. opt may be NULL (the defaults); out is required. 1 <= S <= 4096; ld_theta >= 7 + N and
+ * ld_out >= N of every selected cell (TCI_ERANGE). TCI_EINVAL, naming the index, for an s2 entry that is not finite
+ * and > 0 or a level that is not inside (0, 1); for n_levels outside [1, 8] or scratch_bytes < 0. The simulated rows
+ * (2 * n_sel * S * ld_out doubles) live in the scratch buffer the context owns; past opt->scratch_bytes whole cells
+ * are processed in chunks (the same bits), and TCI_EINVAL is returned when one cell alone does not fit. Every check
+ * comes before any device work. */
+int tci_fitcheck(tci_ctx* ctx, const tci_fitcheck_options* opt, const double* theta, int64_t ld_theta, const double* s2,
+                 const int32_t* cell_id, int64_t n_sel, int64_t S, int64_t ld_out, tci_fitcheck_outputs* out);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

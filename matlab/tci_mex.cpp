@@ -25,8 +25,15 @@
 //          (1 x n) -- column-major, the ABI's [n][S][P] with nothing transposed; probs: 1 to 16
 //          probabilities in [0, 1]. ms2q, pp7q: N_max x nq x n (N_max = the longest selected cell),
 //          the quantiles over the S simulated values at every acquisition time, NaN past a cell's N.
+//   [pt, cell] = tci_mex('fitcheck', h, cells, X, s2[, levels])
+//          posterior predictive fit checks reduced on the GPU (tci_fitcheck; formulas in include/tci.h): X is
+//          P x S x n as for 'predict', s2 is S x n (the sigma2 of the same chain rows, finite and > 0), levels: 1 to 8
+//          central-interval levels inside (0, 1) (default [0.5 0.95]). pt: struct with lppd, p_waic, pit, resid,
+//          zbar, z2, each N_max x 2 x n (column 1 = MS2, 2 = PP7; NaN at unscored points and past a cell's N).
+//          cell: struct with n_obs, lppd, p_waic, elpd_waic (WAIC = -2 x this), chi2 (1 x n), coverage
+//          (numel(levels) x n), dw (2 x n, per dye), levels, kernel_ms and forward_ms.
 //   tci_mex('destroy', h)
-//   n = tci_mex('device_count')                 HIP devices visible to this MATLAB process
+//   n = tci_mex('device_count')                HIP devices visible to this MATLAB process
 //   [results, chain, s2chain, R] = tci_mex('dram', h, cells, X0, LB, UB, MU, SIG, J0, sigma2[, options])
 //          mcmcrun (TranscriptionCycleMCMC.m:273) for every chain at once on the GPU (tci_dram_run):
 //          one chain per COLUMN. cells: 1 x n; X0 / LB / UB (params, :242-255), MU / SIG (Gaussian
@@ -313,6 +320,107 @@ void cmd_predict(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   plhs[0] = ms2;
   if (nlhs > 1) plhs[1] = pp7; else mxDestroyArray(pp7);
+}
+
+// ---- 'fitcheck': posterior predictive fit checks per cell ---------------------------------------
+
+void cmd_fitcheck(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 5 || nrhs > 6) mexErrMsgIdAndTxt("tci:arg", "[pt, cell] = tci_mex('fitcheck', h, cells, X, s2[, levels])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const size_t n = mxGetNumberOfElements(prhs[2]);
+  const double* c = doubles(prhs[2], -1, "cells");
+  if (n == 0) mexErrMsgIdAndTxt("tci:arg", "cells must name at least one cell");
+  const double* X = doubles(prhs[3], -1, "X");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[3]);
+  const mwSize* d = mxGetDimensions(prhs[3]);
+  const size_t P = d[0], S = nd > 1 ? d[1] : 1, nx = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || nx != n) mexErrMsgIdAndTxt("tci:arg", "X must be P x S x n: S samples per cell, n = numel(cells)");
+  if (P < 9) mexErrMsgIdAndTxt("tci:arg", "X must have at least 9 rows ([v, tau, ton, MS2_basal, PP7_basal, A, R, dR])");
+  if (S < 1 || S > 4096) mexErrMsgIdAndTxt("tci:arg", "X must hold 1 to 4096 samples per cell (its second dimension)");
+  const double* s2 = doubles(prhs[4], (long long)(S * n), "s2");
+  if (S * n > 1 && (mxGetNumberOfDimensions(prhs[4]) != 2 || mxGetM(prhs[4]) != S))
+    mexErrMsgIdAndTxt("tci:arg", "s2 must be S x n: one sigma2 per column of X");
+  for (size_t i = 0; i < S * n; ++i)
+    if (!(s2[i] > 0.0 && s2[i] <= 1.7976931348623157e308))
+      mexErrMsgIdAndTxt("tci:arg", "s2(%d) must be finite and > 0", (int)i + 1);
+  tci_fitcheck_options opt;
+  tci_fitcheck_defaults(&opt);
+  if (nrhs > 5) {
+    const size_t nl = mxGetNumberOfElements(prhs[5]);
+    const double* lv = doubles(prhs[5], -1, "levels");
+    if (nl < 1 || nl > 8) mexErrMsgIdAndTxt("tci:arg", "levels must have 1 to 8 elements");
+    opt.n_levels = (int32_t)nl;
+    for (size_t l = 0; l < nl; ++l) {
+      if (!(lv[l] > 0.0 && lv[l] < 1.0)) mexErrMsgIdAndTxt("tci:arg", "levels(%d) must be inside (0, 1)", (int)l + 1);
+      opt.levels[l] = lv[l];
+    }
+  }
+  std::vector<int32_t> cid(n);
+  for (size_t b = 0; b < n; ++b) {
+    if (!(c[b] >= 1 && c[b] <= 2147483647.0) || c[b] != (double)(int64_t)c[b])
+      mexErrMsgIdAndTxt("tci:arg", "cells(%d) must be a positive integer", (int)b + 1);
+    cid[b] = (int32_t)c[b] - 1;
+  }
+
+  tci_ctx* ctx = handle_of(prhs[1]);
+  int64_t nmax = 0;
+  for (size_t b = 0; b < n; ++b) {
+    int64_t nb = 0;
+    check(ctx, tci_cell_points(ctx, cid[b], &nb), "tci_cell_points");
+    nmax = std::max(nmax, nb);
+  }
+  static const char* pt_fields[] = {"lppd", "p_waic", "pit", "resid", "zbar", "z2"};
+  static const char* cell_fields[] = {"n_obs", "lppd", "p_waic", "elpd_waic", "chi2", "coverage", "dw", "levels",
+                                      "kernel_ms", "forward_ms"};
+  mxArray* pt = mxCreateStructMatrix(1, 1, 6, pt_fields);
+  mxArray* res = mxCreateStructMatrix(1, 1, 10, cell_fields);
+  const mwSize d3[3] = {(mwSize)nmax, 2, (mwSize)n};  // N_max x 2 x n == [cell][dye][N_max]
+  mxArray* a[6];
+  for (int q = 0; q < 6; ++q) {
+    a[q] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+    mxSetField(pt, 0, pt_fields[q], a[q]);
+  }
+  mxArray* v[4];
+  for (int q = 0; q < 4; ++q) {
+    v[q] = mxCreateDoubleMatrix(1, n, mxREAL);
+    mxSetField(res, 0, cell_fields[1 + q], v[q]);
+  }
+  mxArray* cov = mxCreateDoubleMatrix((size_t)opt.n_levels, n, mxREAL);  // n_levels x n == [cell][level]
+  mxArray* dw = mxCreateDoubleMatrix(2, n, mxREAL);
+  mxArray* lev = mxCreateDoubleMatrix(1, (size_t)opt.n_levels, mxREAL);
+  mxArray* nobs = mxCreateDoubleMatrix(1, n, mxREAL);
+  mxSetField(res, 0, "coverage", cov);
+  mxSetField(res, 0, "dw", dw);
+  mxSetField(res, 0, "levels", lev);
+  mxSetField(res, 0, "n_obs", nobs);
+  for (int32_t l = 0; l < opt.n_levels; ++l) mxGetPr(lev)[l] = opt.levels[l];
+  std::vector<int32_t> n_obs(n);
+  tci_fitcheck_outputs out;
+  memset(&out, 0, sizeof out);
+  out.lppd_i = mxGetPr(a[0]);
+  out.p_waic_i = mxGetPr(a[1]);
+  out.pit = mxGetPr(a[2]);
+  out.resid = mxGetPr(a[3]);
+  out.zbar = mxGetPr(a[4]);
+  out.z2 = mxGetPr(a[5]);
+  out.n_obs = n_obs.data();
+  out.lppd = mxGetPr(v[0]);
+  out.p_waic = mxGetPr(v[1]);
+  out.elpd_waic = mxGetPr(v[2]);
+  out.chi2 = mxGetPr(v[3]);
+  out.coverage = mxGetPr(cov);
+  out.dw = mxGetPr(dw);
+  const int rc = tci_fitcheck(ctx, &opt, X, (int64_t)P, s2, cid.data(), (int64_t)n, (int64_t)S, nmax, &out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(pt);
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_fitcheck");
+  }
+  for (size_t b = 0; b < n; ++b) mxGetPr(nobs)[b] = (double)n_obs[b];
+  mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+  mxSetField(res, 0, "forward_ms", mxCreateDoubleScalar(out.forward_ms));
+  plhs[0] = pt;
+  if (nlhs > 1) plhs[1] = res; else mxDestroyArray(res);
 }
 
 // ---- 'dram': the GPU-resident sampler -------------------------------------------------------
@@ -954,6 +1062,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "forward") cmd_forward(nlhs, plhs, nrhs, prhs);
   else if (cmd == "dram") cmd_dram(nlhs, plhs, nrhs, prhs);
   else if (cmd == "predict") cmd_predict(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "fitcheck") cmd_fitcheck(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainstats") cmd_chainstats(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chaincov") cmd_chaincov(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainquant") cmd_chainquant(nlhs, plhs, nrhs, prhs);

@@ -136,6 +136,16 @@ class tci_chainess_outputs(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class tci_fitcheck_options(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_int64), ("n_levels", C.c_int32), ("levels", C.c_double * 8)]
+
+
+class tci_fitcheck_outputs(C.Structure):
+    _fields_ = [("lppd_i", _dp), ("p_waic_i", _dp), ("pit", _dp), ("resid", _dp), ("zbar", _dp), ("z2", _dp),
+                ("n_obs", _i32p), ("lppd", _dp), ("p_waic", _dp), ("elpd_waic", _dp), ("chi2", _dp), ("coverage", _dp),
+                ("dw", _dp), ("kernel_ms", C.c_double), ("forward_ms", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -195,6 +205,9 @@ SIGNATURES = [
                                    C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
                                    C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                    C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs)]),
+    ("tci_fitcheck_defaults", C.c_int, [C.POINTER(tci_fitcheck_options)]),
+    ("tci_fitcheck", C.c_int, [C.c_void_p, C.POINTER(tci_fitcheck_options), _dp, C.c_int64, _dp, _i32p, C.c_int64,
+                               C.c_int64, C.c_int64, C.POINTER(tci_fitcheck_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -613,6 +613,185 @@ int tci_predict(tci_ctx* ctx, const tci_predict_options* opt, const double* thet
   return TCI_OK;
 }
 
+int tci_fitcheck_defaults(tci_fitcheck_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  o->scratch_bytes = 0;
+  o->n_levels = 2;
+  o->levels[0] = 0.5;
+  o->levels[1] = 0.95;
+  return TCI_OK;
+}
+
+namespace {
+
+// The per-cell values of one cell from its pointwise vectors pt = [2][6][ld_out] (include/tci.h: dye 0 ascending j,
+// then dye 1, over scored points; an unscored point is NaN in all six).
+void fitcheck_cell(const double* pt, int64_t ld_out, const tci_fitcheck_options& o, int64_t k, tci_fitcheck_outputs* out) {
+  const double nan = std::nan("");
+  int32_t n_obs = 0;
+  int32_t inside[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double lppd = 0.0, pw = 0.0, z2 = 0.0, dw[2];
+  for (int d = 0; d < 2; ++d) {
+    const double* v = pt + (size_t)d * 6 * (size_t)ld_out;
+    const double *v_lppd = v, *v_pw = v + ld_out, *v_pit = v + 2 * ld_out, *v_zbar = v + 4 * ld_out, *v_z2 = v + 5 * ld_out;
+    double num = 0.0, den = 0.0;
+    bool prev = false;
+    for (int64_t j = 0; j < ld_out; ++j) {
+      const bool scored = !std::isnan(v_pit[j]);  // pit of a scored point is a sum of values in [0, 1]
+      if (scored) {
+        ++n_obs;
+        lppd = lppd + v_lppd[j];
+        pw = pw + v_pw[j];
+        z2 = z2 + v_z2[j];
+        for (int32_t l = 0; l < o.n_levels; ++l) {
+          const double lo = (1.0 - o.levels[l]) / 2.0, hi = 1.0 - lo;
+          if (lo <= v_pit[j] && v_pit[j] <= hi) ++inside[l];
+        }
+        if (prev) {
+          const double dz = v_zbar[j] - v_zbar[j - 1];
+          num = num + dz * dz;
+        }
+        den = den + v_zbar[j] * v_zbar[j];
+      }
+      prev = scored;
+    }
+    dw[d] = num / den;
+  }
+  const bool any = n_obs > 0;
+  if (out->n_obs) out->n_obs[k] = n_obs;
+  if (out->lppd) out->lppd[k] = any ? lppd : nan;
+  if (out->p_waic) out->p_waic[k] = any ? pw : nan;
+  if (out->elpd_waic) out->elpd_waic[k] = any ? lppd - pw : nan;
+  if (out->chi2) out->chi2[k] = any ? z2 / (double)n_obs : nan;
+  if (out->coverage)
+    for (int32_t l = 0; l < o.n_levels; ++l)
+      out->coverage[(size_t)k * (size_t)o.n_levels + l] = any ? (double)inside[l] / (double)n_obs : nan;
+  if (out->dw)
+    for (int d = 0; d < 2; ++d) out->dw[2 * k + d] = any ? dw[d] : nan;
+}
+
+}  // namespace
+
+int tci_fitcheck(tci_ctx* ctx, const tci_fitcheck_options* opt, const double* theta, int64_t ld_theta, const double* s2,
+                 const int32_t* cell_id, int64_t n_sel, int64_t S, int64_t ld_out, tci_fitcheck_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  tci_fitcheck_options o;
+  tci_fitcheck_defaults(&o);
+  if (opt) o = *opt;
+  // ---- every check comes before any device work
+  if (!out) return fail(ctx, TCI_EINVAL, "tci_fitcheck: out is NULL");
+  if (o.scratch_bytes < 0) return fail(ctx, TCI_EINVAL, "tci_fitcheck: scratch_bytes must be >= 0");
+  if (o.n_levels < 1 || o.n_levels > 8)
+    return fail(ctx, TCI_EINVAL, "tci_fitcheck: n_levels=" + std::to_string(o.n_levels) + " must be in [1, 8]");
+  for (int32_t l = 0; l < o.n_levels; ++l)
+    if (!(o.levels[l] > 0.0 && o.levels[l] < 1.0))
+      return fail(ctx, TCI_EINVAL, "tci_fitcheck: levels[" + std::to_string(l) + "] must be strictly inside (0, 1)");
+  if (S < 1 || S > 4096) return fail(ctx, TCI_EINVAL, "tci_fitcheck: S=" + std::to_string(S) + " must be in [1, 4096]");
+  if (n_sel < 0 || (n_sel > 0 && (!theta || !s2 || !cell_id)))
+    return fail(ctx, TCI_EINVAL, "tci_fitcheck: null pointer or negative n_sel");
+  out->kernel_ms = 0.0;
+  out->forward_ms = 0.0;
+  if (n_sel == 0) return TCI_OK;
+  int rc = check_rows(ctx, ld_theta, cell_id, n_sel);
+  if (rc != TCI_OK) return rc;
+  for (int64_t k = 0; k < n_sel; ++k)
+    if (ld_out < ctx->meta[(size_t)cell_id[k]].n) return fail(ctx, TCI_ERANGE, "tci_fitcheck: ld_out shorter than a cell");
+  if (ld_theta > ((int64_t)1 << 24) || ld_out > ((int64_t)1 << 24))
+    return fail(ctx, TCI_ERANGE, "tci_fitcheck: ld_theta / ld_out above 2^24");
+  if (n_sel > ((int64_t)1 << 40) / S) return fail(ctx, TCI_ERANGE, "tci_fitcheck: n_sel x S above 2^40");
+  for (int64_t i = 0; i < n_sel * S; ++i)
+    if (!(std::isfinite(s2[i]) && s2[i] > 0.0))
+      return fail(ctx, TCI_EINVAL, "tci_fitcheck: s2[" + std::to_string(i) + "] must be finite and > 0");
+  const int64_t cap = o.scratch_bytes > 0 ? o.scratch_bytes : (int64_t)1 << 30;
+  const int64_t per_cell = 2 * S * ld_out * (int64_t)sizeof(double);  // <= 2^41
+  if (per_cell > cap)
+    return fail(ctx, TCI_EINVAL, "tci_fitcheck: one cell needs " + std::to_string(per_cell) +
+                                     " bytes of scratch (2 x S x ld_out doubles), scratch_bytes allows " +
+                                     std::to_string(cap));
+  int64_t chunk = 0;
+  if (tci::fitcheck_max_cells(S, ld_out, &chunk) != TCI_OK)
+    return fail(ctx, TCI_EINVAL, "tci_fitcheck: S x ld_out too large for one launch");
+  chunk = std::min(std::min(chunk, cap / per_cell), n_sel);  // whole cells per chunk, at least one
+  const size_t rows_max = (size_t)(chunk * S), cell_out = (size_t)12 * (size_t)ld_out;
+  std::vector<int32_t> row_cell;
+  std::vector<double> sdlg, pt;
+  try {
+    row_cell.resize(rows_max);
+    sdlg.resize(2 * rows_max);
+    pt.resize((size_t)chunk * cell_out);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, "tci_fitcheck: host allocation failed");
+  }
+  const double logS = std::log((double)S);
+
+  // ---- device work: per chunk, the forward launch into the scratch, then the reduction over the samples
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = ensure(ctx, &ctx->d_theta, &ctx->cap_theta, rows_max * (size_t)ld_theta)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_cell, &ctx->cap_cell, rows_max)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_sim, &ctx->cap_sim, 2 * rows_max * (size_t)ld_out)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_out0, &ctx->cap_out0, (size_t)chunk * cell_out)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_out1, &ctx->cap_out1, 2 * rows_max)) != TCI_OK) return rc;
+  hipStream_t st = ctx->stream;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventCreate(&e2) != hipSuccess) {
+    const hipError_t e = hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return hip_fail(ctx, e, "tci_fitcheck: hipEventCreate");
+  }
+  auto body = [&]() -> int {
+    for (int64_t k0 = 0; k0 < n_sel; k0 += chunk) {
+      const int64_t nc = std::min(chunk, n_sel - k0), B = nc * S;
+      for (int64_t k = 0; k < nc; ++k) std::fill_n(row_cell.begin() + k * S, S, cell_id[k0 + k]);
+      for (int64_t i = 0; i < B; ++i) {
+        const double v = s2[k0 * S + i];
+        sdlg[(size_t)i] = std::sqrt(v);
+        sdlg[(size_t)(B + i)] = std::log(6.283185307179586 * v);
+      }
+      double* sim0 = ctx->d_sim;
+      double* sim1 = ctx->d_sim + (size_t)B * (size_t)ld_out;
+      double* d_sd = ctx->d_out1;
+      double* d_lg = ctx->d_out1 + B;
+      TCI_HIP(ctx, hipMemcpyAsync(ctx->d_theta, theta + (size_t)k0 * (size_t)S * (size_t)ld_theta,
+                                  (size_t)B * (size_t)ld_theta * sizeof(double), hipMemcpyHostToDevice, st));
+      TCI_HIP(ctx, hipMemcpyAsync(ctx->d_cell, row_cell.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      TCI_HIP(ctx, hipMemcpyAsync(d_sd, sdlg.data(), 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+      TCI_HIP(ctx, hipEventRecord(e0, st));
+      int r = run(ctx, tci::MODE_FWD_INTERP, ctx->d_theta, ld_theta, ctx->d_cell, nullptr, B, sim0, sim1, ld_out, (void*)st);
+      if (r != TCI_OK) return r;
+      TCI_HIP(ctx, hipEventRecord(e1, st));
+      r = tci::launch_fitcheck(ctx->kp, ctx->d_cell, sim0, sim1, d_sd, d_lg, nc, S, ld_out, logS, ctx->d_out0, (void*)st);
+      if (r == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "tci_fitcheck: kernel launch");
+      if (r != TCI_OK) return fail(ctx, r, "tci_fitcheck: the kernel does not fit a CU's LDS or the grid");
+      TCI_HIP(ctx, hipEventRecord(e2, st));
+      TCI_HIP(ctx, hipMemcpyAsync(pt.data(), ctx->d_out0, (size_t)nc * cell_out * sizeof(double), hipMemcpyDeviceToHost, st));
+      TCI_HIP(ctx, hipStreamSynchronize(st));  // the host vectors and the staging buffers are reused by the next chunk
+      float ms = 0.f;
+      TCI_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+      out->forward_ms += (double)ms;
+      TCI_HIP(ctx, hipEventElapsedTime(&ms, e1, e2));
+      out->kernel_ms += (double)ms;
+      for (int64_t k = 0; k < nc; ++k) {
+        const double* p = pt.data() + (size_t)k * cell_out;
+        double* const dst[6] = {out->lppd_i, out->p_waic_i, out->pit, out->resid, out->zbar, out->z2};
+        for (int q = 0; q < 6; ++q)
+          if (dst[q])
+            for (int d = 0; d < 2; ++d)
+              std::memcpy(dst[q] + ((size_t)(k0 + k) * 2 + d) * (size_t)ld_out, p + ((size_t)d * 6 + q) * (size_t)ld_out,
+                          (size_t)ld_out * sizeof(double));
+        fitcheck_cell(p, ld_out, o, k0 + k, out);
+      }
+    }
+    return TCI_OK;
+  };
+  rc = body();
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipEventDestroy(e2);
+  return rc;
+}
+
 int tci_device_count(int* n_out) {
   if (!n_out) return TCI_EINVAL;
   int n = 0;

@@ -91,6 +91,16 @@ int launch_quantile(const KParams& kp, const int32_t* row_cell, const double* si
 // The most selected cells one forward + quantile launch pair takes (grid limits).
 int quantile_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
 
+// Fit checks over samples (tci_fitcheck.hip, k_fitcheck). sim0/sim1 and row_cell as for launch_quantile; sd, lg
+// (device): [n_sel * S], sqrt(s2) and log(2 pi s2) of every row; logS = log((double)S). out (device):
+// [n_sel][2][6][ld_out] = per dye lppd, p_waic, pit, resid, zbar, z2; unscored points and entries past a cell's N are
+// NaN. The data are kp.points. TCI_EINVAL when the launch would not fit (grid or LDS), TCI_EHIP on a HIP error.
+int launch_fitcheck(const KParams& kp, const int32_t* row_cell, const double* sim0, const double* sim1,
+                    const double* sd, const double* lg, int64_t n_sel, int64_t S, int64_t ld_out, double logS,
+                    double* out, void* stream);
+// The most selected cells one forward + fitcheck launch pair takes (grid limits).
+int fitcheck_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
+
 // Chain diagnostics (tci_chainstats.hip) of a device chain [n_rows][n_chains][ld] and, when s2 is not null,
 // of s2 [n_rows][n_chains] as column ld of every chain. npar (device, may be null = ld): columns j >= npar[c]
 // are padding. stats (device): [5][n_chains * (ld + 1)] doubles = mcerr, tau, Geweke z, Geweke p and the

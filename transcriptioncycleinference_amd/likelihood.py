@@ -280,6 +280,62 @@ class ChainEss:
                                          I(self.s2_window_split), 0, 0.0)
 
 
+FITCHECK_POINTWISE = ("lppd_i", "p_waic_i", "pit", "resid", "zbar", "z2")
+
+
+def fitcheck_levels(levels) -> np.ndarray:
+    """``levels`` as the float64 vector ``tci_fitcheck_options`` takes; ValueError outside its rules."""
+    lv = np.ascontiguousarray(np.atleast_1d(levels), np.float64)
+    if lv.ndim != 1 or not 1 <= len(lv) <= 8:
+        raise ValueError("levels must hold 1 to 8 interval levels")
+    if not np.all((lv > 0) & (lv < 1)):
+        raise ValueError("levels must be strictly inside (0, 1)")
+    return lv
+
+
+@dataclasses.dataclass
+class FitCheck:
+    """Posterior predictive fit checks (``tci_fitcheck_outputs``; formulas in ``include/tci.h``). Pointwise, each
+    ``[n_sel, 2, ld_out]`` with dye 0 = MS2 and 1 = PP7, NaN at unscored points and past a cell's N: ``lppd_i``,
+    ``p_waic_i``, ``pit``, ``resid``, ``zbar``, ``z2``. Per cell ``[n_sel]``: ``n_obs`` (int32), ``lppd``, ``p_waic``,
+    ``elpd_waic`` (WAIC = -2 x this), ``chi2``; ``coverage`` ``[n_sel, n_levels]`` at ``levels``; ``dw`` ``[n_sel, 2]``."""
+
+    lppd_i: np.ndarray
+    p_waic_i: np.ndarray
+    pit: np.ndarray
+    resid: np.ndarray
+    zbar: np.ndarray
+    z2: np.ndarray
+    n_obs: np.ndarray
+    lppd: np.ndarray
+    p_waic: np.ndarray
+    elpd_waic: np.ndarray
+    chi2: np.ndarray
+    coverage: np.ndarray
+    dw: np.ndarray
+    levels: np.ndarray
+    n_samples: int = 0
+    kernel_ms: float = 0.0    # device time of the fit-check kernel
+    forward_ms: float = 0.0   # device time of the forward launches before it
+
+    @classmethod
+    def empty(cls, n: int, ld_out: int, levels=(0.5, 0.95), n_samples: int = 0) -> "FitCheck":
+        lv = fitcheck_levels(levels)
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        return cls(*[d(n, 2, ld_out) for _ in FITCHECK_POINTWISE], np.zeros(n, np.int32), d(n), d(n), d(n), d(n),
+                   d(n, len(lv)), d(n, 2), lv, int(n_samples))
+
+    def options(self, scratch_bytes: int = 0) -> "_lib.tci_fitcheck_options":
+        lv = (C.c_double * 8)(*self.levels)
+        return _lib.tci_fitcheck_options(int(scratch_bytes), len(self.levels), lv)
+
+    def to_c(self) -> "_lib.tci_fitcheck_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        return _lib.tci_fitcheck_outputs(*[P(getattr(self, f)) for f in FITCHECK_POINTWISE],
+                                         _lib.ptr(self.n_obs, _lib._i32p), P(self.lppd), P(self.p_waic),
+                                         P(self.elpd_waic), P(self.chi2), P(self.coverage), P(self.dw), 0.0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -416,6 +472,41 @@ class Likelihood:
                                           _lib.ptr(cid, _lib._i32p), n_sel, S, _lib.ptr(pr, _lib._dp), nq,
                                           _lib.ptr(ms2, _lib._dp), _lib.ptr(pp7, _lib._dp), ld_out))
         return ms2, pp7
+
+    def fitcheck(self, theta: np.ndarray, s2: np.ndarray, cell_id: Sequence[int], levels=(0.5, 0.95),
+                 scratch_bytes: int = 0) -> FitCheck:
+        """Posterior predictive fit checks reduced on the device (``tci_fitcheck``; formulas in
+        ``include/tci.h``): ``theta`` is ``[n_sel, S, ld]``, S posterior samples of cell ``cell_id[k]`` each, and
+        ``s2`` ``[n_sel, S]`` the sigma2 of the same chain rows (finite and > 0). Every datum of the cell is scored
+        under the Gaussian mixture the samples define, with the forward model through the uniform grid + interp1 as
+        inside the SS. Returns a :class:`FitCheck`; ``levels``: 1 to 8 central-interval levels inside (0, 1) for
+        ``coverage``; ``scratch_bytes`` as in :meth:`predict`."""
+        theta = np.ascontiguousarray(theta, np.float64)
+        if theta.ndim != 3:
+            raise ValueError("theta must be [n_sel, S, ld]: S posterior samples per selected cell")
+        cid = np.ascontiguousarray(cell_id, np.int32)
+        n_sel, S, ld = theta.shape
+        if cid.shape != (n_sel,):
+            raise ValueError("cell_id must have one entry per selected cell (theta.shape[0])")
+        s2 = np.ascontiguousarray(s2, np.float64)
+        if s2.shape != (n_sel, S):
+            raise ValueError("s2 must be [n_sel, S]: one sigma2 per theta row")
+        if not np.all(np.isfinite(s2) & (s2 > 0)):
+            raise ValueError("s2 must be finite and > 0")
+        lv = fitcheck_levels(levels)
+        if not 1 <= S <= 4096:
+            raise ValueError(f"S = theta.shape[1] = {S} must be in [1, 4096]")
+        if int(scratch_bytes) < 0:
+            raise ValueError("scratch_bytes must be >= 0")
+        if n_sel and (cid.min() < 0 or cid.max() >= len(self.lengths)):
+            raise ValueError("cell_id out of range")
+        ld_out = int(self.lengths[cid].max()) if n_sel else 1
+        fc = FitCheck.empty(n_sel, ld_out, lv, S)
+        opt, out = fc.options(scratch_bytes), fc.to_c()
+        self._check(self._lib.tci_fitcheck(self._h, C.byref(opt), _lib.ptr(theta, _lib._dp), ld, _lib.ptr(s2, _lib._dp),
+                                           _lib.ptr(cid, _lib._i32p), n_sel, S, ld_out, C.byref(out)))
+        fc.kernel_ms, fc.forward_ms = float(out.kernel_ms), float(out.forward_ms)
+        return fc
 
     def chainstats(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, max_lag: int = 0):
         """Convergence diagnostics of a chain held on the host (mcmcstat's ``chainstats``), reduced

@@ -28,7 +28,8 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import ChainCov, ChainDens, ChainEss, ChainQuant, ChainRhat, ChainStats, rhat_groups
+from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainQuant, ChainRhat, ChainStats, FitCheck,
+                         rhat_groups)
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -59,6 +60,11 @@ RHAT_FIELDS = ("rhat", "rhat_split", "pooled_mean", "pooled_std", "mean_rep", "a
 # [P + 1] int32; ess_min: the smallest classic or split ess of the cell; max_lag: the cap the fit passed (0 = none)
 ESS_FIELDS = ("ess", "ess_split", "tau", "tau_split", "mcse", "window", "window_split", "ess_min", "max_lag", "n_rows",
               "n_chains", "cell_index")
+# MCMCcheck (fitcheck(lk, fit_result)): posterior predictive fit checks per fitted cell (include/tci.h): the pointwise
+# vectors [2, N] (row 0 = MS2, row 1 = PP7; NaN where a point is not scored), the per-cell scalars, coverage [n_levels]
+# at levels, dw [2] per dye
+CHECK_FIELDS = FITCHECK_POINTWISE + ("n_obs", "lppd", "p_waic", "elpd_waic", "waic", "chi2", "coverage", "dw", "levels",
+                                     "n_samples", "cell_index")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -295,6 +301,7 @@ class FitResult:
     gather_bytes: int = 0                      # parallel.fit_sharded: bytes every rank receives in it
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
+    MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
     MCMCess: Optional[List[Dict]] = None       # fit(..., replicates=M, ess=True): ESS_FIELDS per fitted cell
     MCMCrhat: Optional[List[Dict]] = None      # fit(..., replicates=M): RHAT_FIELDS per fitted cell
     MCMCdens: Optional[List[Dict]] = None      # fit(..., density=True): DENS_FIELDS per fitted cell
@@ -701,6 +708,69 @@ def predict(lk, fit_result: FitResult, nsample: int = 500, probs=(0.025, 0.5, 0.
 
 
 # ---------------------------------------------------------------------------
+# Posterior predictive fit checks (WAIC, PIT, coverage, reduced chi^2, Durbin-Watson)
+# ---------------------------------------------------------------------------
+
+
+def check_entry(fc: FitCheck, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCcheck`` entry (``CHECK_FIELDS``) from selected cell ``k`` of ``fc``, a cell of ``n`` points: the
+    pointwise vectors trimmed to ``[2, n]``, the per-cell scalars, ``waic = -2 elpd_waic``."""
+    d = {f: getattr(fc, f)[k, :, :n].copy() for f in FITCHECK_POINTWISE}
+    d["n_obs"] = int(fc.n_obs[k])
+    for f in ("lppd", "p_waic", "elpd_waic", "chi2"):
+        d[f] = float(getattr(fc, f)[k])
+    d["waic"] = -2.0 * d["elpd_waic"]
+    d["coverage"] = fc.coverage[k].copy()
+    d["dw"] = fc.dw[k].copy()
+    d["levels"] = fc.levels.copy()
+    d["n_samples"] = int(fc.n_samples)
+    d["cell_index"] = int(cell_index)
+    return {f: d[f] for f in CHECK_FIELDS}
+
+
+def fitcheck(lk, fit_result: FitResult, nsample: int = 500, levels=(0.5, 0.95), cell_offset: int = 0,
+             scratch_bytes: int = 0) -> FitResult:
+    """Posterior predictive fit checks of every fitted cell on the device (``Likelihood.fitcheck``; formulas in
+    ``include/tci.h``): each datum is scored under the Gaussian mixture that ``nsample`` posterior samples
+    (theta, sigma2) of the cell's chain define. Sets ``fit_result.MCMCcheck`` (``CHECK_FIELDS`` per fitted cell) and
+    returns ``fit_result``.
+
+    The samples are the rows :func:`predict` takes (:func:`predict_rows` of the post-burn-in rows kept in
+    ``MCMCchain``; fit with ``thin > 0``). ``s2chain`` is stored unsliced by ``n_burn``, so a row's sigma2 is read
+    from the last ``len(v_chain)`` entries of the cell's ``s2chain``: the entries of the same kept rows.
+    ``nsample`` is at most 4096. ``cell_offset``: as in :func:`fit`."""
+    if not fit_result.MCMCchain or any(not c or np.size(c.get("v_chain", ())) == 0 for c in fit_result.MCMCchain):
+        raise ValueError("fitcheck needs the fit's chain rows and this fit kept none: run fit(..., thin=k) with "
+                         "k > 0 and n_burn <= n_steps")
+    cl: Cells = lk.cells
+    groups: Dict[int, List[int]] = {}
+    thetas, s2s = [], []
+    for k, ch in enumerate(fit_result.MCMCchain):
+        c = int(fit_result.cell_index[k]) - int(cell_offset)
+        n = int(cl.lengths[c])
+        rows = int(np.size(ch["v_chain"]))
+        s2c = np.asarray(ch["s2chain"], np.float64).reshape(-1)
+        if len(s2c) < rows:
+            raise ValueError(f"fitted cell {k}: s2chain has {len(s2c)} entries for {rows} chain rows")
+        idx = predict_rows(rows, nsample)
+        thetas.append(chain_theta(ch, n, idx))
+        s2s.append(s2c[len(s2c) - rows:][idx])
+        groups.setdefault(len(idx), []).append(k)
+    entries: List[Optional[Dict]] = [None] * len(thetas)
+    for S, ks in groups.items():   # one device call per distinct sample count (a fit has one)
+        ld = max(thetas[k].shape[1] for k in ks)
+        theta = np.zeros((len(ks), S, ld))
+        for i, k in enumerate(ks):
+            theta[i, :, :thetas[k].shape[1]] = thetas[k]
+        cid = np.array([int(fit_result.cell_index[k]) - int(cell_offset) for k in ks], np.int32)
+        fc = lk.fitcheck(theta, np.stack([s2s[k] for k in ks]), cid, levels=levels, scratch_bytes=scratch_bytes)
+        for i, k in enumerate(ks):
+            entries[k] = check_entry(fc, i, thetas[k].shape[1] - 7, int(fit_result.cell_index[k]) + 1)
+    fit_result.MCMCcheck = entries
+    return fit_result
+
+
+# ---------------------------------------------------------------------------
 # Result files (TranscriptionCycleMCMC.m:371-378)
 # ---------------------------------------------------------------------------
 
@@ -741,6 +811,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCess"] = _struct_array(fit_result.MCMCess, ESS_FIELDS)
     if fit_result.MCMCdens is not None:  # only a fit with density=True
         variables["MCMCdens"] = _struct_array(fit_result.MCMCdens, DENS_FIELDS)
+    if fit_result.MCMCcheck is not None:  # only after fitcheck()
+        variables["MCMCcheck"] = _struct_array(fit_result.MCMCcheck, CHECK_FIELDS)
     sio.savemat(base + ".mat", variables)
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))
