@@ -718,6 +718,95 @@ int tci_fitcheck_defaults(tci_fitcheck_options* opt);
 int tci_fitcheck(tci_ctx* ctx, const tci_fitcheck_options* opt, const double* theta, int64_t ld_theta, const double* s2,
                  const int32_t* cell_id, int64_t n_sel, int64_t S, int64_t ld_out, tci_fitcheck_outputs* out);
 
+/* ---- Log-posterior trace, best sample and DIC of every chain (mcmcstat's sschain, mcmcrun's fourth output) ----
+ * mcmcrun returns [results, chain, s2chain, sschain]; the sampler here keeps no SS. The kept rows are re-evaluated
+ * instead: the engines are bitwise identical to the batched likelihood kernel, so the recomputed SS is the SS the
+ * sampler saw. Everything is per chain c over its n = n_rows rows; P = 7 + N is the parameter count of cell
+ * cell_id[c] and nobs = 2 N the sampler's observation count, NaNs included (the count the sigma2 update uses). All in
+ * FP64, every operation rounded once as written, never fused; log is the device library's (no fast-math variant).
+ * Per row t:
+ *   ss_t   the batched likelihood kernel's SS of chain[t][c][0..P): the bits of tci_ss_batch_async on that row;
+ *          mcmcstat's sschain.
+ *   pri_t  SUM_{j < P} ((theta_tj - mu_j) / sig_j)^2: a subtraction, a division and a multiplication per term. Order:
+ *          64 partial sums; partial l adds the terms j = l, l + 64, .. in ascending j from 0.0; the partials are then
+ *          added in ascending l from 0.0. A term with sig_j = +Inf is exactly 0 and is not special-cased. Entries
+ *          j >= P (of the row, of mu and of sig) are never read.
+ *   dev_t  ss_t / s2_t + nobs * log(6.283185307179586 * s2_t): -2 log likelihood at (theta_t, sigma2_t).
+ *   lp_t   -0.5 * (dev_t + pri_t): the log of likelihood x theta-prior at the sampled point, up to a constant.
+ * Nothing is special-cased: a non-finite theta gives the kernel's NaN, s2_t <= 0 what the formulas give, and the
+ * traces carry it.
+ * Per chain, from the four traces. Every sum over rows runs in segments of 256 consecutive rows (the boundaries
+ * follow from n alone, as in tci_chainrhat); inside a segment the terms are added in ascending t from 0.0, the
+ * segment sums are then added in ascending order from 0.0:
+ *   ss_min     the least ss_t;   ss_mean = (SUM ss_t) / n
+ *   dev_mean   (SUM dev_t) / n
+ *   dev_var    (SUM (dev_t - dev_mean)^2) / (n - 1); NaN for n = 1 (0 / 0)
+ *   best_row   the least t whose lp_t equals the largest lp_t of the chain, compared on the device's own values;
+ *              0-based among the n reduced rows
+ *   lp_best, ss_best, s2_best   the values of that row;   theta_best[0..P) that chain row's bits
+ *   theta_mean[j]   exactly tci_chaincov's mean (Neumaier sum, constant-column rule; the same bits);
+ *   s2_mean    the same rule on the s2 column
+ *   ss_hat     the likelihood kernel's SS of theta_mean
+ *   d_hat      ss_hat / s2_mean + nobs * log(6.283185307179586 * s2_mean)
+ *   p_d = dev_mean - d_hat;   p_v = 0.5 * dev_var;   dic = dev_mean + p_d
+ * A non-finite ss_t, pri_t or dev_t anywhere in a chain: every reduced output of that chain is NaN (theta_mean,
+ * s2_mean and ss_hat included), best_row is -1 and theta_best is NaN; the traces keep what the formulas gave.
+ * Padding of theta_best and theta_mean (j >= P) is NaN.
+ * Bits. An output depends on the chain's rows in order, its s2, the cell, mu, sig and n alone: not on n_chains, the
+ * chain's position, ld or how many workgroups ran.
+ * Error bound. ss, pri, best_row, theta_best, theta_mean and ss_hat are exact: a float64 restatement in the stated
+ * order gives the same bits, and so does it for every reduced value when applied to the returned traces. dev, lp
+ * and d_hat go through log. With u = 2^-53, the device log within K_log = 3 ulp (1 ulp = 2 u; the figure of
+ * tci_fitcheck), L = log(6.283185307179586 * s2) and the formulas evaluated without rounding on the same ss, s2, pri:
+ *   |dev - exact|   <= E_dev = 1.01 u (|ss / s2| + nobs (1 + (2 K_log + 1) |L|) + |dev|)
+ *   |lp - exact|    <= 0.5 E_dev + 1.01 u |lp|
+ *   |d_hat - exact| <= E_dev at (ss_hat, s2_mean)
+ * (DESIGN.md section 7i has the derivation; tests/chainlp_oracle.py restates the bound). */
+typedef struct {
+  int64_t flags;  /* reserved, must be 0 */
+} tci_chainlp_options;
+
+/* Host buffers (any pointer may be NULL). */
+typedef struct {
+  double *ss, *pri, *dev, *lp;                           /* traces, each [n_rows][n_chains] */
+  double *ss_min, *ss_mean, *dev_mean, *dev_var;         /* [n_chains] */
+  double *lp_best, *ss_best, *s2_best;                   /* [n_chains] */
+  double *s2_mean, *ss_hat, *d_hat, *p_d, *p_v, *dic;    /* [n_chains] */
+  int64_t* best_row;                                     /* [n_chains]; -1: a non-finite trace value */
+  double *theta_best, *theta_mean;                       /* [n_chains][ld] */
+  int64_t n_rows;    /* written: rows the reduction used */
+  double kernel_ms;  /* written: device time of the kernels (HIP events), the two likelihood launches included */
+} tci_chainlp_outputs;
+
+int tci_chainlp_defaults(tci_chainlp_options* opt);
+
+/* The reduction of a chain already on the host (e.g. read back from a _RawChain file): chain is
+ * [n_rows][n_chains][ld], s2chain [n_rows][n_chains] (required), cell_id [n_chains], prior_mu and prior_sig
+ * [n_chains][ld] as for tci_dram_run. opt may be NULL (the defaults). Checked in this order, all before any device
+ * work: TCI_EINVAL for a null argument, n_rows < 1, n_chains < 1 or flags != 0; TCI_ERANGE for a cell id out of
+ * range, ld < 7 + N of a chain's cell or n_rows * n_chains at or above 2^31; TCI_EINVAL, naming the chain and the
+ * index, for a prior_mu entry with j < P that is not finite or a prior_sig entry with j < P that is NaN or <= 0;
+ * TCI_ENOMEM when the chain does not fit the device. */
+int tci_chainlp(tci_ctx* ctx, const tci_chainlp_options* opt, const double* chain, const double* s2chain,
+                int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* cell_id, const double* prior_mu,
+                const double* prior_sig, tci_chainlp_outputs* out);
+
+/* tci_dram_run_ess plus tci_chainlp's outputs of the same rows (the kept rows whose 1-based chain row is >=
+ * stats_from), taken from the device chain before any copy, with the priors and cell ids the run already has on the
+ * device. lout is required; lopt may be NULL. red may be NULL (no per-chain reduction). group == NULL: no group
+ * reduction (n_groups, ropt, rout, eopt and eout are ignored); else group, n_groups, ropt, rout, eopt and eout as in
+ * tci_dram_run_ess, where either of rout and eout may be NULL but not both. tci_dram_reductions keeps its eight
+ * fields: a caller-allocated struct cannot grow without breaking the callers built against it, so this reduction is
+ * asked for here, as the group reductions are. TCI_EINVAL when opt->thin == 0 or no kept row is in the range, for
+ * lopt->flags != 0 and for a prior tci_chainlp refuses. Every engine gives the same chain bits, hence the same bits
+ * here. */
+int tci_dram_run_lp(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                    const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                    const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                    tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                    const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                    tci_chainess_outputs* eout, const tci_chainlp_options* lopt, tci_chainlp_outputs* lout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -34,6 +34,12 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag] = tci_fit(data, varargin)
 %        chainstats columns reduced on the device from the rows MCMCchain keeps -- mcerr_*, tau_* and
 %        geweke_p_* for v, ton, A, tau, MS2_basal, PP7_basal, R, dR (vectors) and s2, n_rows,
 %        ess_min = n_rows / max tau and cell_index; formulas in include/tci.h. Needs 'thin' > 0.)
+%     'logpost' (0; 1 fills the fifth output MCMClp, one entry per fitted cell: the sum-of-squares trace ss
+%        (mcmcstat's sschain, mcmcrun's fourth output) and the log-posterior trace lp of the rows MCMCchain
+%        keeps, ss_min, ss_mean, dev_mean, dev_var, the best sample (best_row, 1-based among those rows, lp_best,
+%        ss_best, s2_best and best_v, best_ton, .. best_dR), s2_mean, ss_hat, d_hat, p_d, p_v, dic, n_rows and
+%        cell_index, all on the device (tci_mex('dram') options.logpost; formulas in include/tci.h). Needs
+%        'thin' > 0.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -61,6 +67,7 @@ p.addParameter('engine', 'auto');
 p.addParameter('adapt_pmax', 0);
 p.addParameter('predict', 0);
 p.addParameter('diagnostics', 0);
+p.addParameter('logpost', 0);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -165,6 +172,13 @@ options = struct('nsimu', n_steps, 'burnintime', n_burn, 'adaptint', 100, 'metho
     'seed', o.seed*1000003 + 20201028, 'engine', o.engine, 'adapt_pmax', o.adapt_pmax, ...
     'chain_keys', [setup.cellNum] - 1);
 MCMCdiag = struct([]);
+MCMClp = struct([]);
+if o.logpost && o.thin <= 0
+    error('tci:logpost', 'the log-posterior trace needs the kept chain rows: thin > 0');
+end
+if o.logpost
+    options.logpost = 1;
+end
 if o.diagnostics && o.thin <= 0
     error('tci:diagnostics', 'the diagnostics need the kept chain rows: thin > 0');
 end
@@ -237,6 +251,23 @@ for k = 1:nc
         dg.ess_min = stats.n_rows / max(stats.tau(1:7+n, k));
         dg.cell_index = setup(k).cellNum;
         if isempty(MCMCdiag), MCMCdiag = dg; else, MCMCdiag(k) = dg; end
+    end
+    if o.logpost
+        L = results.logpost;
+        lpk = struct('ss', L.ss(k, :)', 'lp', L.lp(k, :)');
+        for f = {'ss_min', 'ss_mean', 'dev_mean', 'dev_var', 'best_row', 'lp_best', 'ss_best', 's2_best', ...
+                 's2_mean', 'ss_hat', 'd_hat', 'p_d', 'p_v', 'dic'}
+            lpk.(f{1}) = L.(f{1})(k);
+        end
+        names = {'v', 'ton', 'A', 'tau', 'MS2_basal', 'PP7_basal', 'R'};
+        col = [1 3 6 2 4 5 7];
+        for w = 1:7
+            lpk.(['best_' names{w}]) = L.theta_best(col(w), k);
+        end
+        lpk.best_dR = L.theta_best(8:7+n, k)';
+        lpk.n_rows = L.n_rows;
+        lpk.cell_index = setup(k).cellNum;
+        if isempty(MCMClp), MCMClp = lpk; else, MCMClp(k) = lpk; end
     end
     if o.thin > 0
         c = reshape(chain(1:7+n, k, sel), 7+n, [])';   % rows x P

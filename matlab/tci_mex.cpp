@@ -86,6 +86,16 @@
 //          include/tci.h), reduced on the device: arguments as for 'chainrhat'; max_lag: cap on the lags (default 0 =
 //          none). out: struct with ess, ess_split, tau, tau_split, mcse, window, window_split (P x n_groups; the
 //          windows as doubles; NaN / -1 past a group's npar) and n_rows.
+//   out = tci_mex('chainlp', h, cells, chain, s2chain, MU, SIG)
+//          the sum-of-squares trace of chains (mcmcstat's sschain, mcmcrun's fourth output), the prior, deviance and
+//          log-posterior of every row, and per chain the best sample and DIC (tci_chainlp, the definition is in
+//          include/tci.h), on the device: cells 1 x n (1-based, the cell of every chain), chain P x n x rows and
+//          s2chain n x rows as 'dram' returns them, MU and SIG P x n as for 'dram'. out: struct with ss, pri, dev, lp
+//          (n x rows), ss_min, ss_mean, dev_mean, dev_var, lp_best, ss_best, s2_best, s2_mean, ss_hat, d_hat, p_d, p_v,
+//          dic (1 x n), best_row (1 x n, 1-based; 0: a chain with a non-finite trace value, whose other values are
+//          NaN), theta_best, theta_mean (P x n; NaN past a chain's 7 + N), n_rows and kernel_ms. With
+//          options.logpost = true 'dram' attaches the same struct, of the kept rows at or past stats_from, to its
+//          first output as res.logpost (the rows are kept on the device for it even when no chain output is asked for).
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -499,6 +509,43 @@ struct StatsOut {
   }
 };
 
+// The struct of 'chainlp' and of 'dram''s res.logpost, written in place by the ABI: the traces n x rows == [row][chain],
+// the per-chain scalars 1 x n, theta_best and theta_mean P x n == [chain][P]; best_row 1-based (0 = none).
+struct LpOut {
+  static constexpr int kTr = 4, kSc = 13;
+  mxArray* res;
+  std::vector<int64_t> best;
+  size_t n;
+  tci_chainlp_outputs out;
+  LpOut(size_t P, size_t n_, size_t rows) : best(n_), n(n_) {
+    static const char* fields[] = {"ss", "pri", "dev", "lp", "ss_min", "ss_mean", "dev_mean", "dev_var", "lp_best",
+                                   "ss_best", "s2_best", "s2_mean", "ss_hat", "d_hat", "p_d", "p_v", "dic", "theta_best",
+                                   "theta_mean", "best_row", "n_rows", "kernel_ms"};
+    res = mxCreateStructMatrix(1, 1, 22, fields);
+    double* ptr[kTr + kSc + 2];
+    for (int k = 0; k < kTr + kSc + 2; ++k) {
+      mxArray* a = k < kTr ? mxCreateDoubleMatrix(n, rows, mxREAL)
+                           : k < kTr + kSc ? mxCreateDoubleMatrix(1, n, mxREAL) : mxCreateDoubleMatrix(P, n, mxREAL);
+      mxSetField(res, 0, fields[k], a);
+      ptr[k] = mxGetPr(a);
+    }
+    memset(&out, 0, sizeof out);
+    double** dst[kTr + kSc + 2] = {&out.ss, &out.pri, &out.dev, &out.lp, &out.ss_min, &out.ss_mean, &out.dev_mean,
+                                   &out.dev_var, &out.lp_best, &out.ss_best, &out.s2_best, &out.s2_mean, &out.ss_hat,
+                                   &out.d_hat, &out.p_d, &out.p_v, &out.dic, &out.theta_best, &out.theta_mean};
+    for (int k = 0; k < kTr + kSc + 2; ++k) *dst[k] = ptr[k];
+    out.best_row = best.data();
+  }
+  mxArray* finish() {
+    mxArray* b = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t c = 0; c < n; ++c) mxGetPr(b)[c] = (double)(best[c] + 1);
+    mxSetField(res, 0, "best_row", b);
+    mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+    mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+    return res;
+  }
+};
+
 void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (nrhs < 10 || nrhs > 11)
     mexErrMsgIdAndTxt("tci:arg", "tci_mex('dram', h, cells, X0, LB, UB, MU, SIG, J0, sigma2[, options])");
@@ -533,7 +580,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"nsimu", "burnintime", "adaptint", "method", "updatesigma", "drscale", "adascale",
                                   "qcovadj", "burnin_scale", "stats_from", "thin", "seed", "engine", "max_chunk",
-                                  "chain_keys", "adapt_pmax", "max_lag", "verbosity", "waitbar", "printint"};
+                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "verbosity", "waitbar", "printint"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
       bool ok = false;
@@ -565,7 +612,14 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   opt.stats_from = opt_int(o, "stats_from", std::max<int64_t>(opt.burnintime, 1), 1);
   const bool want_chain = nlhs >= 2;
   const int64_t thin = opt_int(o, "thin", 1, 0);
-  opt.thin = want_chain ? thin : 0;
+  const bool want_lp = opt_num(o, "logpost", 0.0) != 0.0;
+  opt.thin = want_chain || want_lp ? thin : 0;
+  int64_t lp_rows = 0;  // the kept rows at or past stats_from (tci_dram_run_lp refuses a run that keeps none)
+  if (want_lp) {
+    if (opt.thin < 1) mexErrMsgIdAndTxt("tci:opts", "options.logpost needs the kept rows: options.thin must be >= 1");
+    lp_rows = (opt.n_steps + opt.thin - 1) / opt.thin - (opt.stats_from - 1 + opt.thin - 1) / opt.thin;
+    if (lp_rows < 1) mexErrMsgIdAndTxt("tci:opts", "options.logpost: no kept row at or past options.stats_from");
+  }
   opt.seed = (uint64_t)opt_int(o, "seed", (int64_t)opt.seed, 0);
   const std::string engine = opt_str(o, "engine", "auto");
   if (engine == "auto") opt.engine = TCI_DRAM_AUTO;
@@ -594,8 +648,8 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   tci_ctx* ctx = handle_of(prhs[1]);
   // outputs, written in place: the ABI's row-major [chain][P] is MATLAB's column-major P x n
   static const char* fields[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
-                                 "elapsed_ms"};
-  mxArray* res = mxCreateStructMatrix(1, 1, 8, fields);
+                                 "elapsed_ms", "logpost"};
+  mxArray* res = mxCreateStructMatrix(1, 1, want_lp ? 9 : 8, fields);
   mxArray* pn[6];
   for (int k = 0; k < 3; ++k) pn[k] = mxCreateDoubleMatrix(P, n, mxREAL);
   for (int k = 3; k < 6; ++k) pn[k] = mxCreateDoubleMatrix(1, n, mxREAL);
@@ -610,7 +664,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   out.sigma_std = mxGetPr(pn[4]);
   out.accept_rate = mxGetPr(pn[5]);
   out.n_evals = nev.data();
-  const size_t n_keep = opt.thin > 0 ? (size_t)((opt.n_steps + opt.thin - 1) / opt.thin) : 0;
+  const size_t n_keep = want_chain && opt.thin > 0 ? (size_t)((opt.n_steps + opt.thin - 1) / opt.thin) : 0;
   mxArray* ch = nullptr;
   mxArray* s2c = nullptr;
   if (want_chain) {
@@ -628,11 +682,22 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     out.qcov_R = rbuf.data();
   }
   StatsOut so(want_stats ? P : 0, want_stats ? n : 0);
-  const int rc = want_stats ? tci_dram_run_stats(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
-                                                 in[5], s2v.data(), (int64_t)P, &out, &sopt, &so.out)
-                            : tci_dram_run(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
-                                           s2v.data(), (int64_t)P, &out);
+  LpOut lo(want_lp ? P : 0, want_lp ? n : 0, (size_t)lp_rows);
+  tci_dram_reductions red;
+  memset(&red, 0, sizeof red);
+  if (want_stats) {
+    red.sopt = &sopt;
+    red.sout = &so.out;
+  }
+  const int rc = want_lp ? tci_dram_run_lp(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
+                                           s2v.data(), (int64_t)P, &out, &red, nullptr, 0, nullptr, nullptr, nullptr,
+                                           nullptr, nullptr, &lo.out)
+                 : want_stats ? tci_dram_run_stats(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
+                                                   in[5], s2v.data(), (int64_t)P, &out, &sopt, &so.out)
+                              : tci_dram_run(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
+                                             s2v.data(), (int64_t)P, &out);
   if (rc != TCI_OK || !want_stats) mxDestroyArray(so.res);
+  if (rc != TCI_OK || !want_lp) mxDestroyArray(lo.res);
   if (rc != TCI_OK) {
     mxDestroyArray(res);
     if (ch) mxDestroyArray(ch);
@@ -643,6 +708,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   for (size_t b = 0; b < n; ++b) mxGetPr(ne)[b] = (double)nev[b];
   mxSetField(res, 0, "n_evals", ne);
   mxSetField(res, 0, "elapsed_ms", mxCreateDoubleScalar(out.elapsed_ms));
+  if (want_lp) mxSetField(res, 0, "logpost", lo.finish());
   plhs[0] = res;
   if (nlhs >= 2) plhs[1] = ch;
   if (nlhs >= 3) plhs[2] = s2c;
@@ -1046,6 +1112,39 @@ void cmd_chainess(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = res;
 }
 
+// ---- 'chainlp': log-posterior trace, best sample and DIC of every chain -------------------------------
+
+void cmd_chainlp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs != 7) mexErrMsgIdAndTxt("tci:arg", "tci_mex('chainlp', h, cells, chain, s2chain, MU, SIG)");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[3], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[3]);
+  const mwSize* d = mxGetDimensions(prhs[3]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  const double* c = doubles(prhs[2], (long long)n, "cells");
+  std::vector<int32_t> cid(n);
+  for (size_t b = 0; b < n; ++b) {
+    if (!(c[b] >= 1 && c[b] <= 2147483647.0) || c[b] != (double)(int64_t)c[b])
+      mexErrMsgIdAndTxt("tci:arg", "cells(%d) must be a positive integer", (int)b + 1);
+    cid[b] = (int32_t)c[b] - 1;
+  }
+  const double* s2 = doubles(prhs[4], (long long)(n * rows), "s2chain");
+  if (n * rows > 1 && (mxGetNumberOfDimensions(prhs[4]) != 2 || mxGetM(prhs[4]) != n))
+    mexErrMsgIdAndTxt("tci:arg", "s2chain must be n x rows, as 'dram' returns it");
+  const double* mu = chain_matrix(prhs[5], "MU", P, n);
+  const double* sig = chain_matrix(prhs[6], "SIG", P, n);
+  tci_ctx* ctx = handle_of(prhs[1]);
+  LpOut lo(P, n, rows);
+  const int rc = tci_chainlp(ctx, nullptr, X, s2, (int64_t)rows, (int64_t)n, (int64_t)P, cid.data(), mu, sig, &lo.out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(lo.res);
+    check(ctx, rc, "tci_chainlp");
+  }
+  plhs[0] = lo.finish();
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -1069,6 +1168,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chaindens") cmd_chaindens(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainrhat") cmd_chainrhat(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainess") cmd_chainess(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chainlp") cmd_chainlp(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

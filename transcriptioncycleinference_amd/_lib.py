@@ -108,6 +108,21 @@ class tci_chaindens_outputs(C.Structure):
                 ("s2_dens", _dp), ("s2_counts", _i32p), ("n_rows", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class tci_chainlp_options(C.Structure):
+    _fields_ = [("flags", C.c_int64)]
+
+
+CHAINLP_TRACES = ("ss", "pri", "dev", "lp")
+CHAINLP_SCALARS = ("ss_min", "ss_mean", "dev_mean", "dev_var", "lp_best", "ss_best", "s2_best", "s2_mean", "ss_hat",
+                   "d_hat", "p_d", "p_v", "dic")
+
+
+class tci_chainlp_outputs(C.Structure):
+    _fields_ = ([(f, _dp) for f in CHAINLP_TRACES + CHAINLP_SCALARS]
+                + [("best_row", _i64p), ("theta_best", _dp), ("theta_mean", _dp), ("n_rows", C.c_int64),
+                   ("kernel_ms", C.c_double)])
+
+
 class tci_dram_reductions(C.Structure):
     _fields_ = [("sopt", C.POINTER(tci_chainstats_options)), ("sout", C.POINTER(tci_chainstats_outputs)),
                 ("copt", C.POINTER(tci_chaincov_options)), ("cout", C.POINTER(tci_chaincov_outputs)),
@@ -208,6 +223,15 @@ SIGNATURES = [
     ("tci_fitcheck_defaults", C.c_int, [C.POINTER(tci_fitcheck_options)]),
     ("tci_fitcheck", C.c_int, [C.c_void_p, C.POINTER(tci_fitcheck_options), _dp, C.c_int64, _dp, _i32p, C.c_int64,
                                C.c_int64, C.c_int64, C.POINTER(tci_fitcheck_outputs)]),
+    ("tci_chainlp_defaults", C.c_int, [C.POINTER(tci_chainlp_options)]),
+    ("tci_chainlp", C.c_int, [C.c_void_p, C.POINTER(tci_chainlp_options), _dp, _dp, C.c_int64, C.c_int64, C.c_int64,
+                              _i32p, _dp, _dp, C.POINTER(tci_chainlp_outputs)]),
+    ("tci_dram_run_lp", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                  _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                  C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
+                                  C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                  C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
+                                  C.POINTER(tci_chainlp_options), C.POINTER(tci_chainlp_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

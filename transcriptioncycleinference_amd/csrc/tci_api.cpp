@@ -1118,6 +1118,115 @@ int chaindens_device(tci_ctx* ctx, const char* who, const double* d_chain, const
   return TCI_OK;
 }
 
+// Checks of a tci_chainlp call before any device work (the cell ids and ld are check_rows'): the options, the sizes
+// and the priors of every chain's P = 7 + N entries.
+int chainlp_check(tci_ctx* ctx, const char* who, const tci_chainlp_options* lopt, int64_t n_rows, int64_t n_chains,
+                  int64_t ld, const int32_t* cell_id, const double* prior_mu, const double* prior_sig, size_t* scratch) {
+  if (n_rows < 1) return fail(ctx, TCI_EINVAL, std::string(who) + ": n_rows must be >= 1");
+  if (lopt && lopt->flags != 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": flags is reserved and must be 0");
+  int rc = check_rows(ctx, ld, cell_id, n_chains);
+  if (rc != TCI_OK) return rc;
+  rc = tci::chainlp_scratch_bytes(n_rows, n_chains, ld, scratch);
+  if (rc != TCI_OK)
+    return fail(ctx, rc, std::string(who) + ": n_rows * n_chains must stay below 2^31 (n_rows and n_chains at most 2^30, ld 2^24)");
+  for (int64_t c = 0; c < n_chains; ++c) {
+    const int64_t P = 7 + ctx->meta[(size_t)cell_id[c]].n;
+    for (int64_t j = 0; j < P; ++j) {
+      const double m = prior_mu[c * ld + j], s = prior_sig[c * ld + j];
+      if (!std::isfinite(m))
+        return fail(ctx, TCI_EINVAL, std::string(who) + ": prior_mu of chain " + std::to_string(c) + ", index " +
+                                         std::to_string(j) + " is not finite");
+      if (!(s > 0))
+        return fail(ctx, TCI_EINVAL, std::string(who) + ": prior_sig of chain " + std::to_string(c) + ", index " +
+                                         std::to_string(j) + " is NaN or <= 0");
+    }
+  }
+  return TCI_OK;
+}
+
+// The log-posterior kernels on a device chain (tci_chainlp.hip) with the two likelihood launches between them, timed
+// with HIP events, and their results copied into the caller's host buffers. d_cell, d_npar (= 7 + N), d_mu and d_sig
+// are the chains' (device); scratch: chainlp_check's.
+int chainlp_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                   int64_t n_chains, int64_t ld, const int32_t* d_cell, const int32_t* d_npar, const double* d_mu,
+                   const double* d_sig, size_t scratch, tci_chainlp_outputs* out) {
+  const size_t n = (size_t)n_chains, L = (size_t)ld, B = (size_t)n_rows * n;
+  const int K = tci::kChainlpScalars;
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  int32_t* d_rowcell = A.alloc<int32_t>(B, &e);
+  double* d_tr = e == hipSuccess ? A.alloc<double>(4 * B, &e) : nullptr;  // ss, pri, dev, lp
+  double* d_scal = e == hipSuccess ? A.alloc<double>((size_t)K * n, &e) : nullptr;
+  int64_t* d_best = e == hipSuccess ? A.alloc<int64_t>(n, &e) : nullptr;
+  double* d_tb = e == hipSuccess ? A.alloc<double>(n * L, &e) : nullptr;
+  double* d_tm = e == hipSuccess ? A.alloc<double>(n * L, &e) : nullptr;
+  char* d_scr = e == hipSuccess ? A.alloc<char>(scratch, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the traces failed");
+  }
+  std::vector<double> hs;
+  try {
+    hs.resize((size_t)K * n);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  double *d_ss = d_tr, *d_pri = d_tr + B, *d_dev = d_tr + 2 * B, *d_lp = d_tr + 3 * B;
+  hipStream_t s = ctx->stream;
+  hipEvent_t ev0, ev1;
+  TCI_HIP(ctx, hipEventCreate(&ev0));
+  e = hipEventCreate(&ev1);
+  if (e != hipSuccess) {
+    (void)hipEventDestroy(ev0);
+    return hip_fail(ctx, e, "hipEventCreate");
+  }
+  hipError_t e1 = hipEventRecord(ev0, s);
+  // the SS of every kept row: one launch of the batched likelihood kernel straight on the chain
+  int rc = tci::launch_chainlp_ids(d_cell, n_rows, n_chains, d_rowcell, (void*)s);
+  if (rc == TCI_OK)
+    rc = tci::launch(ctx->kp, ctx->rpl, tci::MODE_SS, d_chain, ld, d_rowcell, nullptr, (int64_t)B, d_ss, nullptr, 0, (void*)s);
+  if (rc == TCI_OK)
+    rc = tci::launch_chainlp_rows(ctx->kp, d_chain, d_s2, d_ss, d_cell, d_mu, d_sig, n_rows, n_chains, ld, d_pri, d_dev,
+                                  d_lp, (void*)s);
+  // the means through tci_chaincov's mean kernel (s2: a chain of one column), then the SS of the mean rows
+  if (rc == TCI_OK) rc = tci::launch_chain_mean(d_chain, n_rows, n_chains, ld, d_npar, d_tm, (void*)s);
+  if (rc == TCI_OK) rc = tci::launch_chain_mean(d_s2, n_rows, n_chains, 1, nullptr, d_scal + 7 * n, (void*)s);
+  if (rc == TCI_OK)
+    rc = tci::launch(ctx->kp, ctx->rpl, tci::MODE_SS, d_tm, ld, d_cell, nullptr, n_chains, d_scal + 8 * n, nullptr, 0, (void*)s);
+  if (rc == TCI_OK)
+    rc = tci::launch_chainlp_reduce(ctx->kp, d_chain, d_s2, d_ss, d_pri, d_dev, d_lp, d_cell, n_rows, n_chains, ld, d_scr,
+                                    d_scal, d_best, d_tb, d_tm, (void*)s);
+  if (e1 == hipSuccess) e1 = hipEventRecord(ev1, s);
+  auto copy = [&](void* dst, const void* src, size_t bytes) {
+    if (dst && rc == TCI_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
+  };
+  copy(out->ss, d_ss, B * sizeof(double));
+  copy(out->pri, d_pri, B * sizeof(double));
+  copy(out->dev, d_dev, B * sizeof(double));
+  copy(out->lp, d_lp, B * sizeof(double));
+  copy(hs.data(), d_scal, (size_t)K * n * sizeof(double));
+  copy(out->best_row, d_best, n * sizeof(int64_t));
+  copy(out->theta_best, d_tb, n * L * sizeof(double));
+  copy(out->theta_mean, d_tm, n * L * sizeof(double));
+  const hipError_t e2 = hipStreamSynchronize(s);
+  float ms = 0.f;
+  if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventElapsedTime(&ms, ev0, ev1);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "log-posterior kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "log-posterior kernels");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "log-posterior copy");
+  double* dst[tci::kChainlpScalars] = {out->ss_min,  out->ss_mean, out->dev_mean, out->dev_var, out->lp_best,
+                                       out->ss_best, out->s2_best, out->s2_mean,  out->ss_hat,  out->d_hat,
+                                       out->p_d,     out->p_v,     out->dic};
+  for (int k = 0; k < K; ++k)
+    if (dst[k]) std::memcpy(dst[k], hs.data() + (size_t)k * n, n * sizeof(double));
+  out->n_rows = n_rows;
+  out->kernel_ms = ms;
+  return TCI_OK;
+}
+
 // The groups of a tci_chainrhat call, checked before any device work: group (null: every chain in group 0) as the
 // per-chain vector the kernels skip by, and its CSR form (the chains of a group ascending). npar (host, may be null =
 // ld): the chains of a group must have one npar.
@@ -1336,11 +1445,13 @@ namespace {
 // tci_dram_run, with the reductions of the kept rows that `red` asks for: red.sout the chain statistics
 // (tci_dram_run_stats), red.cout their mean, covariance and correlation (tci_dram_run_cov), red.qout their
 // quantiles and red.dout their densities and histograms (tci_dram_run_reduced); rhat: the reduction across the
-// chains of every group over the same rows (tci_dram_run_rhat).
+// chains of every group over the same rows (tci_dram_run_rhat); lout: the log-posterior trace of the same rows
+// (tci_dram_run_lp).
 int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
                   const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                   const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
-                  tci_dram_outputs* out, const tci_dram_reductions& red, const RhatAsk* rhat = nullptr) {
+                  tci_dram_outputs* out, const tci_dram_reductions& red, const RhatAsk* rhat = nullptr,
+                  const tci_chainlp_options* lopt = nullptr, tci_chainlp_outputs* lout = nullptr) {
   if (!ctx) return TCI_EINVAL;
   const tci_chainstats_options* sopt = red.sopt;
   tci_chainstats_outputs* sout = red.sout;
@@ -1409,6 +1520,16 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     const int rcd = chaindens_opts(ctx, "tci_dram_run_reduced", red.dopt, d_rows, n_chains, ld, &d_G, &d_B, &d_bws, &d_scratch);
     if (rcd != TCI_OK) return rcd;
   }
+  int64_t l_k0 = 0, l_rows = 0;  // and so does the log-posterior trace
+  if (lout) {
+    if (opt->thin <= 0)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_lp: the log-posterior trace needs the kept rows (thin >= 1)");
+    const int64_t from = std::max<int64_t>(opt->stats_from, 1);
+    l_k0 = (from - 1 + opt->thin - 1) / opt->thin;
+    l_rows = (opt->n_steps + opt->thin - 1) / opt->thin - l_k0;
+    if (l_rows < 1)
+      return fail(ctx, TCI_EINVAL, "tci_dram_run_lp: no kept row at or past stats_from (n_rows < 1)");
+  }
   int64_t r_k0 = 0, r_rows = 0;  // and so does the group reduction
   if (rhat) {
     if (opt->thin <= 0)
@@ -1426,6 +1547,11 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   int rc = check_rows(ctx, ld, cell_id, n_chains);
   if (rc != TCI_OK) return rc;
   if (ld > TCI_MAX_POINTS + 7) return fail(ctx, TCI_ERANGE, "tci_dram_run: ld too large");
+  size_t l_scratch = 0;
+  if (lout) {
+    rc = chainlp_check(ctx, "tci_dram_run_lp", lopt, l_rows, n_chains, ld, cell_id, prior_mu, prior_sig, &l_scratch);
+    if (rc != TCI_OK) return rc;
+  }
   const size_t n = (size_t)n_chains, L = (size_t)ld, L2 = L * L;
   std::vector<int32_t> npar(n), nobs(n);
   for (size_t c = 0; c < n; ++c) {
@@ -1542,7 +1668,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   TCI_ALLOC(prof, int64_t, 32);
   TCI_HIP(ctx, hipMemsetAsync(st.prof, 0, 32 * sizeof(int64_t), ctx->stream));
 #endif
-  if (n_keep > 0 && (sout || cvout || qout || dout || rhat) && !(out->chain || out->s2chain)) {
+  if (n_keep > 0 && (sout || cvout || qout || dout || lout || rhat) && !(out->chain || out->s2chain)) {
     // the chain is kept on the device for the statistics alone: running out of memory is the caller's to handle
     st.chain_out = A.alloc<double>((size_t)n_keep * n * L, &e);
     if (e == hipSuccess) st.s2_out = A.alloc<double>((size_t)n_keep * n, &e);
@@ -1821,6 +1947,11 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
                           st.s2_out + (size_t)d_k0 * n, d_rows, n_chains, ld, st.npar, d_G, d_B, d_bws, d_scratch, dout);
     if (rc != TCI_OK) return rc;
   }
+  if (lout) {
+    rc = chainlp_device(ctx, "tci_dram_run_lp", st.chain_out + (size_t)l_k0 * n * L, st.s2_out + (size_t)l_k0 * n,
+                        l_rows, n_chains, ld, st.cell, st.npar, st.pmu, st.psig, l_scratch, lout);
+    if (rc != TCI_OK) return rc;
+  }
   if (rhat)
     return chainrhat_device(ctx, rhat->who, st.chain_out + (size_t)r_k0 * n * L,
                             st.s2_out + (size_t)r_k0 * n, r_rows, n_chains, ld, st.npar, r_groups, rhat->n_groups,
@@ -2002,6 +2133,26 @@ int tci_dram_run_ess(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains
                        out, red ? *red : tci_dram_reductions{}, &ask);
 }
 
+int tci_dram_run_lp(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                    const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                    const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                    tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                    const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                    tci_chainess_outputs* eout, const tci_chainlp_options* lopt, tci_chainlp_outputs* lout) {
+  if (!ctx) return TCI_EINVAL;
+  if (!lout) return fail(ctx, TCI_EINVAL, "tci_dram_run_lp: null log-posterior outputs");
+  const tci_dram_reductions none{};
+  if (!group)
+    return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                         out, red ? *red : none, nullptr, lopt, lout);
+  if (!rout && !eout) return fail(ctx, TCI_EINVAL, "tci_dram_run_lp: group without group reduction outputs");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_dram_run_lp: n_groups must be in [1, n_chains]");
+  const RhatAsk ask{ropt, group, n_groups, rout, "tci_dram_run_lp", eopt, eout};
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, red ? *red : none, &ask, lopt, lout);
+}
+
 int tci_chainess_defaults(tci_chainess_options* o) {
   if (!o) return TCI_EINVAL;
   o->max_lag = 0;  // L - 1: the pairs are summed until Geyer's sequence stops
@@ -2048,6 +2199,50 @@ int tci_chainess(tci_ctx* ctx, const tci_chainess_options* opt, const double* ch
   if (d_npar) TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar, (size_t)n_chains * sizeof(int32_t), hipMemcpyHostToDevice, s));
   return chainrhat_device(ctx, "tci_chainess", d_chain, d_s2, n_rows, n_chains, ld, d_npar, G, n_groups, nullptr,
                           opt ? opt->max_lag : 0, out);
+}
+
+int tci_chainlp_defaults(tci_chainlp_options* o) {
+  if (!o) return TCI_EINVAL;
+  o->flags = 0;
+  return TCI_OK;
+}
+
+int tci_chainlp(tci_ctx* ctx, const tci_chainlp_options* opt, const double* chain, const double* s2chain,
+                int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* cell_id, const double* prior_mu,
+                const double* prior_sig, tci_chainlp_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !s2chain || !cell_id || !prior_mu || !prior_sig || !out)
+    return fail(ctx, TCI_EINVAL, "tci_chainlp: null argument");
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chainlp: n_chains and ld must be >= 1");
+  size_t scratch = 0;
+  const int rc = chainlp_check(ctx, "tci_chainlp", opt, n_rows, n_chains, ld, cell_id, prior_mu, prior_sig, &scratch);
+  if (rc != TCI_OK) return rc;
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  const size_t n = (size_t)n_chains, L = (size_t)ld;
+  const size_t nch = (size_t)n_rows * n * L, ns2 = (size_t)n_rows * n;  // n_rows * n_chains < 2^31, ld <= 2^24
+  std::vector<int32_t> npar(n);
+  for (size_t c = 0; c < n; ++c) npar[c] = 7 + ctx->meta[(size_t)cell_id[c]].n;
+  double* d_chain = A.alloc<double>(nch, &e);
+  double* d_s2 = e == hipSuccess ? A.alloc<double>(ns2, &e) : nullptr;
+  int32_t* d_cell = e == hipSuccess ? A.alloc<int32_t>(n, &e) : nullptr;
+  int32_t* d_npar = e == hipSuccess ? A.alloc<int32_t>(n, &e) : nullptr;
+  double* d_mu = e == hipSuccess ? A.alloc<double>(n * L, &e) : nullptr;
+  double* d_sig = e == hipSuccess ? A.alloc<double>(n * L, &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, "tci_chainlp: the chain (" + std::to_string(nch * sizeof(double)) +
+                                     " bytes) does not fit the device");
+  }
+  hipStream_t s = ctx->stream;
+  TCI_HIP(ctx, hipMemcpyAsync(d_chain, chain, nch * sizeof(double), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_s2, s2chain, ns2 * sizeof(double), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_cell, cell_id, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_npar, npar.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_mu, prior_mu, n * L * sizeof(double), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_sig, prior_sig, n * L * sizeof(double), hipMemcpyHostToDevice, s));
+  return chainlp_device(ctx, "tci_chainlp", d_chain, d_s2, n_rows, n_chains, ld, d_cell, d_npar, d_mu, d_sig, scratch, out);
 }
 
 int tci_chainrhat_defaults(tci_chainrhat_options* o) {

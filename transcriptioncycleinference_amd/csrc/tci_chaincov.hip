@@ -208,6 +208,18 @@ int launch_chaincov(const double* chain, int64_t n_rows, int64_t n_chains, int64
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 
+int launch_chain_mean(const double* chain, int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar,
+                      double* mean, void* stream) {
+  if (!chain || !mean || n_rows < 1 || n_rows > ((int64_t)1 << 30) || n_chains < 1 || ld < 1 || ld > ((int64_t)1 << 24))
+    return TCI_EINVAL;
+  const int64_t tiles = (ld + 63) / 64;
+  if (n_chains * tiles > 2147483647) return TCI_EINVAL;
+  const CcView v{chain, npar, n_chains, ld, 0};
+  hipLaunchKernelGGL(k_cc_mean, dim3((unsigned)(n_chains * tiles)), dim3(64), 0, (hipStream_t)stream, v, n_rows,
+                     (int)tiles, mean);
+  return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
+}
+
 int64_t chaincov_max_chains(int64_t ld) { return ((int64_t)1 << 30) / (ld > 1 ? ld : 1); }
 
 }  // namespace tci

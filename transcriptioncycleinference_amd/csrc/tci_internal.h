@@ -118,6 +118,10 @@ int launch_chaincov(const double* chain, int64_t n_rows, int64_t n_chains, int64
                     int64_t nc, double* mean, double* cov, double* corr, void* stream);
 // The most chains one launch_chaincov takes (grid limits).
 int64_t chaincov_max_chains(int64_t ld);
+// launch_chaincov's mean alone (its k_cc_mean, the same bits) for every chain, n_rows >= 1. mean (device):
+// [n_chains][ld]. A chain's s2 [n_rows][n_chains] goes through as a chain of ld = 1 with npar null.
+int launch_chain_mean(const double* chain, int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar,
+                      double* mean, void* stream);
 
 // Exact quantiles (tci_chainquant.hip) of every column of a device chain [n_rows][n_chains][ld] and, when s2 is
 // not null, of s2 [n_rows][n_chains] as column ld of every chain. npar (device, may be null = ld): columns
@@ -168,5 +172,29 @@ int launch_chainess(const double* chain, const double* s2, int64_t n_rows, int64
                     const int32_t* npar, const int32_t* group, int64_t n_groups, const int32_t* g_off,
                     const int32_t* g_list, int64_t max_lag, const double* cap, void* scratch, double* rhat_out,
                     double* out_d, int32_t* out_w, void* stream);
+
+// Log-posterior trace, best sample and DIC of every chain (tci_chainlp.hip) of a device chain [n_rows][n_chains][ld]
+// with its s2 [n_rows][n_chains]; the traces are laid out as s2 is. cell (device): [n_chains], valid ids of cells
+// with 7 + N <= ld (the host checks). n_rows * n_chains must stay below 2^31 (TCI_ERANGE), the likelihood launch's
+// grid. All asynchronous on `stream`; TCI_EINVAL on a bad size or a null pointer, TCI_EHIP on a HIP error.
+//   launch_chainlp_ids     row_cell (device): [n_rows * n_chains], the cell of every (row, chain): the id vector of the
+//                          likelihood launch on the chain.
+//   launch_chainlp_rows    ss: the likelihood launch's output; mu, sig (device): [n_chains][ld] priors. Writes pri, dev, lp.
+//   launch_chainlp_reduce  scal (device): [kChainlpScalars][n_chains] = ss_min, ss_mean, dev_mean, dev_var, lp_best,
+//                          ss_best, s2_best, s2_mean, ss_hat, d_hat, p_d, p_v, dic; on entry plane 7 holds the s2 mean
+//                          (launch_chain_mean) and plane 8 the SS of theta_mean. theta_mean (device): [n_chains][ld], on
+//                          entry launch_chain_mean's; a chain with a non-finite ss, pri or dev gets NaN there, in every
+//                          plane of scal and in theta_best, and best_row -1. scratch (device): chainlp_scratch_bytes()
+//                          bytes, 8-byte aligned.
+constexpr int kChainlpScalars = 13;
+int launch_chainlp_ids(const int32_t* cell, int64_t n_rows, int64_t n_chains, int32_t* row_cell, void* stream);
+int launch_chainlp_rows(const KParams& kp, const double* chain, const double* s2, const double* ss, const int32_t* cell,
+                        const double* mu, const double* sig, int64_t n_rows, int64_t n_chains, int64_t ld, double* pri,
+                        double* dev, double* lp, void* stream);
+int launch_chainlp_reduce(const KParams& kp, const double* chain, const double* s2, const double* ss, const double* pri,
+                          const double* dev, const double* lp, const int32_t* cell, int64_t n_rows, int64_t n_chains,
+                          int64_t ld, void* scratch, double* scal, int64_t* best_row, double* theta_best,
+                          double* theta_mean, void* stream);
+int chainlp_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, size_t* bytes);
 
 }  // namespace tci

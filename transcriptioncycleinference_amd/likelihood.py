@@ -336,6 +336,52 @@ class FitCheck:
                                          P(self.elpd_waic), P(self.chi2), P(self.coverage), P(self.dw), 0.0, 0.0)
 
 
+@dataclasses.dataclass
+class ChainLp:
+    """Log-posterior trace, best sample and DIC of every chain (``tci_chainlp_outputs``; formulas in
+    ``include/tci.h``). Traces ``[n_rows, n_chains]``: ``ss`` (mcmcstat's ``sschain``), ``pri``, ``dev``, ``lp``.
+    Per chain ``[n_chains]``: the scalars of ``_lib.CHAINLP_SCALARS`` and ``best_row`` (int64, -1 for a chain with a
+    non-finite trace value); ``theta_best`` and ``theta_mean`` ``[n_chains, ld]``, padding NaN."""
+
+    ss: np.ndarray
+    pri: np.ndarray
+    dev: np.ndarray
+    lp: np.ndarray
+    ss_min: np.ndarray
+    ss_mean: np.ndarray
+    dev_mean: np.ndarray
+    dev_var: np.ndarray
+    lp_best: np.ndarray
+    ss_best: np.ndarray
+    s2_best: np.ndarray
+    s2_mean: np.ndarray
+    ss_hat: np.ndarray
+    d_hat: np.ndarray
+    p_d: np.ndarray
+    p_v: np.ndarray
+    dic: np.ndarray
+    best_row: np.ndarray
+    theta_best: np.ndarray
+    theta_mean: np.ndarray
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, rows: int, n: int, ld: int) -> "ChainLp":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        return cls(*[d(rows, n) for _ in _lib.CHAINLP_TRACES], *[d(n) for _ in _lib.CHAINLP_SCALARS],
+                   np.full(n, -1, np.int64), d(n, ld), d(n, ld))
+
+    def options(self) -> "_lib.tci_chainlp_options":
+        return _lib.tci_chainlp_options(0)
+
+    def to_c(self) -> "_lib.tci_chainlp_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        return _lib.tci_chainlp_outputs(*[P(getattr(self, f)) for f in _lib.CHAINLP_TRACES + _lib.CHAINLP_SCALARS],
+                                        _lib.ptr(self.best_row, _lib._i64p), P(self.theta_best), P(self.theta_mean),
+                                        0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -678,6 +724,36 @@ class Likelihood:
                                            C.byref(out)))
         ce.n_rows, ce.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return ce
+
+    def chainlp(self, chain: np.ndarray, s2chain: np.ndarray, cell_id: Sequence[int], prior_mu: np.ndarray,
+                prior_sig: np.ndarray) -> ChainLp:
+        """The sum-of-squares trace of chains held on the host (mcmcstat's ``sschain``, ``mcmcrun``'s fourth output),
+        with the prior, deviance and log-posterior of every row and, per chain, the best sample (a posterior-mode
+        estimate) and DIC, on the device (``tci_chainlp``; the definition is in ``include/tci.h``). ``chain``
+        ``[rows, n_chains, ld]`` (or ``[rows, ld]``: one chain), ``s2chain`` ``[rows, n_chains]``, ``cell_id`` one
+        cell per chain, ``prior_mu`` / ``prior_sig`` ``[n_chains, ld]`` as for ``dram_run``. Returns a
+        :class:`ChainLp`; a chain with a non-finite ss, prior or deviance anywhere has NaN reductions and
+        ``best_row = -1``."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        cid = np.ascontiguousarray(np.atleast_1d(cell_id), np.int32)
+        if cid.shape != (n,):
+            raise ValueError("cell_id must have one entry per chain")
+        mu = np.ascontiguousarray(np.asarray(prior_mu, np.float64).reshape(n, ld))
+        sig = np.ascontiguousarray(np.asarray(prior_sig, np.float64).reshape(n, ld))
+        cl = ChainLp.empty(rows, n, ld)
+        opt, out = cl.options(), cl.to_c()
+        self._check(self._lib.tci_chainlp(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp), rows,
+                                          n, ld, _lib.ptr(cid, _lib._i32p), _lib.ptr(mu, _lib._dp),
+                                          _lib.ptr(sig, _lib._dp), C.byref(out)))
+        cl.n_rows, cl.kernel_ms = int(out.n_rows), float(out.kernel_ms)
+        return cl
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

@@ -28,8 +28,8 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainQuant, ChainRhat, ChainStats, FitCheck,
-                         rhat_groups)
+from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainLp, ChainQuant, ChainRhat, ChainStats,
+                         FitCheck, rhat_groups)
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -65,6 +65,16 @@ ESS_FIELDS = ("ess", "ess_split", "tau", "tau_split", "mcse", "window", "window_
 # at levels, dw [2] per dye
 CHECK_FIELDS = FITCHECK_POINTWISE + ("n_obs", "lppd", "p_waic", "elpd_waic", "waic", "chi2", "coverage", "dw", "levels",
                                      "n_samples", "cell_index")
+# MCMClp (fit(..., logpost=True)): the log-posterior trace of a fitted cell (include/tci.h, tci_chainlp). With one chain
+# per cell the scalars are floats, best_row an int, best_<name> the best sample split into the reference's parameter
+# names (best_dR [N]) and ss / lp the traces [n_rows] (ss: mcmcstat's sschain). With replicates = M every one of those
+# gains a leading axis of M (the traces become [M, n_rows]) and the cell also carries LP_GROUP_FIELDS: R-hat (classic
+# and split), the multi-chain ESS and the MCSE of lp across the replicates, ss_gap = max_r ss_mean - min_r ss_mean and
+# best_replicate, the replicate of the largest lp_best (-1 when every one is NaN)
+LP_SCALARS = _lib.CHAINLP_SCALARS
+LP_FIELDS = (LP_SCALARS + ("best_row",) + tuple("best_" + s for s in _SCALARS) + ("best_dR", "ss", "lp", "n_rows",
+                                                                                  "n_chains", "cell_index"))
+LP_GROUP_FIELDS = ("lp_rhat", "lp_rhat_split", "lp_ess", "lp_mcse", "ss_gap", "best_replicate")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -124,6 +134,7 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    lp: Optional[ChainLp] = None                  # dram_run(logpost=True): log-posterior trace, best sample, DIC
     ess: Optional[ChainEss] = None                # dram_run(group=ids, ess=True): effective sample size of every group
     rhat: Optional[ChainRhat] = None              # dram_run(group=ids): R-hat / pooled moments of every group of chains
     dens: Optional[ChainDens] = None              # dram_run(dens=True): densities / histograms of the kept rows
@@ -135,7 +146,8 @@ class DramResult:
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
-             cov_scratch_bytes: int = 0, quant=None, dens=None, group=None, ess: bool = False) -> DramResult:
+             cov_scratch_bytes: int = 0, quant=None, dens=None, group=None, ess: bool = False,
+             logpost: bool = False) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -154,7 +166,12 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     same rows, at least 2 of them (``DramResult.rhat``, as ``Likelihood.chainrhat`` gives), reduced from the device
     chain through ``tci_dram_run_rhat``, with any of the other reductions. ``ess`` (needs ``group``): also the
     multi-chain effective sample size of every group over those rows (``DramResult.ess``, as ``Likelihood.chainess``
-    gives, with ``max_lag`` as its cap on the lags), through ``tci_dram_run_ess``."""
+    gives, with ``max_lag`` as its cap on the lags), through ``tci_dram_run_ess``. ``logpost``: also the sum-of-squares
+    trace (mcmcstat's ``sschain``), the prior, deviance and log-posterior of every one of those same rows and per chain
+    the best sample and DIC (``DramResult.lp``, as ``Likelihood.chainlp`` gives with the run's priors), from the device
+    chain through ``tci_dram_run_lp``, with any of the other reductions. With ``logpost`` the priors are checked before
+    the run as ``Likelihood.chainlp`` checks them: a ``prior_mu`` entry (of a chain's ``7 + N``) that is not finite, or a
+    ``prior_sig`` entry that is NaN or <= 0, is a ``TciError`` (``TCI_EINVAL``) although the sampler alone would run."""
     if ess and group is None:
         raise ValueError("ess=True needs group: the effective sample size is a statistic of groups of chains")
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
@@ -181,7 +198,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = cc = cq = cd = cr = ce = None
+    cs = cc = cq = cd = cr = ce = clp = None
     sopt = sout = None
     if group is not None:
         grp, ng = rhat_groups(group, n)
@@ -195,7 +212,10 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     if stats:
         cs = ChainStats.empty(n, ld)
         sopt, sout = _lib.tci_chainstats_options(int(max_lag)), cs.to_c()
-    if cq is not None or cd is not None or cr is not None:
+    if logpost:
+        k0 = (max(int(opts.stats_from), 1) - 1 + opts.thin - 1) // opts.thin if opts.thin > 0 else 0
+        clp = ChainLp.empty(max(n_keep - k0, 0), n, ld)
+    if cq is not None or cd is not None or cr is not None or clp is not None:
         red = _lib.tci_dram_reductions()
         if cq is not None:
             qopt, qout = cq.options(), cq.to_c()
@@ -209,7 +229,23 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
             cc = ChainCov.empty(n, ld)
             copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
             red.copt, red.cout = C.pointer(copt), C.pointer(cout)
-        if cr is not None:
+        if clp is not None:   # tci_dram_run_lp takes every other reduction with it
+            lopt, lout = clp.options(), clp.to_c()
+            ropt = rout = eopt = eout = None
+            if cr is not None:
+                ropt, rout = cr.options(), cr.to_c()
+            if ce is not None:
+                eopt, eout = ce.options(), ce.to_c()
+            ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
+            lk._check(lk._lib.tci_dram_run_lp(*args, C.byref(red), _lib.ptr(grp, _lib._i32p) if cr is not None else None,
+                                              ng if cr is not None else 0, ref(ropt), ref(rout), ref(eopt), ref(eout),
+                                              C.byref(lopt), C.byref(lout)))
+            clp.n_rows, clp.kernel_ms = int(lout.n_rows), float(lout.kernel_ms)
+            if cr is not None:
+                cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
+            if ce is not None:
+                ce.n_rows, ce.kernel_ms = int(eout.n_rows), float(eout.kernel_ms)
+        elif cr is not None:
             ropt, rout = cr.options(), cr.to_c()
             if ce is not None:
                 eopt, eout = ce.options(), ce.to_c()
@@ -242,7 +278,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
         cs.n_rows, cs.kernel_ms = int(sout.n_rows), float(sout.kernel_ms)
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
                       kernel_ms=np.array(out.kernel_ms[:], np.float64),
-                      kernel_launches=np.array(out.kernel_launches[:], np.int64), ess=ce, rhat=cr, dens=cd, quant=cq, stats=cs,
+                      kernel_launches=np.array(out.kernel_launches[:], np.int64), lp=clp, ess=ce, rhat=cr, dens=cd, quant=cq, stats=cs,
                       cov=cc)
 
 
@@ -302,6 +338,7 @@ class FitResult:
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
     MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
+    MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
     MCMCess: Optional[List[Dict]] = None       # fit(..., replicates=M, ess=True): ESS_FIELDS per fitted cell
     MCMCrhat: Optional[List[Dict]] = None      # fit(..., replicates=M): RHAT_FIELDS per fitted cell
     MCMCdens: Optional[List[Dict]] = None      # fit(..., density=True): DENS_FIELDS per fitted cell
@@ -418,7 +455,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
-        rhat: Optional[bool] = None, ess: bool = False) -> FitResult:
+        rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -470,7 +507,15 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     ``ess`` (needs ``MCMCrhat``, i.e. replicates or ``rhat=True``): also ``MCMCess``, one dict of ``ESS_FIELDS`` per
     fitted cell: the multi-chain effective sample size (BDA3 11.5) and autocorrelation time, classic and split, the
     lags summed and the pooled mean's Monte-Carlo standard error, over the same rows and reduced on the device
-    (:func:`ess_entry`); ``max_lag`` caps its lags as it caps the diagnostics'. Nothing else in the result changes."""
+    (:func:`ess_entry`); ``max_lag`` caps its lags as it caps the diagnostics'. Nothing else in the result changes.
+
+    ``logpost``: also ``MCMClp``, one dict of ``LP_FIELDS`` per fitted cell: the sum-of-squares trace (mcmcstat's
+    ``sschain``) and the log-posterior trace of the rows ``MCMCchain`` keeps (needs ``thin >= 1``), the best sample (a
+    posterior-mode estimate) and DIC, all on the device (:func:`lp_entry`). With ``replicates=M`` the entry holds every
+    replicate's values and ``LP_GROUP_FIELDS``: R-hat, ESS and MCSE of ``lp`` across the replicates (the ``lp__``
+    diagnostic), ``ss_gap`` and ``best_replicate``: whether replicates that disagree sit at different SS levels. The
+    priors :func:`plan_fit` builds always pass the check ``dram_run(..., logpost=True)`` makes on them (a
+    ``ratePriorWidth`` that is NaN or <= 0 does not: such a fit runs without ``logpost`` and is refused with it)."""
     M = int(replicates)
     if M != replicates or M < 1:
         raise ValueError("replicates must be an integer >= 1")
@@ -480,6 +525,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
                          "pass rhat=False to run the replicates without it")
     if ess and not want_rhat:
         raise ValueError("MCMCess is reduced with MCMCrhat: ess=True needs replicates > 1 or rhat=True")
+    if logpost and int(thin) < 1:
+        raise ValueError("MCMClp is reduced from the kept rows: logpost=True needs thin >= 1")
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -497,6 +544,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
                    plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys,
                    **(dict(group=np.tile(np.arange(K, dtype=np.int32), M)) if want_rhat else {}),
                    **(dict(ess=True) if ess else {}),
+                   **(dict(logpost=True) if logpost else {}),
                    **(dict(stats=True) if diagnostics else {}),
                    **(dict(max_lag=max_lag) if ess or diagnostics else {}),
                    **(dict(cov=True) if covariance else {}),
@@ -550,9 +598,54 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     es = None
     if res.ess is not None:
         es = [ess_entry(res.ess, k, int(cl.lengths[c]), off + c + 1, M) for k, c in enumerate(keep)]
+    lps = None
+    if res.lp is not None:
+        grp = lp_group_stats(lk, res.lp, K, M, max_lag) if M > 1 else None
+        lps = [lp_entry(res.lp, k, int(cl.lengths[c]), off + c + 1, K, M, grp) for k, c in enumerate(keep)]
     return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
-                     res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMCess=es, MCMCrhat=rh,
+                     res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMClp=lps, MCMCess=es,
+                     MCMCrhat=rh,
                      MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+
+
+def lp_group_stats(lk, clp: ChainLp, K: int, M: int, max_lag: int = 0) -> Dict[str, np.ndarray]:
+    """R-hat (classic, split), multi-chain ESS and MCSE of the ``lp`` trace across the ``M`` replicates of each of ``K``
+    cells (chains replicate-major, as :func:`fit` orders them): the returned trace goes through
+    ``Likelihood.chainrhat`` / ``chainess`` as a chain of one column, one group per cell. ``[K]`` each."""
+    col = np.ascontiguousarray(clp.lp[:, :, None])
+    group = np.tile(np.arange(K, dtype=np.int32), M)
+    cr = lk.chainrhat(col, group=group)
+    ce = lk.chainess(col, group=group, max_lag=max_lag)
+    return {"lp_rhat": cr.rhat[:, 0].copy(), "lp_rhat_split": cr.rhat_split[:, 0].copy(), "lp_ess": ce.ess[:, 0].copy(),
+            "lp_mcse": ce.mcse[:, 0].copy()}
+
+
+def lp_entry(clp: ChainLp, k: int, n: int, cell_index: int, K: int = 1, M: int = 1, group: Optional[Dict] = None) -> Dict:
+    """One ``MCMClp`` entry (``LP_FIELDS``) of a cell of ``n`` points from the chains ``k, k + K, ..`` (its ``M``
+    replicates, replicate-major) of ``clp``. ``M == 1``: floats, ``best_row`` an int, ``best_dR`` ``[n]``, the traces
+    ``[n_rows]``; ``M > 1``: a leading axis of ``M`` on each, and ``LP_GROUP_FIELDS`` from ``group``
+    (:func:`lp_group_stats`, entry ``k``), ``ss_gap`` and ``best_replicate``."""
+    rows = np.arange(M) * K + k
+    d = {f: getattr(clp, f)[rows].copy() for f in LP_SCALARS + ("best_row",)}
+    tb = clp.theta_best[rows]
+    for name in _SCALARS:
+        d["best_" + name] = tb[:, THETA_INDEX[name]].copy()
+    d["best_dR"] = tb[:, 7:7 + n].copy()
+    d["ss"], d["lp"] = clp.ss[:, rows].T.copy(), clp.lp[:, rows].T.copy()
+    fields = LP_FIELDS
+    if M == 1:
+        d = {f: (int(v[0]) if f == "best_row" else float(v[0]) if v.ndim == 1 else v[0]) for f, v in d.items()}
+    else:
+        fields = LP_FIELDS + LP_GROUP_FIELDS
+        for f in ("lp_rhat", "lp_rhat_split", "lp_ess", "lp_mcse"):
+            d[f] = float(group[f][k])
+        sm, lb = d["ss_mean"], d["lp_best"]
+        d["ss_gap"] = float(np.max(sm) - np.min(sm))  # NaN when a replicate's is
+        d["best_replicate"] = -1 if np.all(np.isnan(lb)) else int(np.nanargmax(lb))
+    d["n_rows"] = int(clp.n_rows)
+    d["n_chains"] = int(M)
+    d["cell_index"] = int(cell_index)
+    return {f: d[f] for f in fields}
 
 
 def ess_entry(ce: ChainEss, k: int, n: int, cell_index: int, n_chains: int) -> Dict:
@@ -811,6 +904,9 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCess"] = _struct_array(fit_result.MCMCess, ESS_FIELDS)
     if fit_result.MCMCdens is not None:  # only a fit with density=True
         variables["MCMCdens"] = _struct_array(fit_result.MCMCdens, DENS_FIELDS)
+    if fit_result.MCMClp is not None:  # only a fit with logpost=True
+        lp_fields = LP_FIELDS + (LP_GROUP_FIELDS if any("lp_rhat" in e for e in fit_result.MCMClp) else ())
+        variables["MCMClp"] = _struct_array(fit_result.MCMClp, lp_fields)
     if fit_result.MCMCcheck is not None:  # only after fitcheck()
         variables["MCMCcheck"] = _struct_array(fit_result.MCMCcheck, CHECK_FIELDS)
     sio.savemat(base + ".mat", variables)

@@ -243,6 +243,79 @@ def unpack_quant(rows: np.ndarray):
     return out
 
 
+_LP_NAMES = ("v", "ton", "A", "tau", "MS2_basal", "PP7_basal", "R")
+
+
+def lp_width(M: int, n_max: int, n_rows: int) -> int:
+    """Columns of a :func:`pack_lp` row."""
+    from .mcmc import LP_GROUP_FIELDS, LP_SCALARS
+
+    return 4 + len(LP_GROUP_FIELDS) + M * (len(LP_SCALARS) + 1 + len(_LP_NAMES) + n_max + 2 * n_rows)
+
+
+def lp_rows(n_steps: int, n_burn: int, thin: int) -> int:
+    """The kept rows at or past ``max(n_burn, 1)`` of a fit: the length of every ``MCMClp`` trace (include/tci.h)."""
+    thin = int(thin)
+    if thin < 1:
+        return 0
+    return max((int(n_steps) + thin - 1) // thin - (max(int(n_burn), 1) - 1 + thin - 1) // thin, 0)
+
+
+def pack_lp(lps, M: int, n_max: int, n_rows: int) -> np.ndarray:
+    """``MCMClp`` as one float64 row per fitted cell: cell_index, N, n_rows, M, the six group values (NaN for
+    ``M == 1``), then per replicate the scalars, best_row, the best sample's seven scalars, best_dR (padded to
+    ``n_max``) and the ``ss`` and ``lp`` traces (``n_rows`` each: 16 bytes per kept row and chain, 1 / ld of the
+    chain)."""
+    from .mcmc import LP_GROUP_FIELDS, LP_SCALARS
+
+    ng, per = len(LP_GROUP_FIELDS), len(LP_SCALARS) + 1 + len(_LP_NAMES) + n_max + 2 * n_rows
+    out = np.full((len(lps), lp_width(M, n_max, n_rows)), np.nan)
+    for i, d in enumerate(lps):
+        dR = np.atleast_2d(d["best_dR"])
+        tr_ss, tr_lp = np.atleast_2d(d["ss"]), np.atleast_2d(d["lp"])
+        if tr_ss.shape != (M, n_rows):
+            raise ValueError(f"MCMClp entry {i}: traces of shape {tr_ss.shape}, expected {(M, n_rows)}")
+        n = dR.shape[1]
+        out[i, :4] = d["cell_index"], n, d["n_rows"], M
+        if M > 1:
+            out[i, 4:4 + ng] = [d[f] for f in LP_GROUP_FIELDS]
+        for r in range(M):
+            b = 4 + ng + r * per
+            vals = [np.atleast_1d(d[f])[r] for f in LP_SCALARS + ("best_row",) + tuple("best_" + v for v in _LP_NAMES)]
+            out[i, b:b + len(vals)] = vals
+            out[i, b + len(vals):b + len(vals) + n] = dR[r]
+            out[i, b + per - 2 * n_rows:b + per - n_rows] = tr_ss[r]
+            out[i, b + per - n_rows:b + per] = tr_lp[r]
+    return out
+
+
+def unpack_lp(rows: np.ndarray):
+    """Inverse of :func:`pack_lp` over the gathered rows (any rank order), sorted by cell."""
+    from .mcmc import LP_FIELDS, LP_GROUP_FIELDS, LP_SCALARS
+
+    rows = rows[np.argsort(rows[:, 0], kind="stable")]
+    ng, names = len(LP_GROUP_FIELDS), LP_SCALARS + ("best_row",) + tuple("best_" + v for v in _LP_NAMES)
+    out = []
+    for row in rows:
+        n, M, n_rows = int(row[1]), int(row[3]), int(row[2])
+        per = (len(row) - 4 - ng) // M
+        blk = row[4 + ng:4 + ng + M * per].reshape(M, per)
+        d = {f: blk[:, j].copy() for j, f in enumerate(names)}
+        d["best_row"] = d["best_row"].astype(np.int64)
+        d["best_dR"] = blk[:, len(names):len(names) + n].copy()
+        d["ss"], d["lp"] = blk[:, per - 2 * n_rows:per - n_rows].copy(), blk[:, per - n_rows:].copy()
+        fields = LP_FIELDS
+        if M == 1:
+            d = {f: (int(v[0]) if f == "best_row" else float(v[0]) if v.ndim == 1 else v[0]) for f, v in d.items()}
+        else:
+            fields = LP_FIELDS + LP_GROUP_FIELDS
+            d.update({f: float(x) for f, x in zip(LP_GROUP_FIELDS, row[4:4 + ng])})
+            d["best_replicate"] = int(d["best_replicate"])
+        d.update(cell_index=int(row[0]), n_rows=int(row[2]), n_chains=M)
+        out.append({f: d[f] for f in fields})
+    return out
+
+
 def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=None,
                 cell_offset: Optional[int] = None, **fit_kwargs):
     """``TranscriptionCycleMCMC`` over ``torch.distributed`` ranks, one GPU each: rank r fits its
@@ -291,7 +364,12 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
     of its own cells (a replicate's x0 and RNG stream are keyed by the dataset-wide cell index and the replicate, :func:`mcmc.replicate_keys`), the
     gathered ``MCMCresults`` / ``MCMCplot`` are replicate 0's, and every rank's ``local`` carries the ``MCMCrhat`` of
     its own cells. The gathered result's ``MCMCrhat`` stays ``None``. ``ess=True`` goes the same way: ``MCMCess`` is
-    on every rank's ``local``, and the gathered one stays ``None``."""
+    on every rank's ``local``, and the gathered one stays ``None``.
+
+    ``logpost=True`` (passed on to :func:`mcmc.fit`): every rank's ``MCMClp`` rows are gathered in an all-gather of
+    their own (:func:`pack_lp`; ``gather_bytes`` counts it): the scalars, the best samples, the ``ss`` and ``lp``
+    traces and, with replicates, the group values of every cell, so the gathered result carries ``MCMClp`` the way it
+    carries ``MCMCdiag``."""
     import time
 
     import torch
@@ -349,6 +427,13 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
         nq = len(np.atleast_1d(quantiles))
         qlocal = pack_quant(fr.MCMCquant, n_max) if fr is not None else np.zeros((0, quant_width(nq, n_max)))
         qrows = gather_rows(qlocal, group=group, device=device)
+    lrows = None
+    if fit_kwargs.get("logpost", False):
+        Mrep = int(fit_kwargs.get("replicates", 1))
+        nrow = lp_rows(fit_kwargs.get("n_steps", 20000), fit_kwargs.get("n_burn", 10000), fit_kwargs.get("thin", 0))
+        llocal = (pack_lp(fr.MCMClp, Mrep, n_max, nrow) if fr is not None
+                  else np.zeros((0, lp_width(Mrep, n_max, nrow))))
+        lrows = gather_rows(llocal, group=group, device=device)
     gather_s = time.perf_counter() - g0
     ev, ms = (fr.n_evals, fr.elapsed_ms) if fr else (0, 0.0)
     if on:
@@ -369,5 +454,8 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
     if qrows is not None:
         out.MCMCquant = unpack_quant(qrows)
         out.gather_bytes += int(qrows.nbytes)
+    if lrows is not None:
+        out.MCMClp = unpack_lp(lrows)
+        out.gather_bytes += int(lrows.nbytes)
     out.rows_per_lane_uniform = rpl_lo >= rpl_hi   # no rank fitted anything, or all ran one variant
     return out
