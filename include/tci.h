@@ -718,6 +718,94 @@ int tci_fitcheck_defaults(tci_fitcheck_options* opt);
 int tci_fitcheck(tci_ctx* ctx, const tci_fitcheck_options* opt, const double* theta, int64_t ld_theta, const double* s2,
                  const int32_t* cell_id, int64_t n_sel, int64_t S, int64_t ld_out, tci_fitcheck_outputs* out);
 
+/* ---- PSIS-LOO per chain and stacking weights across the chains of a cell (loocheck) ----
+ * How well does a chain predict the data it was not fitted to, and how should replicate chains that do not mix be
+ * weighted? Per selected chain and per scored datum: the Pareto-smoothed importance-sampling leave-one-out log
+ * predictive density (Vehtari, Gelman, Gabry 2017; Vehtari et al. 2024), its Pareto k diagnostic, and per group of
+ * chains of one cell the simplex weights that maximise the stacked LOO density (Yao, Vehtari, Gelman 2022). The
+ * formulas below are the definition.
+ * Inputs, forward model, data, host values sd_s, lg_s, logS, the rule for scored points and r_s, z_s, ll_s: exactly
+ *   those of tci_fitcheck; "selected cell k" there is "selected chain k" here. 32 <= S <= 4096.
+ * For a scored point, every operation rounded once, as written, never fused; exp, log, log1p and expm1 are the device
+ * library's (no fast-math variants); every SUM runs in ascending index from 0.0 unless stated.
+ * Tail selection.
+ *   lr_s = -ll_s;   mx = max_s lr_s;   lr_s = lr_s - mx
+ *   M = min(floor(S / 5), ceil(3 * sqrt(S)))                      6 <= M <= 192
+ *   Total order on the samples: by lr_s as tci_chainquant orders doubles (-0 < +0, NaN above +Inf), ties by ascending
+ *   s (among equal values the larger s is the larger). The tail is the M largest; cut = the largest lr_s not in the
+ *   tail; tail_1 <= ... <= tail_M the tail in that order. Membership and order are exact.
+ * Generalised-Pareto fit (Zhang and Stephens 2009 with the weak prior of Vehtari et al.).
+ *   ec = exp(cut);   x_j = exp(tail_j) - ec, j = 1 .. M
+ *   degenerate when x_M <= 0, x_M is not finite or x_1 < 0: khat = +Inf and the tail stays as it is. Otherwise
+ *   G = 30 + floor(sqrt(M));   xq = x_{floor(M / 4 + 0.5)};   c_g = 1 - sqrt(G / (g - 0.5)), the host's, g = 1 .. G
+ *   b_g = 1 / x_M + c_g / (3 * xq)
+ *   k_g = (SUM_j log1p(-b_g * x_j)) / M
+ *   L_g = M * ((log(-b_g / k_g) + (-k_g)) - 1)
+ *   w_g = 1 / SUM_h exp(L_h - L_g);   b = SUM_g b_g * w_g
+ *   k = (SUM_j log1p(-b * x_j)) / M;   sigma = -k / b;   khat = (k * M + 5.0) / (M + 10)
+ *   khat or sigma not finite: degenerate as above.
+ * Smoothing (not degenerate).   p_j = (j - 0.5) / M;   q_j = (sigma * expm1(-khat * log1p(-p_j))) / khat
+ *   (the generalised-Pareto quantile sigma ((1 - p)^(-khat) - 1) / khat at the regularised khat)
+ *   tail_j = min(log(q_j + ec), 0.0), a NaN kept
+ *   lw_s: lr_s with the tail entries replaced by rank.
+ * Outputs per point.
+ *   lse(v) = mv + log(SUM_s exp(v_s - mv)), mv = max_s v_s, SUM_s in tci_fitcheck's order (segments of 64 samples)
+ *   elpd_loo_i = lse(lw + ll) - lse(lw);   lppd_i: tci_fitcheck's, the same bits;   p_loo_i = lppd_i - elpd_loo_i
+ *   khat_i
+ *   Unscored points and padding (j from N to ld_out): NaN in all four.
+ * Per selected chain, on the host from the pointwise vectors (dye 0 ascending j, then dye 1, scored points, sums from
+ *   0.0): n_obs; elpd_loo, p_loo, lppd (sums); khat_max; n_khat_bad = #{i : khat_i > khat_threshold}. n_obs == 0: NaN.
+ * Per group. group[k] in [0, n_groups) puts chain k into a group, -1 (or group == NULL) into none. All chains of a
+ *   group select one cell (TCI_EINVAL). Over the n points scored in every chain c = 1 .. C of the group (in the order
+ *   given) with finite e_ic = elpd_loo_i of chain c, from w_c = 1 / C, with the C library's exp and log:
+ *     m_i = max_c e_ic;   a_ic = w_c * exp(e_ic - m_i);   w_c <- (SUM_i (a_ic / SUM_c' a_ic')) / n
+ *   until max_iter iterations are done or max_c |new w_c - w_c| <= tol (n_iter counts the iterations done). Every step
+ *   raises SUM_i log SUM_c w_c exp(e_ic), whose maximiser is the stacking weight vector.
+ *     weight[k]      w_c of chain k in its group; NaN for a chain in no group
+ *     elpd_stack[g]  SUM_i (m_i + log SUM_c w_c * exp(e_ic - m_i)) at the final weights
+ *     n_points[g]    n;   n_iter[g]
+ *   One chain: weight 1, n_iter 0. n == 0 or an empty group: NaN weights and elpd_stack, n_iter 0.
+ * Bits. A chain's pointwise and per-chain outputs depend on its samples in order, its data, S and khat_threshold
+ * alone: not on n_sel, the chain's position, ld_theta, ld_out, scratch_bytes, the tile shape or how many workgroups
+ * ran. A group's outputs depend on its chains' pointwise outputs in order.
+ * Error. Tail membership, order and cut are exact; lppd_i has tci_fitcheck's bound. khat passes through a profile
+ * likelihood over G <= 43 points; no useful a-priori bound came out, and the tests compare with a float64 restatement
+ * within 8 x the largest difference between that restatement and its long-double twin on the test inputs
+ * (profiles/loocheck/tolerance.json). */
+typedef struct {
+  int64_t scratch_bytes;   /* cap on the device scratch for simulated rows; 0 = default (1 GiB) */
+  int64_t n_groups;        /* length of the per-group outputs; group ids lie in [-1, n_groups); default 0 */
+  double khat_threshold;   /* 0 = default: min(1 - 1 / log10(S), 0.7); else finite and > 0 */
+  int64_t max_iter;        /* stacking iterations, >= 1; default 5000 */
+  double tol;              /* >= 0; default 1e-12 */
+} tci_loocheck_options;
+
+/* Host buffers (any pointer may be NULL). */
+typedef struct {
+  double *elpd_loo_i, *lppd_i, *p_loo_i, *khat_i;  /* pointwise, each [n_sel][2][ld_out]: dye 0 = MS2, 1 = PP7 */
+  int32_t* n_obs;                                  /* [n_sel] */
+  double *elpd_loo, *p_loo, *lppd, *khat_max;      /* [n_sel] */
+  int32_t* n_khat_bad;                             /* [n_sel] */
+  double* weight;                                  /* [n_sel] */
+  double* elpd_stack;                              /* [n_groups] */
+  int32_t *n_points, *n_iter;                      /* [n_groups] */
+  double khat_threshold;  /* written: the threshold used */
+  double kernel_ms;       /* written: device time of the loocheck kernel (HIP events), summed over the chunks */
+  double forward_ms;      /* written: device time of the forward launches that fill the scratch */
+} tci_loocheck_outputs;
+
+int tci_loocheck_defaults(tci_loocheck_options* opt);
+
+/* HOST pointers, synchronous. opt may be NULL (the defaults); out is required; group may be NULL. 32 <= S <= 4096
+ * (TCI_EINVAL); ld_theta >= 7 + N and ld_out >= N of every selected cell (TCI_ERANGE). TCI_EINVAL, naming the index,
+ * for an s2 entry that is not finite and > 0 and for a group whose chains select different cells; TCI_ERANGE for a
+ * group id outside [-1, n_groups); TCI_EINVAL for scratch_bytes < 0, n_groups < 0, max_iter < 1, tol < 0 or not
+ * finite, khat_threshold < 0 or not finite. Scratch and chunking as for tci_fitcheck. Every check comes before any
+ * device work. */
+int tci_loocheck(tci_ctx* ctx, const tci_loocheck_options* opt, const double* theta, int64_t ld_theta, const double* s2,
+                 const int32_t* cell_id, const int32_t* group, int64_t n_sel, int64_t S, int64_t ld_out,
+                 tci_loocheck_outputs* out);
+
 /* ---- Log-posterior trace, best sample and DIC of every chain (mcmcstat's sschain, mcmcrun's fourth output) ----
  * mcmcrun returns [results, chain, s2chain, sschain]; the sampler here keeps no SS. The kept rows are re-evaluated
  * instead: the engines are bitwise identical to the batched likelihood kernel, so the recomputed SS is the SS the

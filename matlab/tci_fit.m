@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -40,6 +40,11 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp] = tci_fit(data, va
 %        ss_best, s2_best and best_v, best_ton, .. best_dR), s2_mean, ss_hat, d_hat, p_d, p_v, dic, n_rows and
 %        cell_index, all on the device (tci_mex('dram') options.logpost; formulas in include/tci.h). Needs
 %        'thin' > 0.)
+%     'stack' (0; nsample in [32, 4096] fills the sixth output MCMCstack, one entry per fitted cell: the PSIS-LOO
+%        log predictive density elpd_loo_i and Pareto k khat_i of every observed value (2 x N, row 1 = MS2), elpd_loo,
+%        p_loo, khat_max, n_khat_bad, the stacking weights (1 for the one chain a cell has here), elpd_stack,
+%        n_samples and cell_index, over rows round(linspace(1, rows, nsample)) of the post-burn-in rows kept, on the
+%        device (tci_mex('dram') options.stack; formulas in include/tci.h). Needs 'thin' > 0 and 32 such rows.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -68,6 +73,7 @@ p.addParameter('adapt_pmax', 0);
 p.addParameter('predict', 0);
 p.addParameter('diagnostics', 0);
 p.addParameter('logpost', 0);
+p.addParameter('stack', 0);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -179,6 +185,13 @@ end
 if o.logpost
     options.logpost = 1;
 end
+MCMCstack = struct([]);
+if o.stack && o.thin <= 0
+    error('tci:stack', 'PSIS-LOO needs the kept chain rows: thin > 0');
+end
+if o.stack
+    options.stack = o.stack;
+end
 if o.diagnostics && o.thin <= 0
     error('tci:diagnostics', 'the diagnostics need the kept chain rows: thin > 0');
 end
@@ -268,6 +281,16 @@ for k = 1:nc
         lpk.n_rows = L.n_rows;
         lpk.cell_index = setup(k).cellNum;
         if isempty(MCMClp), MCMClp = lpk; else, MCMClp(k) = lpk; end
+    end
+    if o.stack
+        T = results.stack;
+        g = T.group(k);
+        sk = struct('weights', T.weight(k), 'elpd_loo', T.elpd_loo(k), 'p_loo', T.p_loo(k), ...
+            'khat_max', T.khat_max(k), 'n_khat_bad', T.n_khat_bad(k), 'elpd_loo_i', T.elpd_loo_i(1:n, :, k)', ...
+            'khat_i', T.khat_i(1:n, :, k)', 'elpd_stack', T.elpd_stack(g), ...
+            'stacked_mean', T.weight(k)*results.mean(1:7+n, k)', 'n_samples', numel(T.rows), ...
+            'cell_index', setup(k).cellNum);
+        if isempty(MCMCstack), MCMCstack = sk; else, MCMCstack(k) = sk; end
     end
     if o.thin > 0
         c = reshape(chain(1:7+n, k, sel), 7+n, [])';   % rows x P

@@ -32,6 +32,18 @@
 //          zbar, z2, each N_max x 2 x n (column 1 = MS2, 2 = PP7; NaN at unscored points and past a cell's N).
 //          cell: struct with n_obs, lppd, p_waic, elpd_waic (WAIC = -2 x this), chi2 (1 x n), coverage
 //          (numel(levels) x n), dw (2 x n, per dye), levels, kernel_ms and forward_ms.
+//   [pt, chain] = tci_mex('loocheck', h, cells, X, s2[, group[, options]])
+//          PSIS-LOO of every chain and stacking weights across the chains of a group, reduced on the GPU (tci_loocheck;
+//          formulas in include/tci.h): X (32 to 4096 samples) and s2 as for 'fitcheck', one page / column per chain;
+//          group: 1 x n, the 1-based group of every chain (0 = in no group; the chains of a group select one cell), or
+//          []: no groups; options: struct with khat_threshold (> 0), max_iter (>= 1) and tol (>= 0), errors 'tci:opts'.
+//          pt: struct with elpd_loo, lppd, p_loo, khat, each N_max x 2 x n (NaN at unscored points and past a cell's
+//          N; khat Inf: a degenerate tail). chain: struct with n_obs, elpd_loo, p_loo, lppd, khat_max, n_khat_bad,
+//          weight (1 x n; NaN for a chain in no group), elpd_stack, n_points, n_iter (1 x n_groups, n_groups =
+//          max(group)), khat_threshold, kernel_ms and forward_ms. With options.stack = nsample (32 to 4096) 'dram'
+//          attaches both structs' fields as res.stack: the samples are rows round(linspace(1, rows, nsample)) of the
+//          kept rows at or past stats_from (all of them when fewer; res.stack.rows, 1-based among those), and the
+//          chains of one cell form a group (res.stack.group). Needs options.thin >= 1.
 //   tci_mex('destroy', h)
 //   n = tci_mex('device_count')                HIP devices visible to this MATLAB process
 //   [results, chain, s2chain, R] = tci_mex('dram', h, cells, X0, LB, UB, MU, SIG, J0, sigma2[, options])
@@ -104,6 +116,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <set>
 #include <string>
 #include <vector>
@@ -433,6 +446,160 @@ void cmd_fitcheck(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (nlhs > 1) plhs[1] = res; else mxDestroyArray(res);
 }
 
+// ---- 'loocheck': PSIS-LOO per chain and stacking weights per group ---------------------------------
+
+// The outputs of tci_loocheck as MATLAB arrays written in place by the ABI; `merged`: one struct (res.stack of 'dram',
+// the pointwise fields named elpd_loo_i, lppd_i, p_loo_i, khat_i) instead of the two of 'loocheck'.
+struct LooOut {
+  mxArray* pt = nullptr;
+  mxArray* res = nullptr;
+  mxArray* nobs = nullptr;
+  mxArray* nbad = nullptr;
+  mxArray* npts = nullptr;
+  mxArray* nit = nullptr;
+  std::vector<int32_t> n_obs, n_bad, n_points, n_iter;
+  tci_loocheck_outputs out;
+  size_t n, ng;
+  LooOut(size_t nmax, size_t n_, size_t ng_, bool merged) : n_obs(n_), n_bad(n_), n_points(ng_), n_iter(ng_), n(n_), ng(ng_) {
+    static const char* pt_fields[] = {"elpd_loo", "lppd", "p_loo", "khat"};
+    static const char* res_fields[] = {"n_obs", "elpd_loo", "p_loo", "lppd", "khat_max", "n_khat_bad", "weight",
+                                       "elpd_stack", "n_points", "n_iter", "khat_threshold", "kernel_ms", "forward_ms",
+                                       "elpd_loo_i", "lppd_i", "p_loo_i", "khat_i", "group", "rows"};
+    res = mxCreateStructMatrix(1, 1, merged ? 19 : 13, res_fields);
+    pt = merged ? res : mxCreateStructMatrix(1, 1, 4, pt_fields);
+    memset(&out, 0, sizeof out);
+    const mwSize d3[3] = {(mwSize)nmax, 2, (mwSize)n};  // N_max x 2 x n == [chain][dye][N_max]
+    double** ptr[4] = {&out.elpd_loo_i, &out.lppd_i, &out.p_loo_i, &out.khat_i};
+    for (int q = 0; q < 4; ++q) {
+      mxArray* a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+      mxSetField(pt, 0, merged ? res_fields[13 + q] : pt_fields[q], a);
+      *ptr[q] = mxGetPr(a);
+    }
+    double** vp[5] = {&out.elpd_loo, &out.p_loo, &out.lppd, &out.khat_max, &out.weight};
+    const char* vn[5] = {"elpd_loo", "p_loo", "lppd", "khat_max", "weight"};
+    for (int q = 0; q < 5; ++q) {
+      mxArray* a = mxCreateDoubleMatrix(1, n, mxREAL);
+      mxSetField(res, 0, vn[q], a);
+      *vp[q] = mxGetPr(a);
+    }
+    mxArray* es = mxCreateDoubleMatrix(1, ng, mxREAL);
+    mxSetField(res, 0, "elpd_stack", es);
+    out.elpd_stack = mxGetPr(es);
+    mxSetField(res, 0, "n_obs", nobs = mxCreateDoubleMatrix(1, n, mxREAL));
+    mxSetField(res, 0, "n_khat_bad", nbad = mxCreateDoubleMatrix(1, n, mxREAL));
+    mxSetField(res, 0, "n_points", npts = mxCreateDoubleMatrix(1, ng, mxREAL));
+    mxSetField(res, 0, "n_iter", nit = mxCreateDoubleMatrix(1, ng, mxREAL));
+    out.n_obs = n_obs.data();
+    out.n_khat_bad = n_bad.data();
+    out.n_points = n_points.data();
+    out.n_iter = n_iter.data();
+  }
+  void destroy() {
+    if (pt != res) mxDestroyArray(pt);
+    mxDestroyArray(res);
+  }
+  void finish() {
+    for (size_t b = 0; b < n; ++b) {
+      mxGetPr(nobs)[b] = (double)n_obs[b];
+      mxGetPr(nbad)[b] = (double)n_bad[b];
+    }
+    for (size_t g = 0; g < ng; ++g) {
+      mxGetPr(npts)[g] = (double)n_points[g];
+      mxGetPr(nit)[g] = (double)n_iter[g];
+    }
+    mxSetField(res, 0, "khat_threshold", mxCreateDoubleScalar(out.khat_threshold));
+    mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+    mxSetField(res, 0, "forward_ms", mxCreateDoubleScalar(out.forward_ms));
+  }
+};
+
+double opt_num(const mxArray* o, const char* name, double def);
+int64_t opt_int(const mxArray* o, const char* name, int64_t def, int64_t lo);
+
+void cmd_loocheck(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 5 || nrhs > 7)
+    mexErrMsgIdAndTxt("tci:arg", "[pt, chain] = tci_mex('loocheck', h, cells, X, s2[, group[, options]])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const size_t n = mxGetNumberOfElements(prhs[2]);
+  const double* c = doubles(prhs[2], -1, "cells");
+  if (n == 0) mexErrMsgIdAndTxt("tci:arg", "cells must name at least one cell");
+  const double* X = doubles(prhs[3], -1, "X");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[3]);
+  const mwSize* d = mxGetDimensions(prhs[3]);
+  const size_t P = d[0], S = nd > 1 ? d[1] : 1, nx = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || nx != n) mexErrMsgIdAndTxt("tci:arg", "X must be P x S x n: S samples per chain, n = numel(cells)");
+  if (P < 9) mexErrMsgIdAndTxt("tci:arg", "X must have at least 9 rows ([v, tau, ton, MS2_basal, PP7_basal, A, R, dR])");
+  if (S < 32 || S > 4096) mexErrMsgIdAndTxt("tci:arg", "X must hold 32 to 4096 samples per chain (its second dimension)");
+  const double* s2 = doubles(prhs[4], (long long)(S * n), "s2");
+  if (mxGetNumberOfDimensions(prhs[4]) != 2 || mxGetM(prhs[4]) != S)
+    mexErrMsgIdAndTxt("tci:arg", "s2 must be S x n: one sigma2 per column of X");
+  for (size_t i = 0; i < S * n; ++i)
+    if (!(s2[i] > 0.0 && s2[i] <= 1.7976931348623157e308))
+      mexErrMsgIdAndTxt("tci:arg", "s2(%d) must be finite and > 0", (int)i + 1);
+  std::vector<int32_t> cid(n);
+  for (size_t b = 0; b < n; ++b) {
+    if (!(c[b] >= 1 && c[b] <= 2147483647.0) || c[b] != (double)(int64_t)c[b])
+      mexErrMsgIdAndTxt("tci:arg", "cells(%d) must be a positive integer", (int)b + 1);
+    cid[b] = (int32_t)c[b] - 1;
+  }
+  std::vector<int32_t> group;  // 0-based for the ABI; MATLAB's 0 (no group) becomes -1
+  size_t ng = 0;
+  if (nrhs > 5 && mxGetNumberOfElements(prhs[5]) != 0) {  // [] = no groups
+    const double* gp = doubles(prhs[5], (long long)n, "group");
+    group.resize(n);
+    std::vector<int32_t> first(n, -1);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(gp[b] >= 0 && gp[b] <= (double)n) || gp[b] != (double)(int64_t)gp[b])
+        mexErrMsgIdAndTxt("tci:arg", "group(%d) must be an integer in [0, n]", (int)b + 1);
+      group[b] = (int32_t)gp[b] - 1;
+      ng = std::max(ng, (size_t)gp[b]);
+      if (group[b] >= 0) {
+        int32_t& f = first[(size_t)group[b]];
+        if (f < 0) f = cid[b];
+        if (f != cid[b]) mexErrMsgIdAndTxt("tci:arg", "group %d selects more than one cell (chain %d)", (int)gp[b], (int)b + 1);
+      }
+    }
+  }
+  tci_loocheck_options opt;
+  tci_loocheck_defaults(&opt);
+  opt.n_groups = (int64_t)ng;
+  if (nrhs > 6 && !(mxIsDouble(prhs[6]) && mxGetNumberOfElements(prhs[6]) == 0)) {
+    const mxArray* o = prhs[6];
+    if (!mxIsStruct(o) || mxGetNumberOfElements(o) != 1) mexErrMsgIdAndTxt("tci:opts", "options must be a 1x1 struct");
+    for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
+      const char* fn = mxGetFieldNameByNumber(o, f);
+      if (strcmp(fn, "khat_threshold") != 0 && strcmp(fn, "max_iter") != 0 && strcmp(fn, "tol") != 0)
+        mexErrMsgIdAndTxt("tci:opts", "options.%s is not an option of tci_mex('loocheck')", fn);
+    }
+    if (mxGetField(o, 0, "khat_threshold")) {
+      opt.khat_threshold = opt_num(o, "khat_threshold", 0.0);
+      if (!(opt.khat_threshold > 0.0 && opt.khat_threshold <= 1.7976931348623157e308))
+        mexErrMsgIdAndTxt("tci:opts", "options.khat_threshold must be finite and > 0");
+    }
+    opt.max_iter = opt_int(o, "max_iter", opt.max_iter, 1);
+    opt.tol = opt_num(o, "tol", opt.tol);
+    if (!(opt.tol >= 0.0 && opt.tol <= 1.7976931348623157e308)) mexErrMsgIdAndTxt("tci:opts", "options.tol must be finite and >= 0");
+  }
+
+  tci_ctx* ctx = handle_of(prhs[1]);
+  int64_t nmax = 0;
+  for (size_t b = 0; b < n; ++b) {
+    int64_t nb = 0;
+    check(ctx, tci_cell_points(ctx, cid[b], &nb), "tci_cell_points");
+    nmax = std::max(nmax, nb);
+  }
+  LooOut lo((size_t)nmax, n, ng, false);
+  const int rc = tci_loocheck(ctx, &opt, X, (int64_t)P, s2, cid.data(), group.empty() ? nullptr : group.data(), (int64_t)n,
+                              (int64_t)S, nmax, &lo.out);
+  if (rc != TCI_OK) {
+    lo.destroy();
+    check(ctx, rc, "tci_loocheck");
+  }
+  lo.finish();
+  plhs[0] = lo.pt;
+  if (nlhs > 1) plhs[1] = lo.res; else mxDestroyArray(lo.res);
+}
+
 // ---- 'dram': the GPU-resident sampler -------------------------------------------------------
 
 double opt_num(const mxArray* o, const char* name, double def) {
@@ -580,7 +747,8 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"nsimu", "burnintime", "adaptint", "method", "updatesigma", "drscale", "adascale",
                                   "qcovadj", "burnin_scale", "stats_from", "thin", "seed", "engine", "max_chunk",
-                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "verbosity", "waitbar", "printint"};
+                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "verbosity", "waitbar",
+                                  "printint"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
       bool ok = false;
@@ -613,7 +781,16 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   const bool want_chain = nlhs >= 2;
   const int64_t thin = opt_int(o, "thin", 1, 0);
   const bool want_lp = opt_num(o, "logpost", 0.0) != 0.0;
-  opt.thin = want_chain || want_lp ? thin : 0;
+  const int64_t stack = opt_int(o, "stack", 0, 0);  // 0: none; else the sample count of res.stack
+  if (stack != 0 && (stack < 32 || stack > 4096)) mexErrMsgIdAndTxt("tci:opts", "options.stack must be 0 or in [32, 4096]");
+  opt.thin = want_chain || want_lp || stack ? thin : 0;
+  int64_t st_rows = 0, st_k0 = 0;  // the kept rows at or past stats_from, and the first of them
+  if (stack) {
+    if (opt.thin < 1) mexErrMsgIdAndTxt("tci:opts", "options.stack needs the kept rows: options.thin must be >= 1");
+    st_k0 = (opt.stats_from - 1 + opt.thin - 1) / opt.thin;
+    st_rows = (opt.n_steps + opt.thin - 1) / opt.thin - st_k0;
+    if (st_rows < 32) mexErrMsgIdAndTxt("tci:opts", "options.stack: fewer than 32 kept rows at or past options.stats_from");
+  }
   int64_t lp_rows = 0;  // the kept rows at or past stats_from (tci_dram_run_lp refuses a run that keeps none)
   if (want_lp) {
     if (opt.thin < 1) mexErrMsgIdAndTxt("tci:opts", "options.logpost needs the kept rows: options.thin must be >= 1");
@@ -648,8 +825,11 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   tci_ctx* ctx = handle_of(prhs[1]);
   // outputs, written in place: the ABI's row-major [chain][P] is MATLAB's column-major P x n
   static const char* fields[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
-                                 "elapsed_ms", "logpost"};
-  mxArray* res = mxCreateStructMatrix(1, 1, want_lp ? 9 : 8, fields);
+                                 "elapsed_ms", "logpost", "stack"};
+  static const char* fields_st[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
+                                    "elapsed_ms", "stack"};
+  mxArray* res = stack && !want_lp ? mxCreateStructMatrix(1, 1, 9, fields_st)
+                                   : mxCreateStructMatrix(1, 1, 8 + (want_lp ? 1 : 0) + (stack ? 1 : 0), fields);
   mxArray* pn[6];
   for (int k = 0; k < 3; ++k) pn[k] = mxCreateDoubleMatrix(P, n, mxREAL);
   for (int k = 3; k < 6; ++k) pn[k] = mxCreateDoubleMatrix(1, n, mxREAL);
@@ -664,7 +844,14 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   out.sigma_std = mxGetPr(pn[4]);
   out.accept_rate = mxGetPr(pn[5]);
   out.n_evals = nev.data();
-  const size_t n_keep = want_chain && opt.thin > 0 ? (size_t)((opt.n_steps + opt.thin - 1) / opt.thin) : 0;
+  const size_t n_keep = (want_chain || stack) && opt.thin > 0 ? (size_t)((opt.n_steps + opt.thin - 1) / opt.thin) : 0;
+  std::vector<double> st_chain, st_s2;  // the kept rows for res.stack when no chain output takes them
+  if (stack && !want_chain) {
+    st_chain.resize(P * n * n_keep);
+    st_s2.resize(n * n_keep);
+    out.chain = st_chain.data();
+    out.s2chain = st_s2.data();
+  }
   mxArray* ch = nullptr;
   mxArray* s2c = nullptr;
   if (want_chain) {
@@ -709,6 +896,58 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   mxSetField(res, 0, "n_evals", ne);
   mxSetField(res, 0, "elapsed_ms", mxCreateDoubleScalar(out.elapsed_ms));
   if (want_lp) mxSetField(res, 0, "logpost", lo.finish());
+  if (stack) {
+    // the samples: rows round(linspace(0, rows - 1, S)) of the kept rows from st_k0 on (numpy's linspace and
+    // round-half-even), all of them when fewer; the chains of one cell form a group, numbered by first appearance
+    const size_t S = (size_t)std::min(st_rows, stack);
+    std::vector<int64_t> rows(S);
+    const double step = (double)(st_rows - 1) / (double)(S - 1);
+    for (size_t i = 0; i < S; ++i)
+      rows[i] = st_rows <= stack ? (int64_t)i : i + 1 == S ? st_rows - 1 : (int64_t)std::nearbyint((double)i * step);
+    std::vector<double> X(n * S * P), xs2(n * S);
+    for (size_t b = 0; b < n; ++b)
+      for (size_t i = 0; i < S; ++i) {
+        const size_t r = (size_t)(st_k0 + rows[i]);
+        memcpy(&X[(b * S + i) * P], out.chain + (r * n + b) * P, P * sizeof(double));
+        xs2[b * S + i] = out.s2chain[r * n + b];
+      }
+    std::vector<int32_t> group(n, -1), gcell;
+    for (size_t b = 0; b < n; ++b) {
+      for (size_t g = 0; g < gcell.size() && group[b] < 0; ++g)
+        if (gcell[g] == cid[b]) group[b] = (int32_t)g;
+      if (group[b] < 0) {
+        group[b] = (int32_t)gcell.size();
+        gcell.push_back(cid[b]);
+      }
+    }
+    int64_t nmax = 0;
+    for (size_t b = 0; b < n; ++b) {
+      int64_t nb = 0;
+      check(ctx, tci_cell_points(ctx, cid[b], &nb), "tci_cell_points");
+      nmax = std::max(nmax, nb);
+    }
+    tci_loocheck_options lopt;
+    tci_loocheck_defaults(&lopt);
+    lopt.n_groups = (int64_t)gcell.size();
+    LooOut so2((size_t)nmax, n, gcell.size(), true);
+    const int rc2 = tci_loocheck(ctx, &lopt, X.data(), (int64_t)P, xs2.data(), cid.data(), group.data(), (int64_t)n,
+                                 (int64_t)S, nmax, &so2.out);
+    if (rc2 != TCI_OK) {
+      so2.destroy();
+      mxDestroyArray(res);
+      if (ch) mxDestroyArray(ch);
+      if (s2c) mxDestroyArray(s2c);
+      check(ctx, rc2, "tci_loocheck");
+    }
+    so2.finish();
+    mxArray* gm = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t b = 0; b < n; ++b) mxGetPr(gm)[b] = (double)group[b] + 1.0;
+    mxArray* rm = mxCreateDoubleMatrix(1, S, mxREAL);
+    for (size_t i = 0; i < S; ++i) mxGetPr(rm)[i] = (double)rows[i] + 1.0;
+    mxSetField(so2.res, 0, "group", gm);
+    mxSetField(so2.res, 0, "rows", rm);
+    mxSetField(res, 0, "stack", so2.res);
+  }
   plhs[0] = res;
   if (nlhs >= 2) plhs[1] = ch;
   if (nlhs >= 3) plhs[2] = s2c;
@@ -1162,6 +1401,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "dram") cmd_dram(nlhs, plhs, nrhs, prhs);
   else if (cmd == "predict") cmd_predict(nlhs, plhs, nrhs, prhs);
   else if (cmd == "fitcheck") cmd_fitcheck(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "loocheck") cmd_loocheck(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainstats") cmd_chainstats(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chaincov") cmd_chaincov(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainquant") cmd_chainquant(nlhs, plhs, nrhs, prhs);

@@ -161,6 +161,21 @@ class tci_fitcheck_outputs(C.Structure):
                 ("dw", _dp), ("kernel_ms", C.c_double), ("forward_ms", C.c_double)]
 
 
+class tci_loocheck_options(C.Structure):
+    _fields_ = [("scratch_bytes", C.c_int64), ("n_groups", C.c_int64), ("khat_threshold", C.c_double),
+                ("max_iter", C.c_int64), ("tol", C.c_double)]
+
+
+LOOCHECK_POINTWISE = ("elpd_loo_i", "lppd_i", "p_loo_i", "khat_i")
+LOOCHECK_SCALARS = ("elpd_loo", "p_loo", "lppd", "khat_max")
+
+
+class tci_loocheck_outputs(C.Structure):
+    _fields_ = ([(f, _dp) for f in LOOCHECK_POINTWISE] + [("n_obs", _i32p)] + [(f, _dp) for f in LOOCHECK_SCALARS]
+                + [("n_khat_bad", _i32p), ("weight", _dp), ("elpd_stack", _dp), ("n_points", _i32p), ("n_iter", _i32p),
+                   ("khat_threshold", C.c_double), ("kernel_ms", C.c_double), ("forward_ms", C.c_double)])
+
+
 # (name, restype, argtypes) for every symbol declared in include/tci.h
 SIGNATURES = [
     ("tci_construct_by_name", C.c_int, [C.c_char_p, C.POINTER(tci_construct)]),
@@ -223,6 +238,9 @@ SIGNATURES = [
     ("tci_fitcheck_defaults", C.c_int, [C.POINTER(tci_fitcheck_options)]),
     ("tci_fitcheck", C.c_int, [C.c_void_p, C.POINTER(tci_fitcheck_options), _dp, C.c_int64, _dp, _i32p, C.c_int64,
                                C.c_int64, C.c_int64, C.POINTER(tci_fitcheck_outputs)]),
+    ("tci_loocheck_defaults", C.c_int, [C.POINTER(tci_loocheck_options)]),
+    ("tci_loocheck", C.c_int, [C.c_void_p, C.POINTER(tci_loocheck_options), _dp, C.c_int64, _dp, _i32p, _i32p, C.c_int64,
+                               C.c_int64, C.c_int64, C.POINTER(tci_loocheck_outputs)]),
     ("tci_chainlp_defaults", C.c_int, [C.POINTER(tci_chainlp_options)]),
     ("tci_chainlp", C.c_int, [C.c_void_p, C.POINTER(tci_chainlp_options), _dp, _dp, C.c_int64, C.c_int64, C.c_int64,
                               _i32p, _dp, _dp, C.POINTER(tci_chainlp_outputs)]),

@@ -18,7 +18,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = [os.path.join(CSRC, "tci_kernels.hip"), os.path.join(CSRC, "tci_dram.hip"), os.path.join(CSRC, "tci_predict.hip"),
            os.path.join(CSRC, "tci_chainstats.hip"), os.path.join(CSRC, "tci_chaincov.hip"), os.path.join(CSRC, "tci_chainquant.hip"),
            os.path.join(CSRC, "tci_chaindens.hip"), os.path.join(CSRC, "tci_chainrhat.hip"), os.path.join(CSRC, "tci_chainess.hip"),
-           os.path.join(CSRC, "tci_fitcheck.hip"), os.path.join(CSRC, "tci_chainlp.hip"), os.path.join(CSRC, "tci_api.cpp")]
+           os.path.join(CSRC, "tci_fitcheck.hip"), os.path.join(CSRC, "tci_chainlp.hip"), os.path.join(CSRC, "tci_loocheck.hip"),
+           os.path.join(CSRC, "tci_api.cpp")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "tci.h"), os.path.join(CSRC, "tci_internal.h"), os.path.join(CSRC, "tci_diag.h"), os.path.join(CSRC, "tci_tile16.h"), os.path.join(CSRC, "tci_adapt_map.h"),
            os.path.join(CSRC, "tci_dram_internal.h"), os.path.join(CSRC, "tci_eval.h"), os.path.join(CSRC, "tci_csum.h"), os.path.join(CSRC, "tci_key.h"),
            os.path.join(CSRC, "tci_chainrhat_dev.h")]

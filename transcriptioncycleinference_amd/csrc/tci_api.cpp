@@ -792,6 +792,284 @@ int tci_fitcheck(tci_ctx* ctx, const tci_fitcheck_options* opt, const double* th
   return rc;
 }
 
+int tci_loocheck_defaults(tci_loocheck_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  o->scratch_bytes = 0;
+  o->n_groups = 0;
+  o->khat_threshold = 0.0;
+  o->max_iter = 5000;
+  o->tol = 1e-12;
+  return TCI_OK;
+}
+
+namespace {
+
+// The per-chain values of one chain from its pointwise vectors pt = [2][4][ld_out] = per dye elpd_loo, lppd, p_loo,
+// khat (include/tci.h: dye 0 ascending j, then dye 1, over scored points; an unscored point is NaN in all four).
+void loocheck_chain(const double* pt, int64_t ld_out, double thr, int64_t k, tci_loocheck_outputs* out) {
+  const double nan = std::nan("");
+  int32_t n_obs = 0, n_bad = 0;
+  double elpd = 0.0, ploo = 0.0, lppd = 0.0, kmax = -INFINITY;
+  for (int d = 0; d < 2; ++d) {
+    const double* v = pt + (size_t)d * 4 * (size_t)ld_out;
+    for (int64_t j = 0; j < ld_out; ++j) {
+      if (std::isnan(v[3 * ld_out + j])) continue;  // khat of a scored point is a number or +Inf
+      ++n_obs;
+      elpd = elpd + v[j];
+      lppd = lppd + v[ld_out + j];
+      ploo = ploo + v[2 * ld_out + j];
+      const double kh = v[3 * ld_out + j];
+      kmax = kh > kmax ? kh : kmax;
+      if (kh > thr) ++n_bad;
+    }
+  }
+  const bool any = n_obs > 0;
+  if (out->n_obs) out->n_obs[k] = n_obs;
+  if (out->elpd_loo) out->elpd_loo[k] = any ? elpd : nan;
+  if (out->p_loo) out->p_loo[k] = any ? ploo : nan;
+  if (out->lppd) out->lppd[k] = any ? lppd : nan;
+  if (out->khat_max) out->khat_max[k] = any ? kmax : nan;
+  if (out->n_khat_bad) out->n_khat_bad[k] = n_bad;
+}
+
+// The stacking weights of one group (include/tci.h): e[c] = the chain's pointwise elpd_loo, len values each.
+void loocheck_stack(const std::vector<const double*>& e, size_t len, int64_t max_iter, double tol, std::vector<double>* w,
+                    double* elpd_stack, int32_t* n_points, int32_t* n_iter) {
+  const size_t C = e.size();
+  const double nan = std::nan("");
+  std::vector<double> E, mi;  // exp(e_ic - m_i), [n][C], and m_i
+  for (size_t i = 0; i < len; ++i) {
+    bool all = true;
+    double m = -INFINITY;
+    for (size_t c = 0; c < C; ++c) {
+      all = all && std::isfinite(e[c][i]);
+      m = e[c][i] > m ? e[c][i] : m;
+    }
+    if (!all) continue;
+    mi.push_back(m);
+    for (size_t c = 0; c < C; ++c) E.push_back(std::exp(e[c][i] - m));
+  }
+  const size_t n = mi.size();
+  *n_points = (int32_t)n;
+  *n_iter = 0;
+  w->assign(C, nan);
+  *elpd_stack = nan;
+  if (C == 0 || n == 0) return;
+  const double dn = (double)n;
+  std::vector<double> a(C), num(C);
+  std::fill(w->begin(), w->end(), 1.0 / (double)C);
+  if (C == 1) (*w)[0] = 1.0;
+  for (int64_t it = 1; C > 1 && it <= max_iter; ++it) {
+    std::fill(num.begin(), num.end(), 0.0);
+    for (size_t i = 0; i < n; ++i) {
+      double den = 0.0;
+      for (size_t c = 0; c < C; ++c) {
+        a[c] = (*w)[c] * E[i * C + c];
+        den = den + a[c];
+      }
+      for (size_t c = 0; c < C; ++c) num[c] = num[c] + a[c] / den;
+    }
+    double delta = 0.0;
+    for (size_t c = 0; c < C; ++c) {
+      const double wn = num[c] / dn, dw = std::fabs(wn - (*w)[c]);
+      delta = dw > delta ? dw : delta;
+      (*w)[c] = wn;
+    }
+    *n_iter = (int32_t)it;
+    if (delta <= tol) break;
+  }
+  double tot = 0.0;
+  for (size_t i = 0; i < n; ++i) {
+    double den = 0.0;
+    for (size_t c = 0; c < C; ++c) den = den + (*w)[c] * E[i * C + c];
+    tot = tot + (mi[i] + std::log(den));
+  }
+  *elpd_stack = tot;
+}
+
+}  // namespace
+
+int tci_loocheck(tci_ctx* ctx, const tci_loocheck_options* opt, const double* theta, int64_t ld_theta, const double* s2,
+                 const int32_t* cell_id, const int32_t* group, int64_t n_sel, int64_t S, int64_t ld_out,
+                 tci_loocheck_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  tci_loocheck_options o;
+  tci_loocheck_defaults(&o);
+  if (opt) o = *opt;
+  // ---- every check comes before any device work
+  if (!out) return fail(ctx, TCI_EINVAL, "tci_loocheck: out is NULL");
+  if (o.scratch_bytes < 0) return fail(ctx, TCI_EINVAL, "tci_loocheck: scratch_bytes must be >= 0");
+  if (o.n_groups < 0 || o.n_groups > ((int64_t)1 << 31) - 1)
+    return fail(ctx, TCI_EINVAL, "tci_loocheck: n_groups must be in [0, 2^31)");
+  if (o.max_iter < 1) return fail(ctx, TCI_EINVAL, "tci_loocheck: max_iter must be >= 1");
+  if (!(std::isfinite(o.tol) && o.tol >= 0.0)) return fail(ctx, TCI_EINVAL, "tci_loocheck: tol must be finite and >= 0");
+  if (!(std::isfinite(o.khat_threshold) && o.khat_threshold >= 0.0))
+    return fail(ctx, TCI_EINVAL, "tci_loocheck: khat_threshold must be finite and >= 0 (0 = the default)");
+  if (S < 32 || S > 4096) return fail(ctx, TCI_EINVAL, "tci_loocheck: S=" + std::to_string(S) + " must be in [32, 4096]");
+  if (n_sel < 0 || (n_sel > 0 && (!theta || !s2 || !cell_id)))
+    return fail(ctx, TCI_EINVAL, "tci_loocheck: null pointer or negative n_sel");
+  const double thr = o.khat_threshold > 0.0 ? o.khat_threshold : std::min(1.0 - 1.0 / std::log10((double)S), 0.7);
+  int rc = TCI_OK;
+  if (n_sel > 0) {
+    rc = check_rows(ctx, ld_theta, cell_id, n_sel);
+    if (rc != TCI_OK) return rc;
+    for (int64_t k = 0; k < n_sel; ++k)
+      if (ld_out < ctx->meta[(size_t)cell_id[k]].n) return fail(ctx, TCI_ERANGE, "tci_loocheck: ld_out shorter than a cell");
+    if (ld_theta > ((int64_t)1 << 24) || ld_out > ((int64_t)1 << 24))
+      return fail(ctx, TCI_ERANGE, "tci_loocheck: ld_theta / ld_out above 2^24");
+    if (n_sel > ((int64_t)1 << 40) / S) return fail(ctx, TCI_ERANGE, "tci_loocheck: n_sel x S above 2^40");
+    for (int64_t i = 0; i < n_sel * S; ++i)
+      if (!(std::isfinite(s2[i]) && s2[i] > 0.0))
+        return fail(ctx, TCI_EINVAL, "tci_loocheck: s2[" + std::to_string(i) + "] must be finite and > 0");
+  }
+  // the chains of every group, in the order given
+  std::vector<std::vector<int64_t>> members;
+  bool grouped = false;
+  try {
+    members.resize((size_t)o.n_groups);
+    for (int64_t k = 0; group && k < n_sel; ++k) {
+      if (group[k] < -1 || group[k] >= o.n_groups)
+        return fail(ctx, TCI_ERANGE, "tci_loocheck: group[" + std::to_string(k) + "] = " + std::to_string(group[k]) +
+                                         " outside [-1, n_groups)");
+      if (group[k] < 0) continue;
+      std::vector<int64_t>& mem = members[(size_t)group[k]];
+      if (!mem.empty() && cell_id[mem[0]] != cell_id[k])
+        return fail(ctx, TCI_EINVAL, "tci_loocheck: group " + std::to_string(group[k]) + " selects cells " +
+                                         std::to_string(cell_id[mem[0]]) + " and " + std::to_string(cell_id[k]) +
+                                         " (chain " + std::to_string(k) + "): the chains of a group select one cell");
+      mem.push_back(k);
+      grouped = true;
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, "tci_loocheck: host allocation failed");
+  }
+  const int64_t cap = o.scratch_bytes > 0 ? o.scratch_bytes : (int64_t)1 << 30;
+  const int64_t per_cell = 2 * S * ld_out * (int64_t)sizeof(double);  // <= 2^41
+  if (n_sel > 0 && per_cell > cap)
+    return fail(ctx, TCI_EINVAL, "tci_loocheck: one chain needs " + std::to_string(per_cell) +
+                                     " bytes of scratch (2 x S x ld_out doubles), scratch_bytes allows " +
+                                     std::to_string(cap));
+  // the last check is passed: from here on out is written
+  out->khat_threshold = thr;
+  out->kernel_ms = 0.0;
+  out->forward_ms = 0.0;
+  const double nan = std::nan("");
+  for (int64_t k = 0; out->weight && k < n_sel; ++k) out->weight[k] = nan;
+  for (int64_t g = 0; g < o.n_groups; ++g) {
+    if (out->elpd_stack) out->elpd_stack[g] = nan;
+    if (out->n_points) out->n_points[g] = 0;
+    if (out->n_iter) out->n_iter[g] = 0;
+  }
+  if (n_sel == 0) return TCI_OK;
+  int64_t chunk = 0;
+  if (tci::loocheck_max_cells(S, ld_out, &chunk) != TCI_OK)
+    return fail(ctx, TCI_EINVAL, "tci_loocheck: S x ld_out too large for one launch");
+  chunk = std::min(std::min(chunk, cap / per_cell), n_sel);  // whole chains per chunk, at least one
+  const size_t rows_max = (size_t)(chunk * S), cell_out = (size_t)8 * (size_t)ld_out, len = 2 * (size_t)ld_out;
+  std::vector<int32_t> row_cell;
+  std::vector<double> sdlg, pt, elpd_all;
+  try {
+    row_cell.resize(rows_max);
+    sdlg.resize(2 * rows_max);
+    pt.resize((size_t)chunk * cell_out);
+    if (grouped) elpd_all.resize((size_t)n_sel * len);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, "tci_loocheck: host allocation failed");
+  }
+  const double logS = std::log((double)S);
+
+  // ---- device work: per chunk, the forward launch into the scratch, then the reduction over the samples
+  TCI_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = ensure(ctx, &ctx->d_theta, &ctx->cap_theta, rows_max * (size_t)ld_theta)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_cell, &ctx->cap_cell, rows_max)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_sim, &ctx->cap_sim, 2 * rows_max * (size_t)ld_out)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_out0, &ctx->cap_out0, (size_t)chunk * cell_out)) != TCI_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->d_out1, &ctx->cap_out1, 2 * rows_max)) != TCI_OK) return rc;
+  hipStream_t st = ctx->stream;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventCreate(&e2) != hipSuccess) {
+    const hipError_t e = hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return hip_fail(ctx, e, "tci_loocheck: hipEventCreate");
+  }
+  auto body = [&]() -> int {
+    for (int64_t k0 = 0; k0 < n_sel; k0 += chunk) {
+      const int64_t nc = std::min(chunk, n_sel - k0), B = nc * S;
+      for (int64_t k = 0; k < nc; ++k) std::fill_n(row_cell.begin() + k * S, S, cell_id[k0 + k]);
+      for (int64_t i = 0; i < B; ++i) {
+        const double v = s2[k0 * S + i];
+        sdlg[(size_t)i] = std::sqrt(v);
+        sdlg[(size_t)(B + i)] = std::log(6.283185307179586 * v);
+      }
+      double* sim0 = ctx->d_sim;
+      double* sim1 = ctx->d_sim + (size_t)B * (size_t)ld_out;
+      double* d_sd = ctx->d_out1;
+      double* d_lg = ctx->d_out1 + B;
+      TCI_HIP(ctx, hipMemcpyAsync(ctx->d_theta, theta + (size_t)k0 * (size_t)S * (size_t)ld_theta,
+                                  (size_t)B * (size_t)ld_theta * sizeof(double), hipMemcpyHostToDevice, st));
+      TCI_HIP(ctx, hipMemcpyAsync(ctx->d_cell, row_cell.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      TCI_HIP(ctx, hipMemcpyAsync(d_sd, sdlg.data(), 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+      TCI_HIP(ctx, hipEventRecord(e0, st));
+      int r = run(ctx, tci::MODE_FWD_INTERP, ctx->d_theta, ld_theta, ctx->d_cell, nullptr, B, sim0, sim1, ld_out, (void*)st);
+      if (r != TCI_OK) return r;
+      TCI_HIP(ctx, hipEventRecord(e1, st));
+      r = tci::launch_loocheck(ctx->kp, ctx->d_cell, sim0, sim1, d_sd, d_lg, nc, S, ld_out, logS, ctx->d_out0, (void*)st);
+      if (r == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "tci_loocheck: kernel launch");
+      if (r != TCI_OK) return fail(ctx, r, "tci_loocheck: the kernel does not fit a CU's LDS or the grid");
+      TCI_HIP(ctx, hipEventRecord(e2, st));
+      TCI_HIP(ctx, hipMemcpyAsync(pt.data(), ctx->d_out0, (size_t)nc * cell_out * sizeof(double), hipMemcpyDeviceToHost, st));
+      TCI_HIP(ctx, hipStreamSynchronize(st));  // the host vectors and the staging buffers are reused by the next chunk
+      float ms = 0.f;
+      TCI_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+      out->forward_ms += (double)ms;
+      TCI_HIP(ctx, hipEventElapsedTime(&ms, e1, e2));
+      out->kernel_ms += (double)ms;
+      for (int64_t k = 0; k < nc; ++k) {
+        const double* p = pt.data() + (size_t)k * cell_out;
+        double* const dst[4] = {out->elpd_loo_i, out->lppd_i, out->p_loo_i, out->khat_i};
+        for (int q = 0; q < 4; ++q)
+          if (dst[q])
+            for (int d = 0; d < 2; ++d)
+              std::memcpy(dst[q] + ((size_t)(k0 + k) * 2 + d) * (size_t)ld_out, p + ((size_t)d * 4 + q) * (size_t)ld_out,
+                          (size_t)ld_out * sizeof(double));
+        if (grouped)
+          for (int d = 0; d < 2; ++d)
+            std::memcpy(elpd_all.data() + ((size_t)(k0 + k) * 2 + d) * (size_t)ld_out, p + (size_t)d * 4 * (size_t)ld_out,
+                        (size_t)ld_out * sizeof(double));
+        loocheck_chain(p, ld_out, thr, k0 + k, out);
+      }
+    }
+    return TCI_OK;
+  };
+  rc = body();
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipEventDestroy(e2);
+  if (rc != TCI_OK) return rc;
+  try {
+    std::vector<const double*> e;
+    std::vector<double> w;
+    for (int64_t g = 0; g < o.n_groups; ++g) {
+      const std::vector<int64_t>& mem = members[(size_t)g];
+      if (mem.empty()) continue;
+      e.clear();
+      for (int64_t k : mem) e.push_back(elpd_all.data() + (size_t)k * len);
+      double es = nan;
+      int32_t np = 0, ni = 0;
+      loocheck_stack(e, len, o.max_iter, o.tol, &w, &es, &np, &ni);
+      for (size_t c = 0; out->weight && c < mem.size(); ++c) out->weight[mem[c]] = w[c];
+      if (out->elpd_stack) out->elpd_stack[g] = es;
+      if (out->n_points) out->n_points[g] = np;
+      if (out->n_iter) out->n_iter[g] = ni;
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, "tci_loocheck: host allocation failed");
+  }
+  return TCI_OK;
+}
+
 int tci_device_count(int* n_out) {
   if (!n_out) return TCI_EINVAL;
   int n = 0;

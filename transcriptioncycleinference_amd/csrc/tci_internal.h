@@ -101,6 +101,19 @@ int launch_fitcheck(const KParams& kp, const int32_t* row_cell, const double* si
 // The most selected cells one forward + fitcheck launch pair takes (grid limits).
 int fitcheck_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
 
+// PSIS-LOO over samples (tci_loocheck.hip, k_loocheck). Arguments as for launch_fitcheck; 32 <= S <= 4096. out
+// (device): [n_sel][2][4][ld_out] = per dye elpd_loo, lppd, p_loo, khat; unscored points and entries past a cell's N
+// are NaN. TCI_EINVAL when the launch would not fit (grid or LDS), TCI_EHIP on a HIP error.
+constexpr int kLcMaxM = 192;  // the tail length M at S = 4096
+constexpr int kLcMaxG = 43;   // 30 + floor(sqrt(kLcMaxM)): points of the profile likelihood
+int launch_loocheck(const KParams& kp, const int32_t* row_cell, const double* sim0, const double* sim1,
+                    const double* sd, const double* lg, int64_t n_sel, int64_t S, int64_t ld_out, double logS,
+                    double* out, void* stream);
+// The most selected chains one forward + loocheck launch pair takes (grid limits).
+int loocheck_max_cells(int64_t S, int64_t ld_out, int64_t* max_cells);
+// The tail length M and the profile's point count G for S samples (include/tci.h); TCI_EINVAL outside [32, 4096].
+int loocheck_tail(int64_t S, int32_t* M, int32_t* G);
+
 // Chain diagnostics (tci_chainstats.hip) of a device chain [n_rows][n_chains][ld] and, when s2 is not null,
 // of s2 [n_rows][n_chains] as column ld of every chain. npar (device, may be null = ld): columns j >= npar[c]
 // are padding. stats (device): [5][n_chains * (ld + 1)] doubles = mcerr, tau, Geweke z, Geweke p and the

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import math
 from typing import Optional, Sequence
 
 import numpy as np
@@ -336,6 +337,65 @@ class FitCheck:
                                          P(self.elpd_waic), P(self.chi2), P(self.coverage), P(self.dw), 0.0, 0.0)
 
 
+def loocheck_tail(S: int):
+    """The tail length ``M = min(floor(S / 5), ceil(3 sqrt(S)))`` and the profile's point count
+    ``G = 30 + floor(sqrt(M))`` of ``tci_loocheck`` for ``S`` samples; ValueError outside [32, 4096]."""
+    S = int(S)
+    if not 32 <= S <= 4096:
+        raise ValueError(f"S = {S} must be in [32, 4096]")
+    M = min(S // 5, int(math.ceil(3.0 * math.sqrt(float(S)))))
+    return M, 30 + int(math.floor(math.sqrt(float(M))))
+
+
+def loocheck_threshold(S: int) -> float:
+    """The default ``khat_threshold`` for ``S`` samples: ``min(1 - 1 / log10(S), 0.7)``."""
+    return min(1.0 - 1.0 / math.log10(float(S)), 0.7)
+
+
+@dataclasses.dataclass
+class LooCheck:
+    """PSIS-LOO per chain and stacking weights per group (``tci_loocheck_outputs``; formulas in ``include/tci.h``).
+    Pointwise, each ``[n_sel, 2, ld_out]`` with dye 0 = MS2 and 1 = PP7, NaN at unscored points and past a cell's N:
+    ``elpd_loo_i``, ``lppd_i``, ``p_loo_i``, ``khat_i`` (+Inf: a degenerate tail). Per chain ``[n_sel]``: ``n_obs``,
+    ``n_khat_bad`` (int32), ``elpd_loo``, ``p_loo``, ``lppd``, ``khat_max``, and ``weight`` (NaN for a chain in no
+    group). Per group ``[n_groups]``: ``elpd_stack``, ``n_points``, ``n_iter`` (int32)."""
+
+    elpd_loo_i: np.ndarray
+    lppd_i: np.ndarray
+    p_loo_i: np.ndarray
+    khat_i: np.ndarray
+    n_obs: np.ndarray
+    elpd_loo: np.ndarray
+    p_loo: np.ndarray
+    lppd: np.ndarray
+    khat_max: np.ndarray
+    n_khat_bad: np.ndarray
+    weight: np.ndarray
+    elpd_stack: np.ndarray
+    n_points: np.ndarray
+    n_iter: np.ndarray
+    n_samples: int = 0
+    khat_threshold: float = float("nan")
+    kernel_ms: float = 0.0    # device time of the loocheck kernel
+    forward_ms: float = 0.0   # device time of the forward launches before it
+
+    @classmethod
+    def empty(cls, n: int, ld_out: int, n_groups: int = 0, n_samples: int = 0) -> "LooCheck":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        z = lambda m: np.zeros(m, np.int32)  # noqa: E731
+        g = int(n_groups)
+        return cls(*[d(n, 2, ld_out) for _ in _lib.LOOCHECK_POINTWISE], z(n), *[d(n) for _ in _lib.LOOCHECK_SCALARS],
+                   z(n), d(n), d(g), z(g), z(g), int(n_samples))
+
+    def to_c(self) -> "_lib.tci_loocheck_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        I = lambda a: _lib.ptr(a, _lib._i32p)  # noqa: E731,E741
+        return _lib.tci_loocheck_outputs(*[P(getattr(self, f)) for f in _lib.LOOCHECK_POINTWISE], I(self.n_obs),
+                                         *[P(getattr(self, f)) for f in _lib.LOOCHECK_SCALARS], I(self.n_khat_bad),
+                                         P(self.weight), P(self.elpd_stack), I(self.n_points), I(self.n_iter),
+                                         0.0, 0.0, 0.0)
+
+
 @dataclasses.dataclass
 class ChainLp:
     """Log-posterior trace, best sample and DIC of every chain (``tci_chainlp_outputs``; formulas in
@@ -553,6 +613,58 @@ class Likelihood:
                                            _lib.ptr(cid, _lib._i32p), n_sel, S, ld_out, C.byref(out)))
         fc.kernel_ms, fc.forward_ms = float(out.kernel_ms), float(out.forward_ms)
         return fc
+
+    def loocheck(self, theta: np.ndarray, s2: np.ndarray, cell_id: Sequence[int], group=None,
+                 khat_threshold: Optional[float] = None, max_iter: int = 5000, tol: float = 1e-12,
+                 scratch_bytes: int = 0) -> LooCheck:
+        """PSIS-LOO of every selected chain and stacking weights across the chains of a group, reduced on the device
+        (``tci_loocheck``; formulas in ``include/tci.h``). ``theta``, ``s2`` and ``cell_id`` as in :meth:`fitcheck`,
+        one entry per selected chain, with 32 <= S <= 4096. ``group``: None (no groups) or one integer id per chain,
+        -1 = no group; the chains of a group must select one cell and get the simplex ``weight`` that maximises the
+        stacked leave-one-out density. ``khat_threshold``: the Pareto k above which a point counts into
+        ``n_khat_bad`` (None: ``min(1 - 1 / log10(S), 0.7)``); ``max_iter``, ``tol``: the stopping rule of the
+        weight iteration. Returns a :class:`LooCheck`."""
+        theta = np.ascontiguousarray(theta, np.float64)
+        if theta.ndim != 3:
+            raise ValueError("theta must be [n_sel, S, ld]: S posterior samples per selected chain")
+        cid = np.ascontiguousarray(cell_id, np.int32)
+        n_sel, S, ld = theta.shape
+        if cid.shape != (n_sel,):
+            raise ValueError("cell_id must have one entry per selected chain (theta.shape[0])")
+        s2 = np.ascontiguousarray(s2, np.float64)
+        if s2.shape != (n_sel, S):
+            raise ValueError("s2 must be [n_sel, S]: one sigma2 per theta row")
+        if not np.all(np.isfinite(s2) & (s2 > 0)):
+            raise ValueError("s2 must be finite and > 0")
+        if not 32 <= S <= 4096:
+            raise ValueError(f"S = theta.shape[1] = {S} must be in [32, 4096]")
+        if int(scratch_bytes) < 0:
+            raise ValueError("scratch_bytes must be >= 0")
+        if int(max_iter) != max_iter or int(max_iter) < 1:
+            raise ValueError("max_iter must be an integer >= 1")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("tol must be finite and >= 0")
+        if khat_threshold is not None and not (np.isfinite(khat_threshold) and khat_threshold > 0):
+            raise ValueError("khat_threshold must be finite and > 0")
+        if n_sel and (cid.min() < 0 or cid.max() >= len(self.lengths)):
+            raise ValueError("cell_id out of range")
+        g, n_groups = None, 0
+        if group is not None and n_sel:
+            g, n_groups = rhat_groups(group, n_sel)
+            for k in np.unique(g[g >= 0]):
+                if len(np.unique(cid[g == k])) > 1:
+                    raise ValueError(f"group {int(k)} selects more than one cell")
+        ld_out = int(self.lengths[cid].max()) if n_sel else 1
+        lc = LooCheck.empty(n_sel, ld_out, n_groups, S)
+        opt = _lib.tci_loocheck_options(int(scratch_bytes), n_groups, 0.0 if khat_threshold is None else
+                                        float(khat_threshold), int(max_iter), float(tol))
+        out = lc.to_c()
+        self._check(self._lib.tci_loocheck(self._h, C.byref(opt), _lib.ptr(theta, _lib._dp), ld, _lib.ptr(s2, _lib._dp),
+                                           _lib.ptr(cid, _lib._i32p), _lib.ptr(g, _lib._i32p), n_sel, S, ld_out,
+                                           C.byref(out)))
+        lc.khat_threshold = float(out.khat_threshold)
+        lc.kernel_ms, lc.forward_ms = float(out.kernel_ms), float(out.forward_ms)
+        return lc
 
     def chainstats(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, max_lag: int = 0):
         """Convergence diagnostics of a chain held on the host (mcmcstat's ``chainstats``), reduced

@@ -75,6 +75,12 @@ LP_SCALARS = _lib.CHAINLP_SCALARS
 LP_FIELDS = (LP_SCALARS + ("best_row",) + tuple("best_" + s for s in _SCALARS) + ("best_dR", "ss", "lp", "n_rows",
                                                                                   "n_chains", "cell_index"))
 LP_GROUP_FIELDS = ("lp_rhat", "lp_rhat_split", "lp_ess", "lp_mcse", "ss_gap", "best_replicate")
+# MCMCstack (fit(..., stack=nsample)): PSIS-LOO of every replicate of a fitted cell and the stacking weights across them
+# (include/tci.h, tci_loocheck): weights [M]; per replicate [M] elpd_loo, p_loo, khat_max, n_khat_bad; replicate 0's
+# pointwise elpd_loo_i and khat_i [2, N]; elpd_stack; stacked_mean [7 + N] = sum_r weights_r * (replicate r's posterior
+# mean).
+STACK_FIELDS = ("weights", "elpd_loo", "p_loo", "khat_max", "n_khat_bad", "elpd_loo_i", "khat_i", "elpd_stack",
+                "stacked_mean", "n_samples", "cell_index")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -338,6 +344,7 @@ class FitResult:
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
     MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
+    MCMCstack: Optional[List[Dict]] = None     # fit(..., stack=nsample): STACK_FIELDS per fitted cell
     MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
     MCMCess: Optional[List[Dict]] = None       # fit(..., replicates=M, ess=True): ESS_FIELDS per fitted cell
     MCMCrhat: Optional[List[Dict]] = None      # fit(..., replicates=M): RHAT_FIELDS per fitted cell
@@ -455,7 +462,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         v0=None, approved=None, thin: int = 0, cells: Optional[Sequence[int]] = None,
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
-        rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False) -> FitResult:
+        rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False,
+        stack: Optional[int] = None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -515,7 +523,14 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     replicate's values and ``LP_GROUP_FIELDS``: R-hat, ESS and MCSE of ``lp`` across the replicates (the ``lp__``
     diagnostic), ``ss_gap`` and ``best_replicate``: whether replicates that disagree sit at different SS levels. The
     priors :func:`plan_fit` builds always pass the check ``dram_run(..., logpost=True)`` makes on them (a
-    ``ratePriorWidth`` that is NaN or <= 0 does not: such a fit runs without ``logpost`` and is refused with it)."""
+    ``ratePriorWidth`` that is NaN or <= 0 does not: such a fit runs without ``logpost`` and is refused with it).
+
+    ``stack``: a sample count in [32, 4096]: also ``MCMCstack``, one dict of ``STACK_FIELDS`` per fitted cell (needs
+    ``thin >= 1`` and at least 32 kept post-burn-in rows): the PSIS-LOO expected log predictive density and Pareto k
+    of every replicate over :func:`predict_rows` of its kept rows, and the weights across the cell's replicates that
+    maximise the stacked leave-one-out density (``Likelihood.loocheck``, on the device; :func:`stack_entries`):
+    the estimate for replicates that do not mix. ``replicates=1`` gives the LOO values alone, with weight 1. Nothing
+    else in the result changes."""
     M = int(replicates)
     if M != replicates or M < 1:
         raise ValueError("replicates must be an integer >= 1")
@@ -527,6 +542,11 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         raise ValueError("MCMCess is reduced with MCMCrhat: ess=True needs replicates > 1 or rhat=True")
     if logpost and int(thin) < 1:
         raise ValueError("MCMClp is reduced from the kept rows: logpost=True needs thin >= 1")
+    if stack is not None:
+        if isinstance(stack, bool) or int(stack) != stack or not 32 <= int(stack) <= 4096:
+            raise ValueError("stack must be an integer sample count in [32, 4096]")
+        if int(thin) < 1:
+            raise ValueError("MCMCstack is reduced from the kept rows: stack=nsample needs thin >= 1")
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
@@ -602,10 +622,41 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     if res.lp is not None:
         grp = lp_group_stats(lk, res.lp, K, M, max_lag) if M > 1 else None
         lps = [lp_entry(res.lp, k, int(cl.lengths[c]), off + c + 1, K, M, grp) for k, c in enumerate(keep)]
+    stk = None
+    if stack is not None:
+        rows_idx = 1 + int(thin) * np.arange(res.chain.shape[0])
+        stk = stack_entries(lk, res.chain[rows_idx >= max(n_burn, 1)], res.s2chain, res.mean, keep, M, int(stack), off)
     return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
                      res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMClp=lps, MCMCess=es,
-                     MCMCrhat=rh,
+                     MCMCrhat=rh, MCMCstack=stk,
                      MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+
+
+def stack_entries(lk, chain: np.ndarray, s2chain: np.ndarray, mean: np.ndarray, keep: Sequence[int], M: int,
+                  nsample: int, cell_offset: int = 0, scratch_bytes: int = 0) -> List[Dict]:
+    """``MCMCstack`` of a fit: ``chain`` ``[rows, M * K, ld]`` holds the post-burn-in kept rows of the ``M`` replicates
+    of the ``K = len(keep)`` fitted cells (replicate-major, as :func:`fit` orders them), ``s2chain`` ``[>= rows, M * K]``
+    every kept row's sigma2 (a row's sigma2 is among the last ``rows`` entries, as in :func:`fitcheck`) and ``mean``
+    ``[M * K, ld]`` the chains' posterior means. :func:`predict_rows` of every chain go through ``Likelihood.loocheck``
+    in one call, cell ``k``'s replicates as group ``k``."""
+    K, rows = len(keep), chain.shape[0]
+    idx = predict_rows(rows, nsample)
+    if len(idx) < 32:
+        raise ValueError(f"stack needs at least 32 kept post-burn-in rows and this fit kept {rows}")
+    theta = np.ascontiguousarray(np.transpose(chain[idx], (1, 0, 2)))
+    s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64)[s2chain.shape[0] - rows:][idx].T)
+    cid = np.tile(np.array(keep, np.int32), M)
+    lc = lk.loocheck(theta, s2, cid, group=np.tile(np.arange(K, dtype=np.int32), M), scratch_bytes=scratch_bytes)
+    out = []
+    for k, c in enumerate(keep):
+        n = int(lk.cells.lengths[c])
+        w = lc.weight[k::K].copy()
+        d = {f: getattr(lc, f)[k::K].copy() for f in ("elpd_loo", "p_loo", "khat_max", "n_khat_bad")}
+        d.update(weights=w, elpd_loo_i=lc.elpd_loo_i[k, :, :n].copy(), khat_i=lc.khat_i[k, :, :n].copy(),
+                 elpd_stack=float(lc.elpd_stack[k]), stacked_mean=w @ mean[k::K, :7 + n], n_samples=int(lc.n_samples),
+                 cell_index=int(cell_offset) + c + 1)
+        out.append({f: d[f] for f in STACK_FIELDS})
+    return out
 
 
 def lp_group_stats(lk, clp: ChainLp, K: int, M: int, max_lag: int = 0) -> Dict[str, np.ndarray]:
@@ -907,6 +958,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
     if fit_result.MCMClp is not None:  # only a fit with logpost=True
         lp_fields = LP_FIELDS + (LP_GROUP_FIELDS if any("lp_rhat" in e for e in fit_result.MCMClp) else ())
         variables["MCMClp"] = _struct_array(fit_result.MCMClp, lp_fields)
+    if fit_result.MCMCstack is not None:  # only a fit with stack=nsample
+        variables["MCMCstack"] = _struct_array(fit_result.MCMCstack, STACK_FIELDS)
     if fit_result.MCMCcheck is not None:  # only after fitcheck()
         variables["MCMCcheck"] = _struct_array(fit_result.MCMCcheck, CHECK_FIELDS)
     sio.savemat(base + ".mat", variables)
