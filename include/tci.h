@@ -895,6 +895,65 @@ int tci_dram_run_lp(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains,
                     const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
                     tci_chainess_outputs* eout, const tci_chainlp_options* lopt, tci_chainlp_outputs* lout);
 
+/* ---- Parallel tempering: a ladder of chains per cell that exchange states on the device ----
+ * Replica exchange (Swendsen and Wang 1986; Geyer 1991) for chains that do not mix. A ladder is a set of chains of one
+ * cell, its rungs in ascending chain index, at inverse temperatures 1 >= beta_0 > beta_1 > ... . A rung with inverse
+ * temperature beta samples the posterior with the likelihood alone tempered,
+ *   pi_beta(theta, sigma2) ~ [ (2 pi sigma2)^(-N/2) exp(-ss(theta) / (2 sigma2)) ]^beta * (1 / sigma2) * prior(theta),
+ * N = 2 N_c the chain's observation count; the theta prior and the implicit 1 / sigma2 prior are not tempered. Its
+ * theta-conditional is the plain acceptance rule with 1 / sigma2 replaced by beta / sigma2 and its sigma2-conditional
+ * 1 / sigma2 ~ Gamma(beta N / 2, scale 2 / (beta ss)). The sampler holds s2t = sigma2 / beta for such a rung: every
+ * acceptance is then the plain sampler's, and the Gibbs draw is 1 / s2t ~ Gamma(beta N / 2, scale 2 / ss).
+ *   UNITS. sigma2_0 is passed physical and stored as sigma2_0 / beta. Every s2 OUTPUT of a rung with beta < 1 is in
+ *   s2t = sigma2 / beta: s2chain, sigma_mean, sigma_std and the s2 columns of every reduction. The cold rung (beta = 1)
+ *   is physical, and it is the posterior sample.
+ * Swaps. The chain rows are cut into windows of `win` rows (adaptint, or 100 without adaptation). After the row
+ * s = w * win that ends window w has been logged and adapted, and only when s < n_steps (never after the run's last
+ * row), neighbouring rungs exchange states when w % swap_every == 0: event e = w / swap_every - 1 tries the pairs
+ * (r, r + 1) of every ladder with r congruent to w / swap_every modulo 2, so a ladder with an odd rung count leaves one
+ * rung idle each time. For a = rung r and b = rung r + 1, with the physical sigma2_x = beta_x * s2t_x and
+ *   dev_x = ss_x / sigma2_x + nobs * log(6.283185307179586 * sigma2_x)     (tci_chainlp's dev, the same operations)
+ *   logr  = (0.5 * (beta_a - beta_b)) * (dev_a - dev_b)
+ * the swap is accepted iff u < exp(logr), u the uniform of stream (seed, chain_keys[a], row s, purpose 6); a logr that
+ * is not finite is rejected. On accept theta, ss and the prior SS change places; with updatesigma = 1 the physical
+ * sigma2 does too (s2t_a = (beta_b * s2t_b) / beta_a, s2t_b = (beta_a * s2t_a_old) / beta_b); with updatesigma = 0
+ * sigma2 is a constant of the model and stays. The adaptation state (covariance, mean, proposal factor, window,
+ * counters: accept_rate and n_evals) stays with the rung. Every engine gives the same bits.
+ * A call whose beta are all 1 and that never swaps, and any chain with ladder = -1 and beta = 1, has tci_dram_run's bits.
+ * Checked before any device work (TCI_EINVAL, the ladder or chain named in the message): beta finite and in (0, 1];
+ * with updatesigma = 1, beta * N / 2 >= 1 (the Gamma sampler's range); ladder values in [-1, n_ladders); beta strictly decreasing along a
+ * ladder; all rungs of a ladder with the same cell, lower, upper, prior_mu and prior_sig; with updatesigma = 0 the same
+ * sigma2_0; swap_every >= 0 (0: never swap); flags == 0. */
+typedef struct {
+  const double* beta;    /* [n_chains]; NULL: 1 for every chain */
+  const int32_t* ladder; /* [n_chains], -1: in no ladder; NULL: -1 for every chain */
+  int64_t n_ladders;
+  int64_t swap_every;
+  int64_t flags;         /* reserved, must be 0 */
+} tci_temper_options;
+
+/* Host buffers (any pointer may be NULL). swap_tried / swap_accepted count at the lower rung of a pair (0 elsewhere).
+ * The logs have one row per swap event, at most swap_log_rows of them are written (events past it are counted only):
+ * swap_logr is logr at the lower rung of every pair tried and NaN elsewhere, swap_acc 1 where the swap was accepted. */
+typedef struct {
+  int32_t *swap_tried, *swap_accepted; /* [n_chains] */
+  double* swap_logr;                   /* [swap_log_rows][n_chains] */
+  uint8_t* swap_acc;                   /* [swap_log_rows][n_chains] */
+  int64_t swap_log_rows;               /* rows the two logs hold (the caller's) */
+  int64_t n_events;                    /* written: swap events of the run */
+} tci_temper_outputs;
+
+int tci_temper_defaults(tci_temper_options* opt); /* no ladders, swap_every = 1 */
+
+/* tci_dram_run_rhat with the ladder added: red, group, ropt and rout as there, but rout may be NULL (then group,
+ * n_groups and ropt are ignored and no group reduction runs). topt NULL is tci_temper_defaults; tout may be NULL. */
+int tci_dram_run_tempered(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                          const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                          const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                          tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                          const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_temper_options* topt,
+                          tci_temper_outputs* tout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -45,6 +45,14 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack] = tci_f
 %        p_loo, khat_max, n_khat_bad, the stacking weights (1 for the one chain a cell has here), elpd_stack,
 %        n_samples and cell_index, over rows round(linspace(1, rows, nsample)) of the post-burn-in rows kept, on the
 %        device (tci_mex('dram') options.stack; formulas in include/tci.h). Needs 'thin' > 0 and 32 such rows.)
+%     'temper' (1; R > 1 runs a ladder of R chains per cell at inverse temperatures beta_r = q^r,
+%        q = 1/(1 + sqrt(2/(7 + N))), whose neighbouring rungs exchange states after every 'swap_every'-th (1)
+%        adaptation window on the device (parallel tempering: tci_mex('dram') options.temper; include/tci.h). Chain
+%        column r*nc + k is rung r of fitted cell k: the cold rungs (beta = 1) come first and every other output is
+%        theirs; a hot rung starts from its own draw of x0 and runs on RNG stream cellNum - 1 + r*2^24. Fills the
+%        seventh output MCMCtemper, one entry per fitted cell: beta (1 x R), swap_rate and swap_tried (1 x R-1, per
+%        pair of neighbouring rungs; NaN for a pair never tried), accept_rate (1 x R), swap_every, n_events, cell_index.
+%        Not with 'logpost' or 'stack'.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -74,6 +82,8 @@ p.addParameter('predict', 0);
 p.addParameter('diagnostics', 0);
 p.addParameter('logpost', 0);
 p.addParameter('stack', 0);
+p.addParameter('temper', 1);
+p.addParameter('swap_every', 1);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -172,11 +182,44 @@ for k = 1:nc
     SIG(1:m, k) = setup(k).sig;
     J0(1:m, k) = setup(k).J0;
 end
+R = o.temper;
+if ~(isscalar(R) && R >= 1 && R == floor(R) && R <= 256)
+    error('tci:temper', 'temper must be an integer rung count in [1, 256]');
+end
+if R > 1 && (o.logpost || o.stack)
+    error('tci:temper', 'temper > 1 cannot be combined with logpost or stack');
+end
+keys = [setup.cellNum] - 1;
+cols = 1:nc;
+if R > 1                                            % the hot rungs: columns r*nc + k, their own x0
+    temper = [ones(1, nc*R); repmat(1:nc, 1, R)];
+    for r = 1:R-1
+        for k = 1:nc
+            n = numel(setup(k).t);
+            c = r*nc + k;
+            x = setup(k).x0;
+            if ~loadPrevious
+                x(1) = 1+2*rand;
+            end
+            x(3) = 4*rand; x(6) = rand; x(2) = 4*rand; x(8:end) = normrnd(0,3,1,n);
+            X0(:, c) = 0; X0(1:7+n, c) = x;
+            LB(:, c) = LB(:, k); UB(:, c) = UB(:, k); MU(:, c) = MU(:, k); SIG(:, c) = SIG(:, k); J0(:, c) = J0(:, k);
+            temper(1, c) = (1/(1 + sqrt(2/(7 + n))))^r;
+        end
+    end
+    keys = repmat(keys, 1, R) + kron(0:R-1, 2^24*ones(1, nc));
+    cols = repmat(1:nc, 1, R);
+end
 sigma2_0 = 1;                                       % :212, :259
 options = struct('nsimu', n_steps, 'burnintime', n_burn, 'adaptint', 100, 'method', 'dram', ...  % :263-270
     'updatesigma', 1, 'verbosity', 0, 'stats_from', max(n_burn, 1), 'thin', o.thin, ...
     'seed', o.seed*1000003 + 20201028, 'engine', o.engine, 'adapt_pmax', o.adapt_pmax, ...
-    'chain_keys', [setup.cellNum] - 1);
+    'chain_keys', keys);
+MCMCtemper = struct([]);
+if R > 1
+    options.temper = temper;
+    options.swap_every = o.swap_every;
+end
 MCMCdiag = struct([]);
 MCMClp = struct([]);
 if o.logpost && o.thin <= 0
@@ -196,15 +239,15 @@ if o.diagnostics && o.thin <= 0
     error('tci:diagnostics', 'the diagnostics need the kept chain rows: thin > 0');
 end
 if o.diagnostics
-    [results, chain, s2chain, ~, stats] = tci_mex('dram', h, 1:nc, X0, LB, UB, MU, SIG, J0, sigma2_0, options);
+    [results, chain, s2chain, ~, stats] = tci_mex('dram', h, cols, X0, LB, UB, MU, SIG, J0, sigma2_0, options);
     rows = 1 + o.thin*(0:size(chain, 3)-1);
     sel = rows >= max(n_burn, 1);
 elseif o.thin > 0
-    [results, chain, s2chain] = tci_mex('dram', h, 1:nc, X0, LB, UB, MU, SIG, J0, sigma2_0, options);  % :273
+    [results, chain, s2chain] = tci_mex('dram', h, cols, X0, LB, UB, MU, SIG, J0, sigma2_0, options);  % :273
     rows = 1 + o.thin*(0:size(chain, 3)-1);         % chain rows kept: 1, 1+thin, ...
     sel = rows >= max(n_burn, 1);                   % chain(n_burn:end, :) (:276-283)
 else
-    results = tci_mex('dram', h, 1:nc, X0, LB, UB, MU, SIG, J0, sigma2_0, options);
+    results = tci_mex('dram', h, cols, X0, LB, UB, MU, SIG, J0, sigma2_0, options);
 end
 
 % ---- predictive bands: the same sample rows for every cell, one call (mcmcpred, deterministic rows) --
@@ -291,6 +334,14 @@ for k = 1:nc
             'stacked_mean', T.weight(k)*results.mean(1:7+n, k)', 'n_samples', numel(T.rows), ...
             'cell_index', setup(k).cellNum);
         if isempty(MCMCstack), MCMCstack = sk; else, MCMCstack(k) = sk; end
+    end
+    if R > 1
+        T = results.temper;
+        rungs = k + nc*(0:R-1);
+        tk = struct('beta', T.beta(rungs), 'swap_rate', T.swap_accepted(rungs(1:end-1)) ./ T.swap_tried(rungs(1:end-1)), ...
+            'swap_tried', T.swap_tried(rungs(1:end-1)), 'accept_rate', results.accept_rate(rungs), ...
+            'swap_every', T.swap_every, 'n_events', T.n_events, 'cell_index', setup(k).cellNum);
+        if isempty(MCMCtemper), MCMCtemper = tk; else, MCMCtemper(k) = tk; end
     end
     if o.thin > 0
         c = reshape(chain(1:7+n, k, sel), 7+n, [])';   % rows x P

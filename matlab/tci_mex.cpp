@@ -108,6 +108,13 @@
 //          NaN), theta_best, theta_mean (P x n; NaN past a chain's 7 + N), n_rows and kernel_ms. With
 //          options.logpost = true 'dram' attaches the same struct, of the kept rows at or past stats_from, to its
 //          first output as res.logpost (the rows are kept on the device for it even when no chain output is asked for).
+//   options.temper of 'dram': parallel tempering (tci_dram_run_tempered, include/tci.h). A 2 x n matrix [beta; ladder]
+//          (ladder ids 1-based, 0 = the chain is in no ladder; the chains of a ladder in column order are its rungs,
+//          cold first) or 1 x n (beta alone); options.swap_every (1; 0 = never) is the number of adaptation windows
+//          between swaps. sigma2 is passed physical; every s2 output of a rung with beta < 1 is sigma2 / beta. Attaches
+//          res.temper: beta, ladder, swap_tried, swap_accepted (1 x n, at the lower rung of a pair), swap_logr and
+//          swap_acc (n x n_events; NaN / 0 where no pair was tried), event_rows (1 x n_events, the 1-based chain row
+//          every event follows), swap_every and n_events. Not with options.logpost.
 // Errors are raised with mexErrMsgIdAndTxt('tci:...'), carrying tci_last_error().
 // Every argument's class and size is checked before a pointer reaches the C ABI. Live contexts
 // are tracked; a handle that this MEX file did not create (or already destroyed) is rejected,
@@ -747,7 +754,8 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"nsimu", "burnintime", "adaptint", "method", "updatesigma", "drscale", "adascale",
                                   "qcovadj", "burnin_scale", "stats_from", "thin", "seed", "engine", "max_chunk",
-                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "verbosity", "waitbar",
+                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "temper", "swap_every", "verbosity",
+                                  "waitbar",
                                   "printint"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
@@ -797,6 +805,41 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     lp_rows = (opt.n_steps + opt.thin - 1) / opt.thin - (opt.stats_from - 1 + opt.thin - 1) / opt.thin;
     if (lp_rows < 1) mexErrMsgIdAndTxt("tci:opts", "options.logpost: no kept row at or past options.stats_from");
   }
+  // options.temper: parallel tempering (tci_dram_run_tempered). A 2 x n matrix [beta; ladder], the ladder ids 1-based
+  // and 0 for a chain in no ladder, or 1 x n (beta alone: no ladders, no swaps); the chains of a ladder in column
+  // order are its rungs, cold first. options.swap_every (default 1; 0 = never): swaps after every swap_every-th
+  // window of adaptint rows.
+  std::vector<double> t_beta;
+  std::vector<int32_t> t_ladder;
+  const mxArray* tm = o ? mxGetField(o, 0, "temper") : nullptr;
+  const bool want_temper = tm != nullptr && mxGetNumberOfElements(tm) != 0;
+  tci_temper_options topt;
+  tci_temper_defaults(&topt);
+  topt.swap_every = opt_int(o, "swap_every", 1, 0);
+  if (want_temper) {
+    if (!mxIsDouble(tm) || mxIsComplex(tm) || mxGetNumberOfDimensions(tm) != 2 || mxGetN(tm) != n ||
+        (mxGetM(tm) != 1 && mxGetM(tm) != 2))
+      mexErrMsgIdAndTxt("tci:opts", "options.temper must be a real double 2 x n matrix [beta; ladder] (or 1 x n: beta)");
+    if (want_lp) mexErrMsgIdAndTxt("tci:opts", "options.temper cannot be combined with options.logpost");
+    const size_t tr = mxGetM(tm);
+    const double* tv = mxGetPr(tm);
+    t_beta.resize(n);
+    t_ladder.assign(n, -1);
+    int32_t lmax = -1;
+    for (size_t b = 0; b < n; ++b) {
+      t_beta[b] = tv[b * tr];
+      if (tr == 2) {
+        const double l = tv[b * tr + 1];
+        if (!(l >= 0 && l <= 2147483647.0) || l != (double)(int64_t)l)
+          mexErrMsgIdAndTxt("tci:opts", "options.temper(2, %d) must be a ladder number >= 1, or 0 for none", (int)b + 1);
+        t_ladder[b] = (int32_t)l - 1;
+        lmax = std::max(lmax, t_ladder[b]);
+      }
+    }
+    topt.beta = t_beta.data();
+    topt.ladder = t_ladder.data();
+    topt.n_ladders = (int64_t)lmax + 1;
+  }
   opt.seed = (uint64_t)opt_int(o, "seed", (int64_t)opt.seed, 0);
   const std::string engine = opt_str(o, "engine", "auto");
   if (engine == "auto") opt.engine = TCI_DRAM_AUTO;
@@ -826,9 +869,12 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   // outputs, written in place: the ABI's row-major [chain][P] is MATLAB's column-major P x n
   static const char* fields[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
                                  "elapsed_ms", "logpost", "stack"};
+  static const char* fields_tm[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
+                                    "elapsed_ms", "temper", "stack"};
   static const char* fields_st[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
                                     "elapsed_ms", "stack"};
-  mxArray* res = stack && !want_lp ? mxCreateStructMatrix(1, 1, 9, fields_st)
+  mxArray* res = want_temper       ? mxCreateStructMatrix(1, 1, 9 + (stack ? 1 : 0), fields_tm)
+                 : stack && !want_lp ? mxCreateStructMatrix(1, 1, 9, fields_st)
                                    : mxCreateStructMatrix(1, 1, 8 + (want_lp ? 1 : 0) + (stack ? 1 : 0), fields);
   mxArray* pn[6];
   for (int k = 0; k < 3; ++k) pn[k] = mxCreateDoubleMatrix(P, n, mxREAL);
@@ -876,7 +922,27 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     red.sopt = &sopt;
     red.sout = &so.out;
   }
-  const int rc = want_lp ? tci_dram_run_lp(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
+  // the swap records of a tempered run, written in place: the per-chain counters 1 x n, the logs n x n_events
+  const int64_t t_win = opt.adaptint > 0 ? opt.adaptint : 100;
+  const size_t t_ev = want_temper && topt.swap_every > 0 ? (size_t)((opt.n_steps - 1) / t_win / topt.swap_every) : 0;
+  std::vector<int32_t> t_tried(want_temper ? n : 0), t_acc(want_temper ? n : 0);
+  std::vector<uint8_t> t_accl(t_ev * n);
+  mxArray* t_logr = want_temper ? mxCreateDoubleMatrix(n, t_ev, mxREAL) : nullptr;
+  tci_temper_outputs tout;
+  memset(&tout, 0, sizeof tout);
+  if (want_temper) {
+    tout.swap_tried = t_tried.data();
+    tout.swap_accepted = t_acc.data();
+    if (t_ev) {
+      tout.swap_logr = mxGetPr(t_logr);
+      tout.swap_acc = t_accl.data();
+    }
+    tout.swap_log_rows = (int64_t)t_ev;
+  }
+  const int rc = want_temper ? tci_dram_run_tempered(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
+                                                     in[5], s2v.data(), (int64_t)P, &out, &red, nullptr, 0, nullptr,
+                                                     nullptr, &topt, &tout)
+                 : want_lp ? tci_dram_run_lp(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
                                            s2v.data(), (int64_t)P, &out, &red, nullptr, 0, nullptr, nullptr, nullptr,
                                            nullptr, nullptr, &lo.out)
                  : want_stats ? tci_dram_run_stats(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
@@ -889,7 +955,35 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxDestroyArray(res);
     if (ch) mxDestroyArray(ch);
     if (s2c) mxDestroyArray(s2c);
+    if (t_logr) mxDestroyArray(t_logr);
     check(ctx, rc, "tci_dram_run");
+  }
+  if (want_temper) {
+    static const char* tf[] = {"beta", "ladder", "swap_every", "swap_tried", "swap_accepted", "swap_logr", "swap_acc",
+                               "event_rows", "n_events"};
+    mxArray* t = mxCreateStructMatrix(1, 1, 9, tf);
+    mxArray* v[4];
+    for (int k = 0; k < 4; ++k) v[k] = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t b = 0; b < n; ++b) {
+      mxGetPr(v[0])[b] = t_beta[b];
+      mxGetPr(v[1])[b] = (double)t_ladder[b] + 1.0;
+      mxGetPr(v[2])[b] = (double)t_tried[b];
+      mxGetPr(v[3])[b] = (double)t_acc[b];
+    }
+    mxArray* ac = mxCreateDoubleMatrix(n, t_ev, mxREAL);
+    for (size_t i = 0; i < t_ev * n; ++i) mxGetPr(ac)[i] = (double)t_accl[i];
+    mxArray* er = mxCreateDoubleMatrix(1, t_ev, mxREAL);
+    for (size_t i = 0; i < t_ev; ++i) mxGetPr(er)[i] = (double)((int64_t)(i + 1) * topt.swap_every * t_win);
+    mxSetField(t, 0, "beta", v[0]);
+    mxSetField(t, 0, "ladder", v[1]);
+    mxSetField(t, 0, "swap_every", mxCreateDoubleScalar((double)topt.swap_every));
+    mxSetField(t, 0, "swap_tried", v[2]);
+    mxSetField(t, 0, "swap_accepted", v[3]);
+    mxSetField(t, 0, "swap_logr", t_logr);
+    mxSetField(t, 0, "swap_acc", ac);
+    mxSetField(t, 0, "event_rows", er);
+    mxSetField(t, 0, "n_events", mxCreateDoubleScalar((double)tout.n_events));
+    mxSetField(res, 0, "temper", t);
   }
   mxArray* ne = mxCreateDoubleMatrix(1, n, mxREAL);
   for (size_t b = 0; b < n; ++b) mxGetPr(ne)[b] = (double)nev[b];

@@ -151,6 +151,16 @@ class tci_chainess_outputs(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class tci_temper_options(C.Structure):
+    _fields_ = [("beta", _dp), ("ladder", _i32p), ("n_ladders", C.c_int64), ("swap_every", C.c_int64),
+                ("flags", C.c_int64)]
+
+
+class tci_temper_outputs(C.Structure):
+    _fields_ = [("swap_tried", _i32p), ("swap_accepted", _i32p), ("swap_logr", _dp), ("swap_acc", _u8p),
+                ("swap_log_rows", C.c_int64), ("n_events", C.c_int64)]
+
+
 class tci_fitcheck_options(C.Structure):
     _fields_ = [("scratch_bytes", C.c_int64), ("n_levels", C.c_int32), ("levels", C.c_double * 8)]
 
@@ -250,6 +260,12 @@ SIGNATURES = [
                                   C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                   C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
                                   C.POINTER(tci_chainlp_options), C.POINTER(tci_chainlp_outputs)]),
+    ("tci_temper_defaults", C.c_int, [C.POINTER(tci_temper_options)]),
+    ("tci_dram_run_tempered", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                        _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                        C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
+                                        C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                        C.POINTER(tci_temper_options), C.POINTER(tci_temper_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

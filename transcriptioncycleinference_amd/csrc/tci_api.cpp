@@ -1673,8 +1673,14 @@ struct RhatAsk {
 
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
 // -> [window records] -> [adapt] -> step + 1.
+// What tci_dram_run_tempered adds to a run: the ladders and where the swap records go.
+struct TemperAsk {
+  const tci_temper_options* topt;
+  tci_temper_outputs* tout;
+};
+
 int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& p, hipStream_t s, bool with_stats,
-                 bool with_adapt) {
+                 bool with_adapt, const tci::SwapArgs* swap = nullptr) {
   int rc;
   if ((rc = tci::dram_launch_propose1(st, p, s)) != TCI_OK) return rc;
   if ((rc = tci::launch(ctx->kp, ctx->rpl, tci::MODE_SS, st.prop1, st.ld, st.cell, st.act1, st.n_chains, st.ss1,
@@ -1687,6 +1693,8 @@ int enqueue_step(tci_ctx* ctx, const tci::DramState& st, const tci::DramParams& 
   if ((rc = tci::dram_launch_accept2(st, p, s)) != TCI_OK) return rc;
   if (with_stats && (rc = tci::dram_launch_stats(st, p, s)) != TCI_OK) return rc;
   if (with_adapt && (rc = tci::dram_launch_adapt(st, p, s)) != TCI_OK) return rc;  // no-op unless step % adaptint == 0
+  // a window's end (with_stats): the ladders' swap, which reads the row from *st.step as the adaptation does
+  if (swap && with_stats && (rc = tci::dram_launch_swap(st, p, *swap, s)) != TCI_OK) return rc;
   return tci::dram_launch_step_incr(st, s);
 }
 
@@ -1729,7 +1737,8 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
                   const double* theta0, const double* lower, const double* upper, const double* prior_mu,
                   const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
                   tci_dram_outputs* out, const tci_dram_reductions& red, const RhatAsk* rhat = nullptr,
-                  const tci_chainlp_options* lopt = nullptr, tci_chainlp_outputs* lout = nullptr) {
+                  const tci_chainlp_options* lopt = nullptr, tci_chainlp_outputs* lout = nullptr,
+                  const TemperAsk* temper = nullptr) {
   if (!ctx) return TCI_EINVAL;
   const tci_chainstats_options* sopt = red.sopt;
   tci_chainstats_outputs* sout = red.sout;
@@ -1843,6 +1852,66 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
       if (!(qcov_diag[c * L + j] > 0)) return fail(ctx, TCI_EINVAL, "tci_dram_run: qcov_diag must be > 0");
     }
   }
+  // the ladders (tci_dram_run_tempered): each chain's Gibbs shape and stored sigma2, and the pairs of neighbouring rungs
+  std::vector<double> gshape(n), s20(sigma2_0, sigma2_0 + n), beta(n, 1.0);
+  for (size_t c = 0; c < n; ++c) gshape[c] = 0.5 * (double)nobs[c];
+  std::vector<int32_t> pair_a, pair_b, pair_r;
+  int64_t swap_every = 0;
+  if (temper) {
+    const tci_temper_options* t = temper->topt;
+    const char* who = "tci_dram_run_tempered";
+    if (t->flags != 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": flags is reserved and must be 0");
+    if (t->swap_every < 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": swap_every must be >= 0");
+    if (t->n_ladders < 0 || t->n_ladders > n_chains)
+      return fail(ctx, TCI_EINVAL, std::string(who) + ": n_ladders must be in [0, n_chains]");
+    swap_every = t->swap_every;
+    for (size_t c = 0; c < n; ++c) {
+      const double b = t->beta ? t->beta[c] : 1.0;
+      const int32_t l = t->ladder ? t->ladder[c] : -1;
+      const std::string where = " (chain " + std::to_string(c) + ", ladder " + std::to_string(l) + ")";
+      if (l < -1 || l >= t->n_ladders)
+        return fail(ctx, TCI_EINVAL, std::string(who) + ": ladder values must be in [-1, n_ladders)" + where);
+      if (!std::isfinite(b) || !(b > 0.0) || !(b <= 1.0))
+        return fail(ctx, TCI_EINVAL, std::string(who) + ": beta must be finite and in (0, 1]" + where);
+      beta[c] = b;
+      if (b != 1.0) {  // beta = 1 keeps the plain run's bits: no arithmetic on its values
+        gshape[c] = b * (0.5 * (double)nobs[c]);
+        s20[c] = sigma2_0[c] / b;
+      }
+      if (opt->updatesigma && !(gshape[c] >= 1.0))  // the Gibbs draw's shape; no draw, no limit
+        return fail(ctx, TCI_EINVAL, std::string(who) + ": beta * N / 2 must be >= 1 for the sigma2 draw" + where);
+    }
+    std::vector<int64_t> last((size_t)t->n_ladders, -1);
+    std::vector<int32_t> rung((size_t)t->n_ladders, 0);
+    for (size_t c = 0; c < n && t->ladder; ++c) {
+      const int32_t l = t->ladder[c];
+      if (l < 0) continue;
+      const int64_t a = last[(size_t)l];
+      if (a >= 0) {
+        const std::string where = " (ladder " + std::to_string(l) + ", chains " + std::to_string(a) + " and " +
+                                  std::to_string(c) + ")";
+        if (!(beta[c] < beta[(size_t)a]))
+          return fail(ctx, TCI_EINVAL, std::string(who) + ": beta must be strictly decreasing along a ladder" + where);
+        if (cell_id[c] != cell_id[a])
+          return fail(ctx, TCI_EINVAL, std::string(who) + ": the rungs of a ladder must share the cell" + where);
+        for (int32_t j = 0; j < npar[c]; ++j) {
+          const size_t x = c * L + j, y = (size_t)a * L + j;
+          const bool same_sig = prior_sig[x] == prior_sig[y] || (prior_sig[x] != prior_sig[x] && prior_sig[y] != prior_sig[y]);
+          if (lower[x] != lower[y] || upper[x] != upper[y] || prior_mu[x] != prior_mu[y] || !same_sig)
+            return fail(ctx, TCI_EINVAL, std::string(who) + ": the rungs of a ladder must share lower, upper, prior_mu "
+                                                           "and prior_sig" + where);
+        }
+        if (!opt->updatesigma && sigma2_0[c] != sigma2_0[a])
+          return fail(ctx, TCI_EINVAL, std::string(who) + ": with updatesigma = 0 the rungs of a ladder must share "
+                                                         "sigma2_0" + where);
+        pair_a.push_back((int32_t)a);
+        pair_b.push_back((int32_t)c);
+        pair_r.push_back(rung[(size_t)l] - 1);
+      }
+      last[(size_t)l] = (int64_t)c;
+      ++rung[(size_t)l];
+    }
+  }
   RhatGroups r_groups;
   if (rhat) {
     rc = chainrhat_groups(ctx, rhat->who, rhat->ropt, r_rows, n_chains, ld, npar.data(), rhat->group,
@@ -1893,6 +1962,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   int64_t* d_key = A.alloc<int64_t>(n, &e);
   d_npar = A.alloc<int32_t>(n, &e);
   d_nobs = A.alloc<int32_t>(n, &e);
+  double* d_gshape = A.alloc<double>(n, &e);
   d_lower = A.alloc<double>(n * L, &e);
   d_upper = A.alloc<double>(n * L, &e);
   d_pmu = A.alloc<double>(n * L, &e);
@@ -1904,6 +1974,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   st.key = d_key;
   st.npar = d_npar;
   st.nobs = d_nobs;
+  st.gshape = d_gshape;
   st.lower = d_lower;
   st.upper = d_upper;
   st.pmu = d_pmu;
@@ -1976,7 +2047,8 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   TCI_HIP(ctx, hipMemcpyAsync(d_pmu, prior_mu, n * L * sizeof(double), hipMemcpyHostToDevice, s));
   TCI_HIP(ctx, hipMemcpyAsync(d_psig, prior_sig, n * L * sizeof(double), hipMemcpyHostToDevice, s));
   TCI_HIP(ctx, hipMemcpyAsync(d_qdiag, qcov_diag, n * L * sizeof(double), hipMemcpyHostToDevice, s));
-  TCI_HIP(ctx, hipMemcpyAsync(d_s20, sigma2_0, n * sizeof(double), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_s20, s20.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+  TCI_HIP(ctx, hipMemcpyAsync(d_gshape, gshape.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
   TCI_HIP(ctx, hipMemcpyAsync(st.theta, theta0, n * L * sizeof(double), hipMemcpyHostToDevice, s));
   TCI_HIP(ctx, hipMemsetAsync(st.wsum, 0, n * sizeof(double), s));
   TCI_HIP(ctx, hipMemsetAsync(st.act2, 0, n, s));
@@ -1993,6 +2065,46 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   p.thin = opt->thin;
   p.n_keep = n_keep;
   p.win = win;
+  // the ladders' swap: one event after every swap_every-th window that is not the run's last row
+  tci::SwapArgs sw{};
+  const tci::SwapArgs* swp = nullptr;
+  const int64_t n_events = swap_every > 0 ? (opt->n_steps - 1) / win / swap_every : 0;
+  const int64_t log_rows = temper && temper->tout && (temper->tout->swap_logr || temper->tout->swap_acc)
+                               ? std::min<int64_t>(n_events, std::max<int64_t>(temper->tout->swap_log_rows, 0))
+                               : 0;
+  if (temper && !pair_a.empty() && n_events > 0) {
+    const size_t np = pair_a.size();
+    int32_t* d_pa = A.alloc<int32_t>(np, &e);
+    int32_t* d_pb = A.alloc<int32_t>(np, &e);
+    int32_t* d_pr = A.alloc<int32_t>(np, &e);
+    double* d_beta = A.alloc<double>(n, &e);
+    sw.tried = A.alloc<int32_t>(n, &e);
+    sw.accepted = A.alloc<int32_t>(n, &e);
+    if (log_rows > 0) {
+      sw.logr = A.alloc<double>((size_t)log_rows * n, &e);
+      sw.acc = A.alloc<uint8_t>((size_t)log_rows * n, &e);
+    }
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipMalloc(dram swap)");
+    TCI_HIP(ctx, hipMemcpyAsync(d_pa, pair_a.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    TCI_HIP(ctx, hipMemcpyAsync(d_pb, pair_b.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    TCI_HIP(ctx, hipMemcpyAsync(d_pr, pair_r.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    TCI_HIP(ctx, hipMemcpyAsync(d_beta, beta.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+    TCI_HIP(ctx, hipMemsetAsync(sw.tried, 0, n * sizeof(int32_t), s));
+    TCI_HIP(ctx, hipMemsetAsync(sw.accepted, 0, n * sizeof(int32_t), s));
+    if (log_rows > 0) {
+      TCI_HIP(ctx, hipMemsetAsync(sw.logr, 0xFF, (size_t)log_rows * n * sizeof(double), s));  // all ones: a NaN
+      TCI_HIP(ctx, hipMemsetAsync(sw.acc, 0, (size_t)log_rows * n, s));
+    }
+    sw.pair_a = d_pa;
+    sw.pair_b = d_pb;
+    sw.pair_r = d_pr;
+    sw.n_pairs = (int64_t)np;
+    sw.beta = d_beta;
+    sw.swap_every = swap_every;
+    sw.n_steps = opt->n_steps;
+    sw.n_events = log_rows;
+    swp = &sw;
+  }
   // initial state: R = chol(J0), prior, sigma2, the initial ssfun call, chain row 1
   if ((rc = tci::dram_launch_init(st, d_qdiag, d_s20, s)) != TCI_OK) return fail(ctx, rc, "dram init launch");
   if ((rc = tci::launch(ctx->kp, ctx->rpl, tci::MODE_SS, st.theta, ld, d_cell, nullptr, n_chains, st.ss, nullptr, 0,
@@ -2092,6 +2204,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
       rc = tci::dram_launch_chain(sc, p, ctx->kp, ctx->rpl, next, end, rec, s, tm,
                                   p.split && i + 1 < chunks.size() ? &nx : nullptr);
       if (rc == TCI_OK && ai > 0 && end % ai == 0) rc = tci::dram_launch_adapt(sc, p, s, tm);
+      if (rc == TCI_OK && swp && end % win == 0 && end < opt->n_steps) rc = tci::dram_launch_swap(sc, p, sw, s);
     }
     e = hipSuccess;
   } else {
@@ -2101,7 +2214,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   int64_t next = 2;  // next step number to enqueue
   auto plain = [&](int64_t upto) {  // steps next .. upto
     for (; next <= upto && rc == TCI_OK; ++next)
-      rc = enqueue_step(ctx, st, p, s, next % win == 0, ai > 0 && next % ai == 0);
+      rc = enqueue_step(ctx, st, p, s, next % win == 0, ai > 0 && next % ai == 0, swp);
   };
   const int64_t G = win;  // graph blocks of one window (win = adaptint when adapting)
   plain(std::min<int64_t>(win, opt->n_steps));  // head: up to the first window's end
@@ -2109,7 +2222,7 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
   if (rc == TCI_OK && blocks > 0) {
     TCI_HIP(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     int crc = TCI_OK;
-    for (int64_t k = 0; k < G && crc == TCI_OK; ++k) crc = enqueue_step(ctx, st, p, s, k == G - 1, ai > 0 && k == G - 1);
+    for (int64_t k = 0; k < G && crc == TCI_OK; ++k) crc = enqueue_step(ctx, st, p, s, k == G - 1, ai > 0 && k == G - 1, swp);
     hipError_t ce = hipStreamEndCapture(s, &graph);
     if (crc != TCI_OK || ce != hipSuccess) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -2186,6 +2299,26 @@ int dram_run_impl(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, c
     if (out->sigma_std) out->sigma_std[c] = std::sqrt(sqm2[c] / (double)opt->n_steps);
     if (out->accept_rate) out->accept_rate[c] = opt->n_steps > 1 ? nacc[c] / (double)(opt->n_steps - 1) : 0.0;
     if (out->n_evals) out->n_evals[c] = nev[c];
+  }
+  if (temper && temper->tout) {
+    tci_temper_outputs* to = temper->tout;
+    to->n_events = n_events;
+    if (to->swap_tried) {
+      if (swp) TCI_HIP(ctx, hipMemcpy(to->swap_tried, sw.tried, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+      else std::fill(to->swap_tried, to->swap_tried + n, 0);
+    }
+    if (to->swap_accepted) {
+      if (swp) TCI_HIP(ctx, hipMemcpy(to->swap_accepted, sw.accepted, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+      else std::fill(to->swap_accepted, to->swap_accepted + n, 0);
+    }
+    if (to->swap_logr && log_rows > 0) {
+      if (swp) TCI_HIP(ctx, hipMemcpy(to->swap_logr, sw.logr, (size_t)log_rows * n * sizeof(double), hipMemcpyDeviceToHost));
+      else std::fill(to->swap_logr, to->swap_logr + (size_t)log_rows * n, (double)NAN);
+    }
+    if (to->swap_acc && log_rows > 0) {
+      if (swp) TCI_HIP(ctx, hipMemcpy(to->swap_acc, sw.acc, (size_t)log_rows * n, hipMemcpyDeviceToHost));
+      else std::fill(to->swap_acc, to->swap_acc + (size_t)log_rows * n, (uint8_t)0);
+    }
   }
   if (out->final_theta) TCI_HIP(ctx, hipMemcpy(out->final_theta, st.theta, n * L * sizeof(double), hipMemcpyDeviceToHost));
   if (st.chain_out && out->chain)
@@ -2429,6 +2562,34 @@ int tci_dram_run_lp(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains,
   const RhatAsk ask{ropt, group, n_groups, rout, "tci_dram_run_lp", eopt, eout};
   return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
                        out, red ? *red : none, &ask, lopt, lout);
+}
+
+int tci_temper_defaults(tci_temper_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  o->swap_every = 1;
+  return TCI_OK;
+}
+
+int tci_dram_run_tempered(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                          const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                          const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                          tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                          const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_temper_options* topt,
+                          tci_temper_outputs* tout) {
+  if (!ctx) return TCI_EINVAL;
+  tci_temper_options def;
+  tci_temper_defaults(&def);
+  const TemperAsk task{topt ? topt : &def, tout};
+  const tci_dram_reductions none{};
+  if (!rout)
+    return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                         out, red ? *red : none, nullptr, nullptr, nullptr, &task);
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_dram_run_tempered: n_groups must be in [1, n_chains]");
+  const RhatAsk ask{ropt, group, n_groups, rout, "tci_dram_run_tempered"};
+  return dram_run_impl(ctx, opt, n_chains, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0, ld,
+                       out, red ? *red : none, &ask, nullptr, nullptr, &task);
 }
 
 int tci_chainess_defaults(tci_chainess_options* o) {

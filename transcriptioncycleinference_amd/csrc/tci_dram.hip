@@ -49,7 +49,7 @@ namespace {
 
 constexpr int kThreads = 256;  // one workgroup (4 waves) per chain
 
-enum Purpose : uint32_t { P_NORM1 = 1, P_U1 = 2, P_NORM2 = 3, P_U2 = 4, P_GAMMA = 5 };
+enum Purpose : uint32_t { P_NORM1 = 1, P_U1 = 2, P_NORM2 = 3, P_U2 = 4, P_GAMMA = 5, P_SWAP = 6 };
 
 
 // The 32 x 32 -> 64-bit product of a Philox round in one v_mad_u64_u32: the compiler's
@@ -182,7 +182,8 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, int64_t c, int64_t s
   return u01(r.x, r.y);
 }
 
-// Gamma(a, 1) by Marsaglia & Tsang (a >= 1 here: a = N/2 >= 2) as the product d*v; a Gamma(a, scale)
+// Gamma(a, 1) by Marsaglia & Tsang as the product d*v, for a >= 1: a = DramState::gshape = N/2 >= 2 on a plain chain
+// and beta N/2 on a tempered rung, which dram_run_impl refuses below 1 (tci_dram_run_tempered); a Gamma(a, scale)
 // variate is (d*v)*scale. The unit variate depends only on the stream and a, so the fused engine
 // draws it ahead of the chain (k_draws) and the scale (2/SS of the current state) is applied when
 // it is used: the same bits as gamma_at.
@@ -754,7 +755,7 @@ __global__ __launch_bounds__(kThreads) void k_accept2(DramState st, DramParams p
   if (threadIdx.x == 0) {
     if (!(st.acc1[c] != 0 || acc2)) st.nrej_win[c] += 1;  // no stage moved the chain
     // sigma2 Gibbs update (updatesigma = 1, :265): 1/sigma2 ~ Gamma(N/2, scale 2/oldss)
-    if (p.updatesigma) st.sigma2[c] = 1.0 / gamma_at(p.seed, st.key[c], step, 0.5 * (double)st.nobs[c], 2.0 / st.ss[c]);
+    if (p.updatesigma) st.sigma2[c] = 1.0 / gamma_at(p.seed, st.key[c], step, st.gshape[c], 2.0 / st.ss[c]);
   }
   __syncthreads();
   log_row_block(st, p, c, step, P, st.theta + c * st.ld, st.sigma2[c], st.acc1[c] != 0 || acc2);
@@ -762,6 +763,70 @@ __global__ __launch_bounds__(kThreads) void k_accept2(DramState st, DramParams p
 
 __global__ void k_step_incr(int64_t* step) {
   if (threadIdx.x == 0) *step += 1;
+}
+
+// ---- Replica exchange between neighbouring rungs of a ladder (SwapArgs, tci_dram_internal.h). One wavefront per
+// pair; run by every engine after the row s = *st.step that ends window w = s / win has been logged and adapted.
+// It acts when s < n_steps, w % swap_every == 0 and the pair's lower rung r has the parity of w / swap_every, so
+// the pairs of one launch share no chain. Lane 0 decides: with the physical sigma2 = beta * s2t of each rung and
+// dev = ss / sigma2 + nobs * log(2 pi sigma2) (tci_chainlp's deviance, the same operations in the same order),
+//   logr = (0.5 * (beta_a - beta_b)) * (dev_a - dev_b),  accept iff u < exp(logr), u = uniform_at(key[a], s, P_SWAP);
+// a non-finite logr is rejected. On accept theta, ss and prior change places; with updatesigma the physical sigma2
+// does too (each rung stores it divided by its own beta), without it sigma2 is a constant of the model and stays.
+// cov, cmean, R, the window logs and the counters stay with the rung.
+__global__ __launch_bounds__(kThreads) void k_swap(DramState st, DramParams p, SwapArgs a) {
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * (kThreads / 64) + w;
+  if (q >= a.n_pairs) return;
+  const int64_t s = *st.step;
+  if (a.swap_every <= 0 || s >= a.n_steps || s % p.win != 0) return;
+  const int64_t wn = s / p.win;
+  if (wn % a.swap_every != 0) return;
+  const int64_t ev = wn / a.swap_every;  // 1, 2, ..: the event's row of the logs is ev - 1
+  if ((int64_t)(a.pair_r[q] & 1) != (ev & 1)) return;
+  const int64_t ca = a.pair_a[q], cb = a.pair_b[q];
+  if (ca < 0 || cb < 0 || ca >= st.n_chains || cb >= st.n_chains) return;
+  int take = 0;
+  if (lane == 0) {
+    const double ba = a.beta[ca], bb = a.beta[cb];
+    const double ta = st.sigma2[ca], tb = st.sigma2[cb];
+    const double s2a = ba * ta, s2b = bb * tb;
+    const double ssa = st.ss[ca], ssb = st.ss[cb];
+    const double nobs = (double)st.nobs[ca];
+    const double da = ssa / s2a + nobs * log(6.283185307179586 * s2a);
+    const double db = ssb / s2b + nobs * log(6.283185307179586 * s2b);
+    const double logr = (0.5 * (ba - bb)) * (da - db);
+    const double u = uniform_at(p.seed, st.key[ca], s, P_SWAP);
+    const bool ok = isfinite(logr) && u < exp(logr);
+    take = ok ? 1 : 0;
+    a.tried[ca] += 1;
+    if (ok) a.accepted[ca] += 1;
+    if (ev - 1 < a.n_events) {
+      if (a.logr != nullptr) a.logr[(ev - 1) * st.n_chains + ca] = logr;
+      if (a.acc != nullptr) a.acc[(ev - 1) * st.n_chains + ca] = ok ? 1 : 0;
+    }
+    if (ok) {
+      const double pa = st.prior[ca], pb = st.prior[cb];
+      st.ss[ca] = ssb;
+      st.ss[cb] = ssa;
+      st.prior[ca] = pb;
+      st.prior[cb] = pa;
+      if (p.updatesigma) {
+        st.sigma2[ca] = s2b / ba;
+        st.sigma2[cb] = s2a / bb;
+      }
+    }
+  }
+  take = __builtin_amdgcn_readfirstlane(take);
+  if (!take) return;
+  const int P = st.npar[ca];  // the rungs of a ladder share the cell
+  double* xa = st.theta + ca * st.ld;
+  double* xb = st.theta + cb * st.ld;
+  for (int j = lane; j < P; j += 64) {
+    const double va = xa[j], vb = xb[j];
+    xa[j] = vb;
+    xb[j] = va;
+  }
 }
 
 
@@ -878,7 +943,7 @@ __device__ __forceinline__ void draws_rng_units(const DramState& st, const DramP
       double* sc = d0 + threadIdx.x * DW + 2 * ld;
       sc[D_U1] = uniform_at(p.seed, key, step, P_U1);
       sc[D_U2] = uniform_at(p.seed, key, step, P_U2);
-      sc[D_G] = p.updatesigma ? gamma_unit_t(p.seed, key, step, 0.5 * (double)st.nobs[c]) : 1.0;
+      sc[D_G] = p.updatesigma ? gamma_unit_t(p.seed, key, step, st.gshape[c]) : 1.0;
     }
     __syncthreads();  // Z is rewritten by the next unit
   }
@@ -922,7 +987,7 @@ __global__ __launch_bounds__(64 * NWD) __attribute__((amdgpu_waves_per_eu(WPE)))
   for (int e = threadIdx.x; e < 2 * kDrawSteps * L + 16; e += kDrawThreads) Z[e] = 0.0;
   __syncthreads();
   const double* Rg = st.Rd + c * tri_stride(ld);
-  const double a = 0.5 * (double)st.nobs[c];
+  const double a = st.gshape[c];
   const double inv_ds = 1.0 / p.drscale;
   double* drow = st.draws + (c * p.chunk - s_begin) * DW;  // row of step s: drow + s * DW
   for (int pass = 0; pass < npass; ++pass) {
@@ -2671,6 +2736,12 @@ int64_t dram_chain_lds_bytes(int64_t ld, int rpl) {
 int dram_launch_stats(const DramState& st, const DramParams& p, void* stream) {
   hipLaunchKernelGGL(k_stats, dim3((unsigned)((st.n_chains + 3) / 4)), dim3(kThreads), 0, (hipStream_t)stream, st, p);
   return finish();
+}
+int dram_launch_swap(const DramState& st, const DramParams& p, const SwapArgs& a, void* stream) {
+  if (a.n_pairs <= 0 || a.swap_every <= 0) return TCI_OK;
+  const unsigned blocks = (unsigned)((a.n_pairs + kThreads / 64 - 1) / (kThreads / 64));
+  hipLaunchKernelGGL(k_swap, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, st, p, a);
+  return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 int dram_launch_step_incr(const DramState& st, void* stream) {
   hipLaunchKernelGGL(k_step_incr, dim3(1), dim3(64), 0, (hipStream_t)stream, st.step);

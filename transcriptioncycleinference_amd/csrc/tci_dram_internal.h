@@ -87,6 +87,7 @@ struct DramState {
   const int64_t* key;      // chain -> RNG stream key (tci_dram_options.chain_keys; identity when absent)
   const int32_t* npar;     // P_c = 7 + N_c
   const int32_t* nobs;     // N = length(ydata) = 2 N_c (TranscriptionCycleMCMC.m:260)
+  const double* gshape;    // shape of the sigma2 Gibbs draw: 0.5 * nobs, times beta on a tempered rung (SwapArgs)
   const double* lower;     // bounds (TranscriptionCycleMCMC.m:242-255)
   const double* upper;
   const double* pmu;       // Gaussian prior mean / sd (sd = +Inf: no prior), :254
@@ -162,6 +163,28 @@ struct DramParams {
   int64_t split;       // k_chain's engine: the draws split in two (the state-independent ones drawn one chunk
                        // ahead by extra k_chain workgroups; k_draws multiplies by R only). Same bits.
 };
+
+// Parallel tempering (tci_dram_run_tempered). A rung with inverse temperature beta samples
+//   [likelihood]^beta * (1 / sigma2) * prior(theta)
+// and holds s2t = sigma2 / beta in DramState::sigma2, so every acceptance is the plain sampler's code and the Gibbs
+// draw is 1 / s2t ~ Gamma(beta N / 2, scale 2 / ss) (DramState::gshape). k_swap exchanges the states of neighbouring
+// rungs between two windows; pair q is rungs pair_r[q] and pair_r[q] + 1 of one ladder, chains pair_a[q] and pair_b[q].
+struct SwapArgs {
+  const int32_t* pair_a;
+  const int32_t* pair_b;
+  const int32_t* pair_r;
+  int64_t n_pairs;
+  const double* beta;      // per chain
+  int64_t swap_every;      // swaps after window w when w % swap_every == 0 (0: never)
+  int64_t n_steps;         // no swap at or after the run's last row
+  int64_t n_events;        // rows of logr / acc
+  int32_t* tried;          // per chain, counted at the pair's lower rung
+  int32_t* accepted;
+  double* logr;            // [n_events][n_chains] or null
+  uint8_t* acc;            // [n_events][n_chains] or null
+};
+// After the row *st.step has been logged and adapted; does nothing unless that row ends a window that swaps.
+int dram_launch_swap(const DramState& st, const DramParams& p, const SwapArgs& a, void* stream);
 
 int dram_launch_init(const DramState& st, const double* qcov_diag, const double* sigma2_0, void* stream);
 int dram_launch_propose1(const DramState& st, const DramParams& p, void* stream);

@@ -81,6 +81,10 @@ LP_GROUP_FIELDS = ("lp_rhat", "lp_rhat_split", "lp_ess", "lp_mcse", "ss_gap", "b
 # mean).
 STACK_FIELDS = ("weights", "elpd_loo", "p_loo", "khat_max", "n_khat_bad", "elpd_loo_i", "khat_i", "elpd_stack",
                 "stacked_mean", "n_samples", "cell_index")
+# MCMCtemper (fit(..., temper=R)): the ladder of a fitted cell: beta [R]; per replicate the swap acceptance of every
+# pair of neighbouring rungs, swap_rate [M, R - 1] (NaN for a pair never tried) with swap_tried [M, R - 1], and every
+# rung's DRAM acceptance rate, accept_rate [M, R]
+TEMPER_FIELDS = ("beta", "swap_rate", "swap_tried", "accept_rate", "swap_every", "n_events", "n_chains", "cell_index")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -140,6 +144,7 @@ class DramResult:
     kernel_ms: Optional[np.ndarray] = None        # DramOptions.kernel_times: ms per class (draws, walk, adapt,
     #                                               the split draws' first-chunk launch; include/tci.h)
     kernel_launches: Optional[np.ndarray] = None  # and launches per class
+    temper: Optional["TemperResult"] = None       # dram_run(beta=, ladder=): the ladders and their swap records
     lp: Optional[ChainLp] = None                  # dram_run(logpost=True): log-posterior trace, best sample, DIC
     ess: Optional[ChainEss] = None                # dram_run(group=ids, ess=True): effective sample size of every group
     rhat: Optional[ChainRhat] = None              # dram_run(group=ids): R-hat / pooled moments of every group of chains
@@ -149,11 +154,51 @@ class DramResult:
     cov: Optional[ChainCov] = None                # dram_run(cov=True): mean / cov / corr of the same rows
 
 
+@dataclass
+class TemperResult:
+    """The ladders of a tempered run (``tci_dram_run_tempered``) and what their swaps did. Event ``e`` follows chain
+    row ``event_rows[e]``; a pair's records sit at its lower rung (the chain of the larger beta)."""
+
+    beta: np.ndarray            # [n_chains]
+    ladder: np.ndarray          # [n_chains] int32, -1 = in no ladder
+    swap_every: int
+    swap_tried: np.ndarray      # [n_chains] int32
+    swap_accepted: np.ndarray   # [n_chains] int32
+    swap_logr: np.ndarray       # [n_events, n_chains], NaN where no pair was tried
+    swap_acc: np.ndarray        # [n_events, n_chains] uint8
+    event_rows: np.ndarray      # [n_events] int64: the 1-based chain row each event follows
+    n_events: int = 0
+
+
+def temper_ladder(P: int, rungs: int, ratio: Optional[float] = None) -> np.ndarray:
+    """Inverse temperatures ``beta_r = ratio**r`` of a ladder of ``rungs`` rungs, cold first. The default ratio
+    ``1 / (1 + sqrt(2 / P))`` is the geometric spacing that holds the swap acceptance constant along the ladder of a
+    ``P``-dimensional Gaussian target (Kofke 2002; Predescu et al. 2004): the energy at beta has standard deviation
+    ``sqrt(P / 2) / beta``, so neighbouring energy distributions overlap alike when ``(beta_r - beta_{r+1}) / beta_{r+1}``
+    is ``sqrt(2 / P)``. It is derived, not tuned."""
+    P, R = int(P), int(rungs)
+    if P < 1 or R < 1:
+        raise ValueError("temper_ladder needs P >= 1 and rungs >= 1")
+    q = 1.0 / (1.0 + math.sqrt(2.0 / P)) if ratio is None else float(ratio)
+    if not (0.0 < q < 1.0):
+        raise ValueError("ratio must be in (0, 1)")
+    return q ** np.arange(R, dtype=np.float64)
+
+
+def swap_event_rows(n_steps: int, adaptint: int, swap_every: int) -> np.ndarray:
+    """The 1-based chain rows the swap events of a run follow: the ends ``w * win`` of the windows (``win = adaptint``,
+    or 100 without adaptation) with ``w % swap_every == 0`` that lie before the run's last row."""
+    win = int(adaptint) if int(adaptint) > 0 else 100
+    se = int(swap_every)
+    n = (int(n_steps) - 1) // win // se if se > 0 else 0
+    return (1 + np.arange(n, dtype=np.int64)) * se * win
+
+
 def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, sigma2_0,
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
              cov_scratch_bytes: int = 0, quant=None, dens=None, group=None, ess: bool = False,
-             logpost: bool = False) -> DramResult:
+             logpost: bool = False, beta=None, ladder=None, swap_every: int = 1) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -177,7 +222,19 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     the best sample and DIC (``DramResult.lp``, as ``Likelihood.chainlp`` gives with the run's priors), from the device
     chain through ``tci_dram_run_lp``, with any of the other reductions. With ``logpost`` the priors are checked before
     the run as ``Likelihood.chainlp`` checks them: a ``prior_mu`` entry (of a chain's ``7 + N``) that is not finite, or a
-    ``prior_sig`` entry that is NaN or <= 0, is a ``TciError`` (``TCI_EINVAL``) although the sampler alone would run."""
+    ``prior_sig`` entry that is NaN or <= 0, is a ``TciError`` (``TCI_EINVAL``) although the sampler alone would run.
+
+    ``beta`` / ``ladder``: parallel tempering (``tci_dram_run_tempered``, include/tci.h). ``beta``: the inverse
+    temperature of every chain (default 1); ``ladder``: one ladder id per chain (-1 or absent = in no ladder): the chains
+    of a ladder, in ascending row order, are its rungs, cold first, and exchange states after every ``swap_every``-th
+    window of ``adaptint`` rows (0 = never). ``sigma2_0`` is physical; every s2 output of a rung with ``beta < 1`` is
+    ``sigma2 / beta``. The swap records come back as ``DramResult.temper``. Works with ``stats``, ``cov``, ``quant``,
+    ``dens`` and ``group``; ``ess`` and ``logpost`` have no tempered entry point (ValueError)."""
+    tempered = beta is not None or ladder is not None
+    if tempered and (ess or logpost):
+        raise ValueError("a tempered run (beta= / ladder=) takes stats, cov, quant, dens and group, not ess or logpost")
+    if tempered and (isinstance(swap_every, bool) or int(swap_every) != swap_every or int(swap_every) < 0):
+        raise ValueError("swap_every must be an integer >= 0")
     if ess and group is None:
         raise ValueError("ess=True needs group: the effective sample size is a statistic of groups of chains")
     f = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
@@ -221,7 +278,21 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     if logpost:
         k0 = (max(int(opts.stats_from), 1) - 1 + opts.thin - 1) // opts.thin if opts.thin > 0 else 0
         clp = ChainLp.empty(max(n_keep - k0, 0), n, ld)
-    if cq is not None or cd is not None or cr is not None or clp is not None:
+    tr = None
+    if tempered:
+        bt = np.ones(n) if beta is None else f(beta)
+        ldr = np.full(n, -1, np.int32) if ladder is None else np.ascontiguousarray(ladder, np.int32)
+        if bt.shape != (n,) or ldr.shape != (n,):
+            raise ValueError("beta and ladder must have one entry per chain")
+        rows = swap_event_rows(opts.n_steps, opts.adaptint, swap_every)
+        ne = len(rows)
+        tr = TemperResult(bt, ldr, int(swap_every), np.zeros(n, np.int32), np.zeros(n, np.int32),
+                          np.full((ne, n), np.nan), np.zeros((ne, n), np.uint8), rows)
+        topt = _lib.tci_temper_options(P(bt), _lib.ptr(ldr, _lib._i32p), int(ldr.max(initial=-1)) + 1, int(swap_every), 0)
+        tout = _lib.tci_temper_outputs(_lib.ptr(tr.swap_tried, _lib._i32p), _lib.ptr(tr.swap_accepted, _lib._i32p),
+                                       P(tr.swap_logr) if ne else None, _lib.ptr(tr.swap_acc, _lib._u8p) if ne else None,
+                                       ne, 0)
+    if tempered or cq is not None or cd is not None or cr is not None or clp is not None:
         red = _lib.tci_dram_reductions()
         if cq is not None:
             qopt, qout = cq.options(), cq.to_c()
@@ -235,7 +306,19 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
             cc = ChainCov.empty(n, ld)
             copt, cout = _lib.tci_chaincov_options(int(cov_scratch_bytes)), cc.to_c()
             red.copt, red.cout = C.pointer(copt), C.pointer(cout)
-        if clp is not None:   # tci_dram_run_lp takes every other reduction with it
+        if tempered:          # tci_dram_run_tempered: the reductions and, with group, the group reduction
+            ropt = rout = None
+            if cr is not None:
+                ropt, rout = cr.options(), cr.to_c()
+            lk._check(lk._lib.tci_dram_run_tempered(*args, C.byref(red),
+                                                    _lib.ptr(grp, _lib._i32p) if cr is not None else None,
+                                                    ng if cr is not None else 0, None if ropt is None else C.byref(ropt),
+                                                    None if rout is None else C.byref(rout), C.byref(topt),
+                                                    C.byref(tout)))
+            tr.n_events = int(tout.n_events)
+            if cr is not None:
+                cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
+        elif clp is not None:   # tci_dram_run_lp takes every other reduction with it
             lopt, lout = clp.options(), clp.to_c()
             ropt = rout = eopt = eout = None
             if cr is not None:
@@ -285,7 +368,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
                       kernel_ms=np.array(out.kernel_ms[:], np.float64),
                       kernel_launches=np.array(out.kernel_launches[:], np.int64), lp=clp, ess=ce, rhat=cr, dens=cd, quant=cq, stats=cs,
-                      cov=cc)
+                      cov=cc, temper=tr)
 
 
 # ---------------------------------------------------------------------------
@@ -344,6 +427,7 @@ class FitResult:
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
     MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
+    MCMCtemper: Optional[List[Dict]] = None    # fit(..., temper=R): TEMPER_FIELDS per fitted cell
     MCMCstack: Optional[List[Dict]] = None     # fit(..., stack=nsample): STACK_FIELDS per fitted cell
     MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
     MCMCess: Optional[List[Dict]] = None       # fit(..., replicates=M, ess=True): ESS_FIELDS per fitted cell
@@ -463,7 +547,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
         rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False,
-        stack: Optional[int] = None) -> FitResult:
+        stack: Optional[int] = None, temper=None, swap_every: int = 1) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -530,8 +614,22 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     of every replicate over :func:`predict_rows` of its kept rows, and the weights across the cell's replicates that
     maximise the stacked leave-one-out density (``Likelihood.loocheck``, on the device; :func:`stack_entries`):
     the estimate for replicates that do not mix. ``replicates=1`` gives the LOO values alone, with weight 1. Nothing
-    else in the result changes."""
+    else in the result changes.
+
+    ``temper``: parallel tempering (include/tci.h, ``tci_dram_run_tempered``). An integer ``R``: a ladder of ``R`` rungs
+    per (cell, replicate) at :func:`temper_ladder` of the cell's ``P = 7 + N``; or a sequence of inverse temperatures,
+    strictly decreasing from 1, used for every cell. Neighbouring rungs exchange states after every ``swap_every``-th
+    adaptation window. Row layout: the fit runs ``M * R`` chains per cell, chain ``(q * M + r) * K + k`` being rung ``q``
+    of replicate ``r`` of fitted cell ``k`` (``K`` cells): the ``M * K`` cold rungs (``beta = 1``) come first in
+    today's replicate-major order and the hot rungs follow; they start where replicates ``M .. M * R - 1`` of
+    :func:`plan_fit` start and run on those replicates' RNG streams (so ``M * R <= 256``). The reductions and groups
+    apply to the cold rungs alone: every other field of the result is the cold rungs', computed as without tempering.
+    ``MCMCtemper`` holds one dict of ``TEMPER_FIELDS`` per fitted cell. ``temper=1`` or its absence is the untempered
+    fit, bit for bit."""
     M = int(replicates)
+    betas, R = _temper_arg(temper)
+    if R > 1 and (isinstance(swap_every, bool) or int(swap_every) != swap_every or int(swap_every) < 0):
+        raise ValueError("swap_every must be an integer >= 0")
     if M != replicates or M < 1:
         raise ValueError("replicates must be an integer >= 1")
     want_rhat = M > 1 if rhat is None else bool(rhat)
@@ -550,26 +648,54 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
     off = int(cell_offset)
-    plan = plan_fit(cl, ids, seed, ratePriorWidth, v0, approved, cell_offset=off, replicates=M)
+    if M * R > MAX_REPLICATES:
+        raise ValueError(f"replicates * temper must be at most {MAX_REPLICATES}: a chain's RNG stream key has 32 bits")
+    plan = plan_fit(cl, ids, seed, ratePriorWidth, v0, approved, cell_offset=off, replicates=M * R)
     keep = plan.cells
     K = len(keep)
+    MK = M * K
     if not keep:
         return FitResult(cl.name, [], [], [], np.zeros(0), 0, 0.0)
     # a private copy: the caller's options object is never modified
     o = dataclasses.replace(opts) if opts is not None else DramOptions()
     o.n_steps, o.burnintime, o.stats_from, o.thin = int(n_steps), int(n_burn), int(max(n_burn, 1)), int(thin)
     o.seed = int(seed) * 1000003 + 20201028
-    keys = replicate_keys(np.array(keep, np.int64) + off, M)
-    res = dram_run(lk, np.tile(np.array(keep, np.int32), M), plan.x0, plan.lower, plan.upper, plan.prior_mu,
-                   plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys,
-                   **(dict(group=np.tile(np.arange(K, dtype=np.int32), M)) if want_rhat else {}),
-                   **(dict(ess=True) if ess else {}),
-                   **(dict(logpost=True) if logpost else {}),
+    keys = replicate_keys(np.array(keep, np.int64) + off, M * R)
+    tk = {}
+    if R > 1:
+        tk = temper_layout([int(cl.lengths[c]) for c in keep], M, R, betas)
+        tk["swap_every"] = int(swap_every)
+    cold_group = np.concatenate([np.tile(np.arange(K, dtype=np.int32), M), np.full(MK * (R - 1), -1, np.int32)])
+    res = dram_run(lk, np.tile(np.array(keep, np.int32), M * R), plan.x0, plan.lower, plan.upper, plan.prior_mu,
+                   plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys, **tk,
+                   **(dict(group=cold_group) if want_rhat else {}),
+                   **(dict(ess=True) if ess and R == 1 else {}),
+                   **(dict(logpost=True) if logpost and R == 1 else {}),
                    **(dict(stats=True) if diagnostics else {}),
                    **(dict(max_lag=max_lag) if ess or diagnostics else {}),
                    **(dict(cov=True) if covariance else {}),
                    **(dict(quant=quantiles) if quantiles is not None else {}),
                    **(dict(dens=density) if density is not None and density is not False else {}))
+    tempers = None
+    if R > 1:
+        tempers = [temper_entry(res, k, K, M, R, off + c + 1) for k, c in enumerate(keep)]
+        # the tempered entry point has no effective sample size or log-posterior reduction: those of the cold rungs
+        # from their kept rows on the host, through the same kernels
+        if ess or logpost:
+            if res.chain is None:
+                raise ValueError("ess and logpost of a tempered fit are reduced from the kept rows: thin >= 1")
+            sel = 1 + int(thin) * np.arange(res.chain.shape[0]) >= max(n_burn, 1)
+            cold_chain, cold_s2 = res.chain[sel][:, :MK], res.s2chain[sel][:, :MK]
+            cid = np.tile(np.array(keep, np.int32), M)
+            if ess:
+                res.ess = lk.chainess(cold_chain, cold_s2, npar=7 + lk.cells.lengths[cid], group=cold_group[:MK],
+                                      max_lag=max_lag)
+            if logpost:
+                res.lp = lk.chainlp(cold_chain, cold_s2, cid, plan.prior_mu[:MK], plan.prior_sig[:MK])
+        # every per-chain field below is read by cell and replicate: the cold rungs'
+        res.mean, res.accept_rate = res.mean[:MK], res.accept_rate[:MK]
+        if res.chain is not None:
+            res.chain, res.s2chain = res.chain[:, :MK], res.s2chain[:, :MK]
     # forward model at the means on the raw times (:307-309)
     ms2, pp7 = lk.forward(res.mean[:K], np.array(keep, np.int32), grid="raw")
     results, plots, chains = [], [], []
@@ -628,8 +754,53 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         stk = stack_entries(lk, res.chain[rows_idx >= max(n_burn, 1)], res.s2chain, res.mean, keep, M, int(stack), off)
     return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
                      res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMClp=lps, MCMCess=es,
-                     MCMCrhat=rh, MCMCstack=stk,
+                     MCMCrhat=rh, MCMCstack=stk, MCMCtemper=tempers,
                      MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+
+
+def _temper_arg(temper):
+    """(betas or None, rung count) of ``fit``'s ``temper``: None / 1 = no tempering; an integer rung count; or a
+    sequence of inverse temperatures, strictly decreasing from 1 and positive."""
+    if temper is None:
+        return None, 1
+    if isinstance(temper, bool):
+        raise ValueError("temper must be a rung count or a sequence of inverse temperatures")
+    if np.ndim(temper) == 0:
+        if int(temper) != temper or int(temper) < 1:
+            raise ValueError("temper must be an integer rung count >= 1 or a sequence of inverse temperatures")
+        return None, int(temper)
+    b = np.asarray(temper, np.float64).reshape(-1)
+    if b.size < 1 or b[0] != 1.0 or not np.all(np.isfinite(b)) or np.any(b <= 0) or np.any(np.diff(b) >= 0):
+        raise ValueError("temper as a sequence must start at 1 (the cold rung) and decrease strictly, every beta > 0")
+    return b, int(b.size)
+
+
+def temper_layout(lengths: Sequence[int], M: int, R: int, betas=None) -> Dict:
+    """``beta`` and ``ladder`` of a tempered fit of ``K = len(lengths)`` cells of those point counts, ``M``
+    replicates and ``R`` rungs, for :func:`dram_run`: chain ``(q * M + r) * K + k`` is rung ``q`` of ladder
+    ``r * K + k`` (replicate ``r`` of cell ``k``). ``betas`` None: :func:`temper_ladder` of each cell's ``7 + N``."""
+    K = len(lengths)
+    beta = np.empty(M * R * K)
+    ladder = np.empty(M * R * K, np.int32)
+    for k, n in enumerate(lengths):
+        b = temper_ladder(7 + int(n), R) if betas is None else np.asarray(betas, np.float64)
+        for q in range(R):
+            for r in range(M):
+                beta[(q * M + r) * K + k] = b[q]
+                ladder[(q * M + r) * K + k] = r * K + k
+    return dict(beta=beta, ladder=ladder)
+
+
+def temper_entry(res: DramResult, k: int, K: int, M: int, R: int, cell_index: int) -> Dict:
+    """``MCMCtemper`` of fitted cell ``k`` from a tempered :func:`dram_run` in :func:`temper_layout`'s order."""
+    t = res.temper
+    idx = np.array([[(q * M + r) * K + k for q in range(R)] for r in range(M)])   # [M, R] chain of (replicate, rung)
+    tried = t.swap_tried[idx[:, :-1]].astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rate = np.where(tried > 0, t.swap_accepted[idx[:, :-1]] / tried, np.nan)
+    d = dict(beta=t.beta[idx[0]].copy(), swap_rate=rate, swap_tried=tried, accept_rate=res.accept_rate[idx].copy(),
+             swap_every=int(t.swap_every), n_events=int(t.n_events), n_chains=M * R, cell_index=int(cell_index))
+    return {f: d[f] for f in TEMPER_FIELDS}
 
 
 def stack_entries(lk, chain: np.ndarray, s2chain: np.ndarray, mean: np.ndarray, keep: Sequence[int], M: int,
