@@ -10,7 +10,7 @@ For each this measures
   * a numpy evaluation of the same statistics on the copied rows (means, variances, the two factors),
   * the run's wall time with the replicates and with one chain per cell (median of three runs each, without the
     copy of the kept rows; with it, as fit() runs, once), and the engine AUTO's rule gives for either (not read from
-    the run: the walk engine above two chains per compute unit, tci_api.cpp),
+    the run: the walk engine above two chains per compute unit, tci_api_dram.cpp),
 checks the device result against the longdouble restatement of tests/chainrhat_oracle.py within its bound (on
 --oracle-groups groups), and writes profiles/chainrhat/chainrhat_time.json.
 
