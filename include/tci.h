@@ -954,6 +954,77 @@ int tci_dram_run_tempered(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_c
                           const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_temper_options* topt,
                           tci_temper_outputs* tout);
 
+/* ---- Population mode search per cell before sampling (differential evolution, Storn and Price 1997) ----
+ * Replicate chains of a cell settle in separate modes, and every chain starts from one draw of the reference's x0
+ * distribution (TranscriptionCycleMCMC.m:200-210). This looks for a good mode first. The SS is discontinuous in theta
+ * (floor and strict masks), so the search uses SS values alone: DE/rand/1/bin on the batched likelihood kernel.
+ * For each selected cell k in [0, n_sel), P = 7 + N of cell cell_id[k], a population of n_pop members (theta rows of ld
+ * doubles) runs n_gen generations. All in FP64, every operation rounded once as written, never fused.
+ * Objective. f = ss / s2[k] + pri: ss the bits of tci_ss_batch_async on the row, pri exactly tci_chainlp's pri_t (the
+ *   same 64-partial order, the same sig = +Inf rule, the same device code), s2[k] a per-cell input (the reference's
+ *   model.sigma2 is 1).
+ * Generation 0 evaluates f of every member of pop0.
+ * Generation g = 1 .. n_gen, member i. All members read the population as it stood after generation g - 1
+ * (synchronous DE). rng(seed, key, step, purpose, idx) is the sampler's Philox4x32-10 stream with the counter
+ * (key, step, purpose, idx); purposes 1-6 are the sampler's. m(w, n) = (uint32)(((uint64)w * n) >> 32).
+ *   Index draw. w = rng(seed, key[k], g, 7, i):
+ *     r1 = m(w.x, n_pop - 1), then + 1 if >= i;
+ *     r2 = m(w.y, n_pop - 2), then, over {i, r1} sorted ascending, + 1 for each excluded value it has reached, tested
+ *          in ascending order;
+ *     r3 = m(w.z, n_pop - 3), the same over {i, r1, r2};
+ *     jrand = m(w.w, P).
+ *   Crossover uniform of coordinate j. c = rng(seed, key[k], g, 8, i * 2048 + (j >> 1)); u_j = u01(c.x, c.y) for even
+ *     j, u01(c.z, c.w) for odd j, u01(a, b) = ((double)((((uint64)a << 32) | b) >> 11) + 0.5) * 2^-53 as in the sampler.
+ *     P <= 7 + TCI_MAX_POINTS = 2055, so j >> 1 < 2048 and no two members of a cell share a counter.
+ *   Mutant.  v_j = x[r1][j] + F * (x[r2][j] - x[r3][j]): a subtraction, a multiplication, an addition.
+ *   Trial.   t_j = v_j when (u_j < CR || j == jrand) and v_j >= lower_j && v_j <= upper_j; else t_j = x[i][j]: a NaN or
+ *     out-of-bounds mutant coordinate keeps the parent's, so a trial is always in bounds and always evaluated. Entries
+ *     j >= P are copied from the parent.
+ *   Selection. The trial replaces the parent iff f_trial <= f_parent; a NaN f_trial never replaces.
+ * best[k] is the member that comes first when the members are ordered by (f is NaN, f, index): the least index whose f
+ * is the least, compared on the device's own values, a NaN f after every number.
+ * Bits. A cell's outputs depend on its population, data, bounds, priors, s2, key, seed and options alone: not on n_sel,
+ * the cell's position, ld, the launch shapes or how many generations share a launch. ss is the likelihood kernel's and
+ * pri tci_chainlp's; everything else is exact in the stated order, so a float64 restatement that takes ss from the
+ * kernel gives every output's bits (tests/modesearch_oracle.py). */
+typedef struct {
+  int64_t n_gen;       /* generations, >= 0; default 500 */
+  double F;            /* differential weight, finite and in (0, 2]; default 0.5 */
+  double CR;           /* crossover rate in [0, 1]; default 0.9 */
+  uint64_t seed;
+  const int64_t* keys; /* optional [n_sel]: cell k draws from RNG stream keys[k] (NULL: stream k), taken modulo 2^32 as
+                          tci_dram_options.chain_keys is. Keying by the dataset-wide cell index makes a shard of a
+                          search reproduce the unsharded one */
+  int64_t flags;       /* reserved, must be 0 */
+} tci_modesearch_options;
+
+/* Host buffers (any pointer may be NULL). */
+typedef struct {
+  double *pop;                            /* [n_sel][n_pop][ld]: the final population */
+  double *f, *ss;                         /* [n_sel][n_pop]: of the final population */
+  int32_t* best;                          /* [n_sel] */
+  double* theta_best;                     /* [n_sel][ld]; padding (j >= P) is NaN */
+  double *f_best, *ss_best, *pri_best;    /* [n_sel] */
+  double* f_trace;                        /* [n_gen + 1][n_sel]: the least f after each generation (row 0: pop0's) */
+  int32_t* n_accepted;                    /* [n_gen][n_sel]: trials that replaced their parent */
+  int64_t n_evals;   /* written: SS evaluations, n_sel * n_pop * (n_gen + 1) */
+  double kernel_ms;  /* written: device time of the search (HIP events), the likelihood launches included */
+} tci_modesearch_outputs;
+
+int tci_modesearch_defaults(tci_modesearch_options* opt);
+
+/* HOST pointers, synchronous. pop0 is [n_sel][n_pop][ld]; lower, upper, prior_mu and prior_sig are [n_sel][ld] as for
+ * tci_dram_run; s2 is [n_sel]. opt may be NULL (the defaults); out is required. Checked in this order, all before any
+ * device work: TCI_EINVAL for a null argument, n_sel < 1, flags != 0, n_gen < 0, F not finite or outside (0, 2], CR
+ * outside [0, 1] or NaN, n_pop outside [4, 4096] or n_sel * n_pop at or above 2^31; TCI_ERANGE for ld outside
+ * [1, 2^24]; TCI_EINVAL for (n_gen + 1) * n_sel at or above 2^31 (the traces); TCI_ERANGE for a cell id out of
+ * range or ld < 7 + N of a selected cell; TCI_EINVAL, naming the cell and the index, for a prior tci_chainlp refuses
+ * and an s2 entry that is not finite and > 0; TCI_EINVAL, naming cell, member and index, for a pop0 entry with j < P
+ * that is not finite or lies outside [lower_j, upper_j]. TCI_ENOMEM when the populations do not fit the device. */
+int tci_modesearch(tci_ctx* ctx, const tci_modesearch_options* opt, const double* pop0, int64_t ld,
+                   const int32_t* cell_id, int64_t n_sel, int64_t n_pop, const double* lower, const double* upper,
+                   const double* prior_mu, const double* prior_sig, const double* s2, tci_modesearch_outputs* out);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

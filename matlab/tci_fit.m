@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -53,6 +53,13 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtem
 %        seventh output MCMCtemper, one entry per fitted cell: beta (1 x R), swap_rate and swap_tried (1 x R-1, per
 %        pair of neighbouring rungs; NaN for a pair never tried), accept_rate (1 x R), swap_every, n_events, cell_index.
 %        Not with 'logpost' or 'stack'.)
+%     'presearch' ([]; [n_pop n_gen] runs a mode search before the chains start: differential evolution on
+%        ss/sigma2 + prior over n_pop members per fitted cell for n_gen generations on the device
+%        (tci_mex('modesearch'); include/tci.h). Member 1 of a cell is its usual x0, the others are drawn as x0
+%        is; the search is seeded as the sampler is and keyed by cellNum - 1. The cell's chain, and with 'temper'
+%        every rung of its ladder, starts from the best member. Fills the eighth output MCMCsearch, one entry per
+%        fitted cell: f_best, ss_best, theta_best (1 x 7+N), f0_best (the best of the initial population), f_trace
+%        (1 x n_gen+1), n_gen, n_pop, n_evals, cell_index.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -84,6 +91,7 @@ p.addParameter('logpost', 0);
 p.addParameter('stack', 0);
 p.addParameter('temper', 1);
 p.addParameter('swap_every', 1);
+p.addParameter('presearch', []);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -211,6 +219,34 @@ if R > 1                                            % the hot rungs: columns r*n
     cols = repmat(1:nc, 1, R);
 end
 sigma2_0 = 1;                                       % :212, :259
+MCMCsearch = struct([]);
+search = [];
+if ~isempty(o.presearch)                            % the mode search: every chain of a cell starts from its best member
+    ps = o.presearch;
+    if ~(isnumeric(ps) && numel(ps) == 2 && all(ps == floor(ps)) && ps(1) >= 4 && ps(1) <= 4096 && ps(2) >= 0)
+        error('tci:presearch', 'presearch must be [n_pop n_gen] with n_pop in [4, 4096] and n_gen >= 0');
+    end
+    n_pop = ps(1);
+    POP0 = zeros(P, n_pop*nc);
+    for k = 1:nc
+        n = numel(setup(k).t);
+        POP0(:, (k-1)*n_pop + 1) = X0(:, k);
+        for i = 2:n_pop
+            x = setup(k).x0;
+            if ~loadPrevious
+                x(1) = 1+2*rand;
+            end
+            x(3) = 4*rand; x(6) = rand; x(2) = 4*rand; x(8:end) = normrnd(0,3,1,n);
+            POP0(1:7+n, (k-1)*n_pop + i) = x;
+        end
+    end
+    search = tci_mex('modesearch', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), sigma2_0, ...
+        struct('n_gen', ps(2), 'seed', o.seed*1000003 + 20201028, 'keys', [setup.cellNum] - 1));
+    for c = 1:numel(cols)
+        k = cols(c);
+        X0(:, c) = search.pop(:, search.best(k), k);
+    end
+end
 options = struct('nsimu', n_steps, 'burnintime', n_burn, 'adaptint', 100, 'method', 'dram', ...  % :263-270
     'updatesigma', 1, 'verbosity', 0, 'stats_from', max(n_burn, 1), 'thin', o.thin, ...
     'seed', o.seed*1000003 + 20201028, 'engine', o.engine, 'adapt_pmax', o.adapt_pmax, ...
@@ -334,6 +370,13 @@ for k = 1:nc
             'stacked_mean', T.weight(k)*results.mean(1:7+n, k)', 'n_samples', numel(T.rows), ...
             'cell_index', setup(k).cellNum);
         if isempty(MCMCstack), MCMCstack = sk; else, MCMCstack(k) = sk; end
+    end
+    if ~isempty(search)
+        qk = struct('f_best', search.f_best(k), 'ss_best', search.ss_best(k), 'theta_best', search.theta_best(1:7+n, k)', ...
+            'f0_best', search.f_trace(k, 1), 'f_trace', search.f_trace(k, :), 'n_gen', size(search.f_trace, 2) - 1, ...
+            'n_pop', size(search.pop, 2), 'n_evals', size(search.pop, 2)*size(search.f_trace, 2), ...
+            'cell_index', setup(k).cellNum);
+        if isempty(MCMCsearch), MCMCsearch = qk; else, MCMCsearch(k) = qk; end
     end
     if R > 1
         T = results.temper;

@@ -108,6 +108,18 @@
 //          NaN), theta_best, theta_mean (P x n; NaN past a chain's 7 + N), n_rows and kernel_ms. With
 //          options.logpost = true 'dram' attaches the same struct, of the kept rows at or past stats_from, to its
 //          first output as res.logpost (the rows are kept on the device for it even when no chain output is asked for).
+//   out = tci_mex('modesearch', h, cells, POP0, LB, UB, MU, SIG[, s2[, options]])
+//          differential evolution on f = ss / s2 + prior over a population per entry of cells (tci_modesearch, the
+//          definition is in include/tci.h). POP0 is P x (n_pop * n), n = numel(cells): column (k - 1) * n_pop + i is
+//          member i of cells(k) (reshape(POP0, P, n_pop, n)); LB, UB, MU, SIG are P x n as for 'dram'; s2 a scalar or
+//          one per entry (default 1). options: n_gen (500), F (0.5), CR (0.9), seed (0), keys (1 x n RNG stream keys,
+//          default 0 .. n - 1). out: pop (P x n_pop x n), f and ss (n_pop x n), best (1 x n, 1-based), theta_best
+//          (P x n), f_best, ss_best, pri_best (1 x n), f_trace (n x n_gen + 1), n_accepted (n x n_gen), n_evals,
+//          kernel_ms.
+//   options.presearch of 'dram': a population P x (n_pop * n) laid out as POP0 above, one per chain. The search runs
+//          first (options.presearch_gen generations, default 500, options.presearch_F, options.presearch_CR; seeded by
+//          options.seed and keyed by options.chain_keys) and chain c starts from the best final member of its
+//          population instead of X0(:, c). res.presearch is the struct 'modesearch' returns.
 //   options.temper of 'dram': parallel tempering (tci_dram_run_tempered, include/tci.h). A 2 x n matrix [beta; ladder]
 //          (ladder ids 1-based, 0 = the chain is in no ladder; the chains of a ladder in column order are its rungs,
 //          cold first) or 1 x n (beta alone); options.swap_every (1; 0 = never) is the number of adaptation windows
@@ -720,6 +732,59 @@ struct LpOut {
   }
 };
 
+// The struct of 'modesearch' and of 'dram''s res.presearch, written in place by the ABI: pop P x n_pop x n ==
+// [cell][member][P], f and ss n_pop x n, the traces n x generations == [generation][cell]; best 1-based.
+struct SearchOut {
+  mxArray* res;
+  std::vector<int32_t> best, nacc;
+  size_t n, G;
+  tci_modesearch_outputs out;
+  SearchOut(size_t P, size_t n_pop, size_t n_, size_t G_) : best(n_), nacc(n_ * G_), n(n_), G(G_) {
+    static const char* fields[] = {"pop", "f", "ss", "theta_best", "f_best", "ss_best", "pri_best", "f_trace", "best",
+                                   "n_accepted", "n_evals", "kernel_ms"};
+    res = mxCreateStructMatrix(1, 1, 12, fields);
+    const mwSize d3[3] = {P, n_pop, n};
+    mxArray* a[8] = {mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), mxCreateDoubleMatrix(n_pop, n, mxREAL),
+                     mxCreateDoubleMatrix(n_pop, n, mxREAL), mxCreateDoubleMatrix(P, n, mxREAL),
+                     mxCreateDoubleMatrix(1, n, mxREAL), mxCreateDoubleMatrix(1, n, mxREAL),
+                     mxCreateDoubleMatrix(1, n, mxREAL), mxCreateDoubleMatrix(n, G + 1, mxREAL)};
+    for (int k = 0; k < 8; ++k) mxSetField(res, 0, fields[k], a[k]);
+    memset(&out, 0, sizeof out);
+    out.pop = mxGetPr(a[0]);
+    out.f = mxGetPr(a[1]);
+    out.ss = mxGetPr(a[2]);
+    out.theta_best = mxGetPr(a[3]);
+    out.f_best = mxGetPr(a[4]);
+    out.ss_best = mxGetPr(a[5]);
+    out.pri_best = mxGetPr(a[6]);
+    out.f_trace = mxGetPr(a[7]);
+    out.best = best.data();
+    out.n_accepted = G ? nacc.data() : nullptr;
+  }
+  mxArray* finish() {
+    mxArray* b = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t c = 0; c < n; ++c) mxGetPr(b)[c] = (double)(best[c] + 1);
+    mxArray* na = mxCreateDoubleMatrix(n, G, mxREAL);
+    for (size_t i = 0; i < n * G; ++i) mxGetPr(na)[i] = (double)nacc[i];
+    mxSetField(res, 0, "best", b);
+    mxSetField(res, 0, "n_accepted", na);
+    mxSetField(res, 0, "n_evals", mxCreateDoubleScalar((double)out.n_evals));
+    mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+    return res;
+  }
+};
+
+// A population P x (n_pop * n), n_pop members per entry; *n_pop: the members per entry.
+const double* pop_matrix(const mxArray* a, const char* what, size_t P, size_t n, size_t* n_pop) {
+  if (!mxIsDouble(a) || mxIsComplex(a) || mxIsSparse(a)) mexErrMsgIdAndTxt("tci:arg", "%s must be real double", what);
+  const size_t total = mxGetNumberOfElements(a);
+  if (mxGetM(a) != P || total == 0 || total % (P * n) != 0)
+    mexErrMsgIdAndTxt("tci:arg", "%s must be %d x (n_pop * %d): n_pop members per entry of cells, as columns", what, (int)P,
+                      (int)n);
+  *n_pop = total / (P * n);
+  return mxGetPr(a);
+}
+
 void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (nrhs < 10 || nrhs > 11)
     mexErrMsgIdAndTxt("tci:arg", "tci_mex('dram', h, cells, X0, LB, UB, MU, SIG, J0, sigma2[, options])");
@@ -754,7 +819,8 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"nsimu", "burnintime", "adaptint", "method", "updatesigma", "drscale", "adascale",
                                   "qcovadj", "burnin_scale", "stats_from", "thin", "seed", "engine", "max_chunk",
-                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "temper", "swap_every", "verbosity",
+                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "temper", "swap_every", "presearch", "presearch_gen",
+                                  "presearch_F", "presearch_CR", "verbosity",
                                   "waitbar",
                                   "printint"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
@@ -864,18 +930,44 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     }
     opt.chain_keys = keys.data();
   }
+  // options.presearch: a population per chain; the chain starts from the best member the search leaves
+  const mxArray* pm = o ? mxGetField(o, 0, "presearch") : nullptr;
+  const bool want_ps = pm != nullptr && mxGetNumberOfElements(pm) != 0;
+  tci_modesearch_options mopt;
+  tci_modesearch_defaults(&mopt);
+  mopt.n_gen = opt_int(o, "presearch_gen", mopt.n_gen, 0);
+  mopt.F = opt_num(o, "presearch_F", mopt.F);
+  mopt.CR = opt_num(o, "presearch_CR", mopt.CR);
+  mopt.seed = opt.seed;
+  mopt.keys = opt.chain_keys;
+  size_t ps_pop = 0;
+  const double* ps_x = want_ps ? pop_matrix(pm, "options.presearch", P, n, &ps_pop) : nullptr;
 
   tci_ctx* ctx = handle_of(prhs[1]);
+  mxArray* ps_res = nullptr;
+  std::vector<double> ps_x0;
+  if (want_ps) {
+    SearchOut ms(P, ps_pop, n, (size_t)mopt.n_gen);
+    const int rcs = tci_modesearch(ctx, &mopt, ps_x, (int64_t)P, cid.data(), (int64_t)n, (int64_t)ps_pop, in[1], in[2],
+                                   in[3], in[4], s2v.data(), &ms.out);
+    if (rcs != TCI_OK) {
+      mxDestroyArray(ms.res);
+      check(ctx, rcs, "tci_modesearch");
+    }
+    ps_x0.resize(P * n);
+    for (size_t b = 0; b < n; ++b)
+      memcpy(&ps_x0[b * P], ms.out.pop + (b * ps_pop + (size_t)ms.best[b]) * P, P * sizeof(double));
+    in[0] = ps_x0.data();
+    ps_res = ms.finish();
+  }
   // outputs, written in place: the ABI's row-major [chain][P] is MATLAB's column-major P x n
-  static const char* fields[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
-                                 "elapsed_ms", "logpost", "stack"};
-  static const char* fields_tm[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
-                                    "elapsed_ms", "temper", "stack"};
-  static const char* fields_st[] = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
-                                    "elapsed_ms", "stack"};
-  mxArray* res = want_temper       ? mxCreateStructMatrix(1, 1, 9 + (stack ? 1 : 0), fields_tm)
-                 : stack && !want_lp ? mxCreateStructMatrix(1, 1, 9, fields_st)
-                                   : mxCreateStructMatrix(1, 1, 8 + (want_lp ? 1 : 0) + (stack ? 1 : 0), fields);
+  std::vector<const char*> fields = {"mean", "std", "final_theta", "sigma_mean", "sigma_std", "accept_rate", "n_evals",
+                                     "elapsed_ms"};
+  if (want_temper) fields.push_back("temper");
+  else if (want_lp) fields.push_back("logpost");
+  if (stack) fields.push_back("stack");
+  if (want_ps) fields.push_back("presearch");
+  mxArray* res = mxCreateStructMatrix(1, 1, (int)fields.size(), fields.data());
   mxArray* pn[6];
   for (int k = 0; k < 3; ++k) pn[k] = mxCreateDoubleMatrix(P, n, mxREAL);
   for (int k = 3; k < 6; ++k) pn[k] = mxCreateDoubleMatrix(1, n, mxREAL);
@@ -956,6 +1048,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (ch) mxDestroyArray(ch);
     if (s2c) mxDestroyArray(s2c);
     if (t_logr) mxDestroyArray(t_logr);
+    if (ps_res) mxDestroyArray(ps_res);
     check(ctx, rc, "tci_dram_run");
   }
   if (want_temper) {
@@ -1031,6 +1124,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       mxDestroyArray(res);
       if (ch) mxDestroyArray(ch);
       if (s2c) mxDestroyArray(s2c);
+      if (ps_res) mxDestroyArray(ps_res);
       check(ctx, rc2, "tci_loocheck");
     }
     so2.finish();
@@ -1042,6 +1136,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxSetField(so2.res, 0, "rows", rm);
     mxSetField(res, 0, "stack", so2.res);
   }
+  if (want_ps) mxSetField(res, 0, "presearch", ps_res);
   plhs[0] = res;
   if (nlhs >= 2) plhs[1] = ch;
   if (nlhs >= 3) plhs[2] = s2c;
@@ -1478,6 +1573,79 @@ void cmd_chainlp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = lo.finish();
 }
 
+// ---- 'modesearch': differential evolution over a population per cell ----------------------------------
+
+void cmd_modesearch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs < 8 || nrhs > 10)
+    mexErrMsgIdAndTxt("tci:arg", "tci_mex('modesearch', h, cells, POP0, LB, UB, MU, SIG[, s2[, options]])");
+  // every argument and option is checked before the handle (and before anything reaches the GPU)
+  const size_t n = mxGetNumberOfElements(prhs[2]);
+  const double* c = doubles(prhs[2], -1, "cells");
+  if (n == 0) mexErrMsgIdAndTxt("tci:arg", "cells must name at least one cell");
+  std::vector<int32_t> cid(n);
+  for (size_t b = 0; b < n; ++b) {
+    if (!(c[b] >= 1 && c[b] <= 2147483647.0) || c[b] != (double)(int64_t)c[b])
+      mexErrMsgIdAndTxt("tci:arg", "cells(%d) must be a positive integer", (int)b + 1);
+    cid[b] = (int32_t)c[b] - 1;
+  }
+  if (!mxIsDouble(prhs[4]) || mxGetNumberOfDimensions(prhs[4]) != 2 || mxGetN(prhs[4]) != n)
+    mexErrMsgIdAndTxt("tci:arg", "LB must be P x n: one column per entry of cells");
+  const size_t P = mxGetM(prhs[4]);
+  if (P < 7) mexErrMsgIdAndTxt("tci:arg", "LB must have at least 7 rows ([v, tau, ton, MS2_basal, PP7_basal, A, R, dR])");
+  const char* names[4] = {"LB", "UB", "MU", "SIG"};
+  const double* in[4];
+  for (int k = 0; k < 4; ++k) in[k] = chain_matrix(prhs[4 + k], names[k], P, n);
+  size_t n_pop = 0;
+  const double* pop = pop_matrix(prhs[3], "POP0", P, n, &n_pop);
+  std::vector<double> s2v(n, 1.0);
+  if (nrhs > 8 && mxGetNumberOfElements(prhs[8]) != 0) {
+    const size_t ns2 = mxGetNumberOfElements(prhs[8]);
+    const double* s2 = doubles(prhs[8], -1, "s2");
+    if (ns2 != 1 && ns2 != n) mexErrMsgIdAndTxt("tci:arg", "s2 must be a scalar or have one entry per entry of cells");
+    for (size_t b = 0; b < n; ++b) s2v[b] = s2[ns2 == 1 ? 0 : b];
+  }
+  const mxArray* o = nullptr;
+  if (nrhs > 9 && !(mxIsDouble(prhs[9]) && mxGetNumberOfElements(prhs[9]) == 0)) {  // [] = defaults
+    if (!mxIsStruct(prhs[9]) || mxGetNumberOfElements(prhs[9]) != 1)
+      mexErrMsgIdAndTxt("tci:opts", "options must be a 1x1 struct");
+    o = prhs[9];
+    static const char* known[] = {"n_gen", "F", "CR", "seed", "keys"};
+    for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
+      const char* fn = mxGetFieldNameByNumber(o, f);
+      bool ok = false;
+      for (const char* k : known) ok = ok || strcmp(fn, k) == 0;
+      if (!ok) mexErrMsgIdAndTxt("tci:opts", "options.%s is not an option of tci_mex('modesearch')", fn);
+    }
+  }
+  tci_modesearch_options mopt;
+  tci_modesearch_defaults(&mopt);
+  mopt.n_gen = opt_int(o, "n_gen", mopt.n_gen, 0);
+  mopt.F = opt_num(o, "F", mopt.F);
+  mopt.CR = opt_num(o, "CR", mopt.CR);
+  mopt.seed = (uint64_t)opt_int(o, "seed", 0, 0);
+  std::vector<int64_t> keys;
+  if (const mxArray* k = o ? mxGetField(o, 0, "keys") : nullptr) {
+    const double* kv = doubles(k, (long long)n, "options.keys");
+    keys.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(kv[b] >= 0 && kv[b] <= 9.0e15) || kv[b] != (double)(int64_t)kv[b])
+        mexErrMsgIdAndTxt("tci:opts", "options.keys(%d) must be a non-negative integer", (int)b + 1);
+      keys[b] = (int64_t)kv[b];
+    }
+    mopt.keys = keys.data();
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  SearchOut ms(P, n_pop, n, (size_t)mopt.n_gen);
+  const int rc = tci_modesearch(ctx, &mopt, pop, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, in[0], in[1], in[2],
+                                in[3], s2v.data(), &ms.out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(ms.res);
+    check(ctx, rc, "tci_modesearch");
+  }
+  plhs[0] = ms.finish();
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -1503,6 +1671,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chainrhat") cmd_chainrhat(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainess") cmd_chainess(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainlp") cmd_chainlp(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "modesearch") cmd_modesearch(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

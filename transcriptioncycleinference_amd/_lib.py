@@ -161,6 +161,17 @@ class tci_temper_outputs(C.Structure):
                 ("swap_log_rows", C.c_int64), ("n_events", C.c_int64)]
 
 
+class tci_modesearch_options(C.Structure):
+    _fields_ = [("n_gen", C.c_int64), ("F", C.c_double), ("CR", C.c_double), ("seed", C.c_uint64),
+                ("keys", C.POINTER(C.c_int64)), ("flags", C.c_int64)]
+
+
+class tci_modesearch_outputs(C.Structure):
+    _fields_ = [("pop", _dp), ("f", _dp), ("ss", _dp), ("best", _i32p), ("theta_best", _dp), ("f_best", _dp),
+                ("ss_best", _dp), ("pri_best", _dp), ("f_trace", _dp), ("n_accepted", _i32p), ("n_evals", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
 class tci_fitcheck_options(C.Structure):
     _fields_ = [("scratch_bytes", C.c_int64), ("n_levels", C.c_int32), ("levels", C.c_double * 8)]
 
@@ -266,6 +277,9 @@ SIGNATURES = [
                                         C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
                                         C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                         C.POINTER(tci_temper_options), C.POINTER(tci_temper_outputs)]),
+    ("tci_modesearch_defaults", C.c_int, [C.POINTER(tci_modesearch_options)]),
+    ("tci_modesearch", C.c_int, [C.c_void_p, C.POINTER(tci_modesearch_options), _dp, C.c_int64, _i32p, C.c_int64,
+                                 C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_modesearch_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

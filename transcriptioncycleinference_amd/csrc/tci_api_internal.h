@@ -1,5 +1,6 @@
 // tci_api_internal.h -- what the host translation units of the C ABI share (tci_api.cpp: context and likelihood,
-// tci_api_chain.cpp: the reductions of a stored chain, tci_api_dram.cpp: the sampler). No .hip file includes it.
+// tci_api_chain.cpp: the reductions of a stored chain, tci_api_dram.cpp: the sampler, tci_api_search.cpp: the mode
+// search). No .hip file includes it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -136,6 +137,7 @@ struct EventTimer {
 // time between the events. `what`: the nouns of the three HIP failures, the launch's, the kernels' and the copies'.
 struct LaunchNouns {
   const char *launch, *kernel, *copy;
+  const char* refused = nullptr;  // what a launch wrapper's own refusal means (null: the chain reductions' size limit)
 };
 struct CopyBack {
   void* dst;
@@ -159,7 +161,8 @@ int timed_launch(tci_ctx* ctx, const char* who, const LaunchNouns& what, Launch&
   *ms = 0.f;
   if (rc == TCI_OK && e1 == hipSuccess && e2 == hipSuccess) e1 = timer.elapsed_ms(ms);
   if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), what.launch);
-  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (rc != TCI_OK)
+    return fail(ctx, rc, std::string(who) + ": " + (what.refused ? what.refused : "rows x chains x ld too large for one launch"));
   if (e2 != hipSuccess) return hip_fail(ctx, e2, what.kernel);
   if (e1 != hipSuccess) return hip_fail(ctx, e1, what.copy);
   return TCI_OK;

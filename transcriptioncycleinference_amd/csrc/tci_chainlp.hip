@@ -8,7 +8,8 @@
 //
 //   k_chainlp_ids     the cell id of every (row, chain).
 //   k_chainlp_rows    one wavefront per (row, chain): lane l sums the prior terms j = l, l + 64, .. in ascending j, the
-//                     64 partials are added in ascending lane order by every lane alike; lane 0 then forms dev and lp.
+//                     64 partials are added in ascending lane order by every lane alike (tci_prior.h); lane 0 then
+//                     forms dev and lp.
 //   k_chainlp_reduce  one workgroup per chain. The rows are cut into segments of kLpSeg rows (the count and the
 //                     boundaries follow from n alone); a thread reduces whole segments, row by row in order, and
 //                     stores every segment's partial results; thread 0 adds them in segment order. A second pass
@@ -21,6 +22,7 @@
 #include <cmath>
 
 #include "tci_internal.h"
+#include "tci_prior.h"
 
 namespace tci {
 
@@ -68,15 +70,7 @@ __global__ __launch_bounds__(kLpThreads) void k_chainlp_rows(const CellMeta* __r
   const double* th = chain + b * ld;
   const double* m = mu + c * ld;
   const double* sg = sig + c * ld;
-  double part = 0.0;
-  for (int j = lane; j < P; j += 64) {
-    const double d = th[j] - m[j];
-    const double q = d / sg[j];
-    part += q * q;
-  }
-  double tot = 0.0;
-#pragma unroll
-  for (int l = 0; l < 64; ++l) tot += __shfl(part, l, 64);
+  const double tot = prior_sum64(th, m, sg, P, lane);
   if (lane == 0) {
     const double d = lp_deviance(ss[b], s2[b], (double)(2 * N));
     pri[b] = tot;

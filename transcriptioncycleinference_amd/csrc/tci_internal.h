@@ -210,4 +210,24 @@ int launch_chainlp_reduce(const KParams& kp, const double* chain, const double* 
                           double* theta_mean, void* stream);
 int chainlp_scratch_bytes(int64_t n_rows, int64_t n_chains, int64_t ld, size_t* bytes);
 
+// One generation of the mode search (tci_modesearch.hip) on a device population [n_sel][n_pop][ld]; f, ss and pri are
+// [n_sel * n_pop], laid out as the rows are. cell_id, s2, keys (device): [n_sel], valid ids of cells with 7 + N <= ld
+// (the host checks); lower, upper, mu, sig (device): [n_sel][ld]. 4 <= n_pop <= 4096 and n_sel * n_pop below 2^31
+// (TCI_ERANGE). Asynchronous on `stream`; TCI_EINVAL on a bad size or a null pointer, TCI_EHIP on a HIP error.
+//   launch_modesearch_trial   gen == 0: pri of every member of pop (keys, lower, upper and trial are not read). gen >= 1:
+//                             the trial of every member into trial [n_sel * n_pop][ld] and the trial's prior into pri.
+//                             The caller then launches the likelihood kernel on the rows it wrote.
+//   launch_modesearch_select  gen == 0: f = ss / s2 + pri of every member (trial, ss_t, pri_t, n_acc are not read). gen >= 1:
+//                             an accepted trial replaces its parent in pop, f, ss, pri; n_acc [n_sel] counts them. Both:
+//                             best [n_sel] and f_trace [n_sel] (this generation's row); with final_gen also theta_best
+//                             [n_sel][ld] and best_vals [3][n_sel] = f, ss, pri of the best member.
+int launch_modesearch_trial(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* pop,
+                            const double* lower, const double* upper, const double* mu, const double* sig, int64_t n_sel,
+                            int64_t n_pop, int64_t ld, int64_t gen, uint64_t seed, double F, double CR, double* trial,
+                            double* pri, void* stream);
+int launch_modesearch_select(const KParams& kp, const int32_t* cell_id, const double* s2, const double* trial,
+                             const double* ss_t, const double* pri_t, int64_t n_sel, int64_t n_pop, int64_t ld, int64_t gen,
+                             bool final_gen, double* pop, double* f, double* ss, double* pri, double* f_trace,
+                             int32_t* n_acc, int32_t* best, double* best_vals, double* theta_best, void* stream);
+
 }  // namespace tci

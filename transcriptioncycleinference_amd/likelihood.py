@@ -442,6 +442,42 @@ class ChainLp:
                                         0, 0.0)
 
 
+@dataclasses.dataclass
+class ModeSearch:
+    """The final population of a mode search and its best member per cell (``tci_modesearch_outputs``; the definition is
+    in ``include/tci.h``). ``pop`` ``[n_sel, n_pop, ld]`` with ``f`` and ``ss`` ``[n_sel, n_pop]``; per cell ``[n_sel]``:
+    ``best`` (int32, the least index of the least ``f``), ``f_best``, ``ss_best``, ``pri_best`` and ``theta_best``
+    ``[n_sel, ld]`` (padding NaN); ``f_trace`` ``[n_gen + 1, n_sel]``: the least ``f`` after each generation, row 0 the
+    initial population's; ``n_accepted`` ``[n_gen, n_sel]`` (int32)."""
+
+    pop: np.ndarray
+    f: np.ndarray
+    ss: np.ndarray
+    best: np.ndarray
+    theta_best: np.ndarray
+    f_best: np.ndarray
+    ss_best: np.ndarray
+    pri_best: np.ndarray
+    f_trace: np.ndarray
+    n_accepted: np.ndarray
+    n_gen: int = 0
+    n_evals: int = 0
+    kernel_ms: float = 0.0
+
+    @classmethod
+    def empty(cls, n: int, n_pop: int, ld: int, n_gen: int) -> "ModeSearch":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        return cls(d(n, n_pop, ld), d(n, n_pop), d(n, n_pop), np.full(n, -1, np.int32), d(n, ld), d(n), d(n), d(n),
+                   d(n_gen + 1, n), np.zeros((n_gen, n), np.int32), int(n_gen))
+
+    def to_c(self) -> "_lib.tci_modesearch_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        I = lambda a: _lib.ptr(a, _lib._i32p)  # noqa: E731
+        return _lib.tci_modesearch_outputs(P(self.pop), P(self.f), P(self.ss), I(self.best), P(self.theta_best),
+                                           P(self.f_best), P(self.ss_best), P(self.pri_best), P(self.f_trace),
+                                           I(self.n_accepted) if self.n_gen else None, 0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -866,6 +902,40 @@ class Likelihood:
                                           _lib.ptr(sig, _lib._dp), C.byref(out)))
         cl.n_rows, cl.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return cl
+
+    def modesearch(self, pop0: np.ndarray, cell_id: Sequence[int], lower: np.ndarray, upper: np.ndarray,
+                   prior_mu: np.ndarray, prior_sig: np.ndarray, s2=None, n_gen: int = 500, F: float = 0.5,
+                   CR: float = 0.9, seed: int = 0, keys=None, flags: int = 0) -> ModeSearch:
+        """Differential evolution (DE/rand/1/bin) on ``f = ss / s2 + prior`` over a population per cell, on the device
+        (``tci_modesearch``; the definition is in ``include/tci.h``). ``pop0`` ``[n_sel, n_pop, ld]``: the initial
+        members of every selected cell, each inside ``[lower, upper]``; ``cell_id`` one cell per population; ``lower``,
+        ``upper``, ``prior_mu``, ``prior_sig`` ``[n_sel, ld]`` as for ``dram_run``; ``s2`` ``[n_sel]`` or a scalar
+        (default 1, the reference's ``model.sigma2``); ``keys`` ``[n_sel]``: the RNG stream key of every cell (default:
+        its position). Returns a :class:`ModeSearch`."""
+        pop0 = np.ascontiguousarray(pop0, np.float64)
+        if pop0.ndim != 3:
+            raise ValueError("pop0 must be [n_sel, n_pop, ld]")
+        n, n_pop, ld = pop0.shape
+        cid = np.ascontiguousarray(np.atleast_1d(cell_id), np.int32)
+        if cid.shape != (n,):
+            raise ValueError("cell_id must have one entry per population")
+        if isinstance(n_gen, bool) or int(n_gen) != n_gen or int(n_gen) < 0:
+            raise ValueError("n_gen must be an integer >= 0")
+        f = lambda a: np.ascontiguousarray(np.asarray(a, np.float64).reshape(n, ld))  # noqa: E731
+        lo, up, mu, sig = f(lower), f(upper), f(prior_mu), f(prior_sig)
+        s2v = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if s2 is None else s2, np.float64), (n,)))
+        kv = None if keys is None else np.ascontiguousarray(keys, np.int64)
+        if kv is not None and kv.shape != (n,):
+            raise ValueError("keys must have one entry per population")
+        ms = ModeSearch.empty(n, n_pop, ld, int(n_gen))
+        opt = _lib.tci_modesearch_options(int(n_gen), float(F), float(CR), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          _lib.ptr(kv, _lib._i64p), int(flags))
+        out = ms.to_c()
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        self._check(self._lib.tci_modesearch(self._h, C.byref(opt), P(pop0), ld, _lib.ptr(cid, _lib._i32p), n, n_pop,
+                                             P(lo), P(up), P(mu), P(sig), P(s2v), C.byref(out)))
+        ms.n_evals, ms.kernel_ms = int(out.n_evals), float(out.kernel_ms)
+        return ms
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

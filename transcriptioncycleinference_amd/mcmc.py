@@ -29,7 +29,7 @@ import numpy as np
 from . import _lib
 from .data import Cells, draw_x0
 from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainLp, ChainQuant, ChainRhat, ChainStats,
-                         FitCheck, rhat_groups)
+                         FitCheck, ModeSearch, rhat_groups)
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -85,6 +85,11 @@ STACK_FIELDS = ("weights", "elpd_loo", "p_loo", "khat_max", "n_khat_bad", "elpd_
 # pair of neighbouring rungs, swap_rate [M, R - 1] (NaN for a pair never tried) with swap_tried [M, R - 1], and every
 # rung's DRAM acceptance rate, accept_rate [M, R]
 TEMPER_FIELDS = ("beta", "swap_rate", "swap_tried", "accept_rate", "swap_every", "n_events", "n_chains", "cell_index")
+# MCMCsearch (fit(..., presearch=dict(...))): the mode search that chose the chains' starts (include/tci.h,
+# tci_modesearch): the best member's f, ss and theta [7 + N], f0_best the best f of the initial population, f_trace
+# [n_gen + 1] the best f after every generation, n_evals the cell's SS evaluations
+SEARCH_FIELDS = ("f_best", "ss_best", "theta_best", "f0_best", "f_trace", "n_gen", "n_pop", "n_evals", "cell_index")
+PRESEARCH_KEYS = ("n_pop", "n_gen", "F", "CR")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -427,6 +432,7 @@ class FitResult:
     local: Optional["FitResult"] = None        # parallel.fit_sharded: this rank's own fit (raw chains, final_theta)
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
     MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
+    MCMCsearch: Optional[List[Dict]] = None    # fit(..., presearch=dict(...)): SEARCH_FIELDS per fitted cell
     MCMCtemper: Optional[List[Dict]] = None    # fit(..., temper=R): TEMPER_FIELDS per fitted cell
     MCMCstack: Optional[List[Dict]] = None     # fit(..., stack=nsample): STACK_FIELDS per fitted cell
     MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
@@ -547,7 +553,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
         rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False,
-        stack: Optional[int] = None, temper=None, swap_every: int = 1) -> FitResult:
+        stack: Optional[int] = None, temper=None, swap_every: int = 1, presearch: Optional[Mapping] = None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -625,8 +631,16 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     :func:`plan_fit` start and run on those replicates' RNG streams (so ``M * R <= 256``). The reductions and groups
     apply to the cold rungs alone: every other field of the result is the cold rungs', computed as without tempering.
     ``MCMCtemper`` holds one dict of ``TEMPER_FIELDS`` per fitted cell. ``temper=1`` or its absence is the untempered
-    fit, bit for bit."""
+    fit, bit for bit.
+
+    ``presearch``: a dict of ``n_pop`` / ``n_gen`` / ``F`` / ``CR`` (any may be left out: :func:`modesearch`'s defaults):
+    a mode search (include/tci.h, ``tci_modesearch``) runs first on :func:`search_population` of every fitted cell, which
+    holds every replicate's usual start, and replicate ``r`` of a cell starts from the ``r``-th best final member (by
+    ``f``, ties by index; needs ``replicates <= n_pop``); the rungs of a tempered replicate start from their replicate's
+    member. Everything else is unchanged. ``MCMCsearch`` holds one dict of ``SEARCH_FIELDS`` per fitted cell.
+    ``presearch=None`` (the default) takes no new code path."""
     M = int(replicates)
+    ps = _presearch_arg(presearch, M)
     betas, R = _temper_arg(temper)
     if R > 1 and (isinstance(swap_every, bool) or int(swap_every) != swap_every or int(swap_every) < 0):
         raise ValueError("swap_every must be an integer >= 0")
@@ -661,6 +675,18 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     o.n_steps, o.burnintime, o.stats_from, o.thin = int(n_steps), int(n_burn), int(max(n_burn, 1)), int(thin)
     o.seed = int(seed) * 1000003 + 20201028
     keys = replicate_keys(np.array(keep, np.int64) + off, M * R)
+    searched = None
+    if ps is not None:
+        sr, sp = modesearch(lk, seed=seed, cells=keep, v0=v0, cell_offset=off, ratePriorWidth=ratePriorWidth, **ps)
+        if sp.cells != keep:   # row k of the search must be fitted cell k
+            raise RuntimeError(f"presearch searched cells {sp.cells}, the fit keeps {keep}")
+        searched = [search_entry(sr, k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
+        for k, c in enumerate(keep):
+            P = 7 + int(cl.lengths[c])
+            order = search_order(sr.f[k])
+            for q in range(R):
+                for r in range(M):
+                    plan.x0[(q * M + r) * K + k, :P] = sr.pop[k, order[r], :P]
     tk = {}
     if R > 1:
         tk = temper_layout([int(cl.lengths[c]) for c in keep], M, R, betas)
@@ -754,8 +780,90 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         stk = stack_entries(lk, res.chain[rows_idx >= max(n_burn, 1)], res.s2chain, res.mean, keep, M, int(stack), off)
     return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
                      res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMClp=lps, MCMCess=es,
-                     MCMCrhat=rh, MCMCstack=stk, MCMCtemper=tempers,
+                     MCMCrhat=rh, MCMCstack=stk, MCMCtemper=tempers, MCMCsearch=searched,
                      MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
+
+
+def _presearch_arg(presearch, replicates: int):
+    """``fit``'s ``presearch`` as keyword arguments of :func:`modesearch`, or None."""
+    if presearch is None:
+        return None
+    if not isinstance(presearch, Mapping):
+        raise ValueError(f"presearch must be a dict with keys among {PRESEARCH_KEYS}")
+    bad = sorted(set(presearch) - set(PRESEARCH_KEYS))
+    if bad:
+        raise ValueError(f"presearch has unknown keys {bad}: the keys are {PRESEARCH_KEYS}")
+    ps = dict(presearch)
+    n_pop = ps.setdefault("n_pop", 64)
+    if isinstance(n_pop, bool) or int(n_pop) != n_pop or not 4 <= int(n_pop) <= 4096:
+        raise ValueError("presearch n_pop must be an integer in [4, 4096]")
+    if int(replicates) > int(n_pop):
+        raise ValueError("presearch starts replicate r from the r-th best member: replicates must be <= n_pop")
+    n_gen = ps.get("n_gen", 0)
+    if isinstance(n_gen, bool) or int(n_gen) != n_gen or int(n_gen) < 0:
+        raise ValueError("presearch n_gen must be an integer >= 0")
+    return ps
+
+
+@dataclass
+class SearchPlan:
+    """The initial population of a mode search (:func:`search_population`): ``pop0`` ``[K, n_pop, ld]`` for the ``K``
+    cells ``cells`` (0-based, skipped cells removed) with their bounds and priors ``[K, ld]``."""
+
+    cells: List[int]
+    pop0: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    prior_mu: np.ndarray
+    prior_sig: np.ndarray
+
+
+def search_population(cl: Cells, ids: Sequence[int], seed: int, n_pop: int, ratePriorWidth: float = 50.0, v0=None,
+                      approved=None, cell_offset: int = 0) -> SearchPlan:
+    """The initial population of the mode search for the cells ``ids`` (host only): member ``i`` of a cell is the x0 of
+    replicate ``i`` of :func:`plan_fit` (member 0 from ``default_rng([seed, g])``, member ``i >= 1`` from
+    ``default_rng([seed, g, i])``, ``g`` the dataset-wide cell index), so the population holds every replicate's start
+    of a fit of up to ``n_pop`` replicates. Bounds, priors and a hierarchical ``v0`` are :func:`plan_fit`'s."""
+    n_pop = int(n_pop)
+    plan = plan_fit(cl, ids, seed, ratePriorWidth, v0, approved, cell_offset=cell_offset, replicates=n_pop)
+    K = len(plan.cells)
+    ld = plan.x0.shape[1]
+    pop0 = np.ascontiguousarray(plan.x0.reshape(n_pop, K, ld).transpose(1, 0, 2))
+    return SearchPlan(plan.cells, pop0, plan.lower[:K].copy(), plan.upper[:K].copy(), plan.prior_mu[:K].copy(),
+                      plan.prior_sig[:K].copy())
+
+
+def modesearch(lk, n_pop: int = 64, n_gen: int = 500, seed: int = 0, cells: Optional[Sequence[int]] = None, v0=None,
+               cell_offset: int = 0, ratePriorWidth: float = 50.0, F: float = 0.5, CR: float = 0.9, s2=1.0,
+               approved=None):
+    """A mode search (``Likelihood.modesearch``) from :func:`search_population` of the cells ``cells`` (default: all) of
+    ``lk``. Everything random is keyed by the dataset-wide cell index (the population by ``default_rng``, the search by
+    RNG stream ``cell_offset + cell``) and seeded as :func:`fit` seeds its sampler, so a shard reproduces its cells of
+    the full search bit for bit. Returns ``(ModeSearch, SearchPlan)``; row ``k`` of either is cell ``plan.cells[k]``."""
+    cl: Cells = lk.cells
+    ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
+    sp = search_population(cl, ids, seed, n_pop, ratePriorWidth, v0, approved, cell_offset)
+    if not sp.cells:
+        return ModeSearch.empty(0, int(n_pop), sp.pop0.shape[2], int(n_gen)), sp
+    res = lk.modesearch(sp.pop0, np.array(sp.cells, np.int32), sp.lower, sp.upper, sp.prior_mu, sp.prior_sig, s2=s2,
+                        n_gen=n_gen, F=F, CR=CR, seed=int(seed) * 1000003 + 20201028,
+                        keys=np.array(sp.cells, np.int64) + int(cell_offset))
+    return res, sp
+
+
+def search_order(f: np.ndarray) -> np.ndarray:
+    """The members of one cell from best to worst: ascending ``f``, ties by index, NaN last."""
+    f = np.asarray(f, np.float64)
+    return np.lexsort((np.arange(len(f)), np.where(np.isnan(f), np.inf, f), np.isnan(f)))
+
+
+def search_entry(sr: ModeSearch, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCsearch`` entry (``SEARCH_FIELDS``) from selected cell ``k`` of ``sr``, a cell of ``n`` points."""
+    n_pop = sr.pop.shape[1]
+    d = dict(f_best=float(sr.f_best[k]), ss_best=float(sr.ss_best[k]), theta_best=sr.theta_best[k, :7 + n].copy(),
+             f0_best=float(sr.f_trace[0, k]), f_trace=sr.f_trace[:, k].copy(), n_gen=int(sr.n_gen), n_pop=int(n_pop),
+             n_evals=int(n_pop) * (int(sr.n_gen) + 1), cell_index=int(cell_index))
+    return {f: d[f] for f in SEARCH_FIELDS}
 
 
 def _temper_arg(temper):
@@ -1133,6 +1241,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCstack"] = _struct_array(fit_result.MCMCstack, STACK_FIELDS)
     if fit_result.MCMCcheck is not None:  # only after fitcheck()
         variables["MCMCcheck"] = _struct_array(fit_result.MCMCcheck, CHECK_FIELDS)
+    if fit_result.MCMCsearch is not None:  # only a fit with presearch
+        variables["MCMCsearch"] = _struct_array(fit_result.MCMCsearch, SEARCH_FIELDS)
     sio.savemat(base + ".mat", variables)
     chains = [c if c else {f: np.zeros((0, 1)) for f in CHAIN_FIELDS} for c in fit_result.MCMCchain]
     for c in chains:  # chains are column vectors in the reference (chain(n_burn:end, k))
