@@ -1025,6 +1025,99 @@ int tci_modesearch(tci_ctx* ctx, const tci_modesearch_options* opt, const double
                    const int32_t* cell_id, int64_t n_sel, int64_t n_pop, const double* lower, const double* upper,
                    const double* prior_mu, const double* prior_sig, const double* s2, tci_modesearch_outputs* out);
 
+/* ---- DE-MC population sampler per cell (differential-evolution Markov chain, ter Braak 2006) ----
+ * A sampler beside DRAM. A population of states of one cell already encodes the posterior's scale and correlations:
+ * a member is proposed along the difference of two other members, so no covariance is adapted, and with gamma = 1 a
+ * member jumps between modes that two others occupy. mcmcstat has no such sampler: the text below is the definition.
+ * For each selected cell k in [0, n_sel), P = 7 + N of cell cell_id[k], a population of n_pop members runs n_gen
+ * generations. A member is a theta row of ld doubles plus its own sigma2. All in FP64, every operation rounded once as
+ * written, never fused. Member i of cell k is chain b = k * n_pop + i in every output (n_chains = n_sel * n_pop).
+ * State per member: theta; ss, the bits of tci_ss_batch_async on the row; pri, exactly tci_chainlp's pri_t (the same
+ *   device code); s2, starting at sigma2_0[k].
+ * Generation 0 evaluates ss and pri of pop0.
+ * Generation g = 1 .. n_gen is two half-sweeps, h = 0 then h = 1. In half-sweep h the members with i mod 2 == h move
+ *   and the others rest; a moving member takes its pair from the resting half as it stands now (after half-sweep 0 of
+ *   the same generation for h = 1). Updating all members at once from the old population is not reversible; the
+ *   two-set update is (the standard parallel form of ensemble moves). n_pop >= 4, so either half has 2 members.
+ * rng(seed, key, step, purpose, idx), m(w, n) and u01(a, b) are tci_modesearch's; step = 2 g + h; purposes 9-12.
+ *   Index draw. w = rng(seed, key[k], step, 9, i). R = the resting members ascending, n_R of them:
+ *     a = m(w.x, n_R); c = m(w.y, n_R - 1), then + 1 if >= a; r1 = R[a], r2 = R[c]; jrand = m(w.z, P).
+ *   Coordinate j < P. q = rng(seed, key[k], step, 10, i * 4096 + j): u_j = u01(q.x, q.y), v_j = u01(q.z, q.w).
+ *     j < 2055 and i < 4096, so no two (member, coordinate) pairs share a counter.
+ *   Jump generation (jump_every > 0 and g mod jump_every == 0): every j < P crosses and gamma = 1.
+ *   Other generations: j crosses iff u_j < CR or j == jrand; d' = the number of crossing coordinates (>= 1);
+ *     gamma = gamma0 / sqrt((double)(2 d')), sqrt and division correctly rounded. gamma0 <= 0 means 2.38.
+ *   Trial. For a crossing j: t_j = (x_i[j] + gamma * (x_r1[j] - x_r2[j])) + jitter[k][j] * (2 * v_j - 1): the
+ *     subtraction, the product, the addition; then 2 * v_j, minus 1, times jitter, and the last addition. A
+ *     non-crossing j, and j >= P, keep the parent's bits. The jitter is uniform, not Gaussian, on purpose: it is
+ *     symmetric, so detailed balance holds; with jitter_j > 0 it has positive width in every coordinate, so the chain
+ *     is irreducible on a connected support; and it is exact arithmetic, so a restatement reproduces the bits.
+ *   Bounds. If any crossing t_j is NaN or outside [lower_j, upper_j] the proposal is rejected without evaluation
+ *     (mcmcstat's rule): the row reaches the likelihood launch inactive, counts in n_oob, and its logr is NaN.
+ *   Acceptance. f_old = ss_i / s2_i + pri_i, formed afresh because s2 moves; f_new = ss_t / s2_i + pri_t;
+ *     logr = -0.5 * (f_new - f_old). Accept iff logr >= 0, or u < exp(logr) with u = u01 of the x and y words of
+ *     rng(seed, key[k], step, 11, i); a NaN logr rejects. exp is the device library's.
+ *   sigma2. After the decision, with updatesigma: 1 / s2_i ~ Gamma(nobs / 2, scale 2 / ss_i), nobs = 2 N, as
+ *     s2_i = 1 / (G * (2 / ss_i)), G the sampler's own Marsaglia-Tsang unit variate on stream (seed, key[k], step, 12):
+ *     its try `it` (< 1024) reads the calls (i << 16) | it and (i << 16) | it | 2^31, and i < 4096 keeps i << 16 below
+ *     2^28, so no two members share a call. Without updatesigma s2 never changes.
+ * Kept rows: the states after generations g = 0, thin, 2 thin, ..: n_keep = n_gen / thin + 1 rows (thin = 0: none).
+ *   sschain and prichain are the values the sampler held (mcmcstat's sschain), not re-evaluated.
+ * Bits. A cell's outputs depend on its population, data, bounds, priors, jitter, sigma2_0, key, seed and options
+ * alone: not on n_sel, the cell's position, ld or the launch shapes. Everything but ss, exp and the Gamma variate's
+ * log, cos and sqrt is exact in the stated order, so a float64 restatement that takes ss from the kernel reproduces
+ * every decision it can decide (tests/demc_oracle.py). */
+typedef struct {
+  int64_t n_gen;       /* generations, >= 0; default 1000 */
+  int64_t thin;        /* keep every thin-th generation, >= 0 (0: no kept rows); default 1 */
+  int64_t jump_every;  /* every jump_every-th generation is a jump generation, >= 0 (0: never); default 10 */
+  int64_t stats_from;  /* the reductions use the kept rows of generations >= stats_from; default 0 */
+  int64_t updatesigma; /* 0 or 1; default 1 */
+  double CR;           /* crossover rate in [0, 1]; default 0.2 */
+  double gamma0;       /* finite; <= 0 means 2.38; default 0 */
+  uint64_t seed;
+  const int64_t* keys; /* optional [n_sel], as tci_modesearch_options.keys */
+  int64_t flags;       /* reserved, must be 0 */
+} tci_demc_options;
+
+/* Host buffers (any pointer may be NULL). n_chains = n_sel * n_pop. The logs hold generation g = 1 .. min(n_gen,
+ * log_rows) in row g - 1: every member moves once per generation. */
+typedef struct {
+  double *chain;                          /* [n_keep][n_chains][ld] */
+  double *s2chain, *sschain, *prichain;   /* [n_keep][n_chains] */
+  double *pop;                            /* [n_chains][ld]: the final population */
+  double *s2, *ss;                        /* [n_chains]: of the final population */
+  double* accept_rate;                    /* [n_chains]: accepted proposals / n_gen (NaN for n_gen = 0) */
+  int32_t* n_oob;                         /* [n_chains]: proposals rejected at the bounds */
+  int64_t* n_evals;                       /* [n_chains]: SS evaluations, 1 + n_gen - n_oob */
+  double* logr;                           /* [log_rows][n_chains]; NaN for a proposal rejected at the bounds */
+  uint8_t *accepted, *trial_oob;          /* [log_rows][n_chains] */
+  int64_t log_rows;                       /* rows the three logs hold (the caller's) */
+  int64_t n_keep;    /* written: kept rows */
+  double kernel_ms;  /* written: device time of the run (HIP events), the likelihood launches included */
+} tci_demc_outputs;
+
+int tci_demc_defaults(tci_demc_options* opt);
+
+/* HOST pointers, synchronous. pop0 is [n_sel][n_pop][ld]; lower, upper, prior_mu, prior_sig and jitter are
+ * [n_sel][ld]; sigma2_0 is [n_sel]. opt may be NULL (the defaults); out is required. rout and eout may be NULL: when
+ * given, tci_chainrhat / tci_chainess (ropt, eopt may be NULL) of the kept rows of generations >= stats_from are taken
+ * from the device chain before any copy, with the members of cell k as group k and npar = P; the device chain exists
+ * for them alone when out->chain is NULL. Checked in this order, all before any device work: TCI_EINVAL for a null
+ * argument, n_sel < 1, flags != 0, n_gen, thin, jump_every or stats_from < 0, updatesigma outside {0, 1}, CR outside
+ * [0, 1] or NaN, gamma0 not finite, log_rows < 0, n_pop outside [4, 4096], n_sel * n_pop or n_gen at or above 2^31;
+ * TCI_ERANGE for ld outside [1, 2^24], a cell id out of range or ld < 7 + N of a selected cell; TCI_EINVAL, naming the
+ * cell (and the index), for a prior tci_chainlp refuses, a jitter entry with j < P that is not finite or < 0, a
+ * sigma2_0 that is not finite and > 0, nobs / 2 < 1 with updatesigma; TCI_EINVAL, naming cell, member and index, for a
+ * pop0 entry with j < P that is not finite or lies outside [lower_j, upper_j]; TCI_EINVAL for a reduction without kept
+ * rows (thin = 0), with fewer than 2 kept rows at or past stats_from, with max_lag < 0 or reduction flags != 0.
+ * TCI_ENOMEM, with the byte count in the message, when the population and the chain do not fit the device. */
+int tci_demc_run(tci_ctx* ctx, const tci_demc_options* opt, const double* pop0, int64_t ld, const int32_t* cell_id,
+                 int64_t n_sel, int64_t n_pop, const double* lower, const double* upper, const double* prior_mu,
+                 const double* prior_sig, const double* jitter, const double* sigma2_0, tci_demc_outputs* out,
+                 const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                 tci_chainess_outputs* eout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch, MCMCdemc] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -60,6 +60,15 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtem
 %        every rung of its ladder, starts from the best member. Fills the eighth output MCMCsearch, one entry per
 %        fitted cell: f_best, ss_best, theta_best (1 x 7+N), f0_best (the best of the initial population), f_trace
 %        (1 x n_gen+1), n_gen, n_pop, n_evals, cell_index.)
+%     'demc' ([]; [n_pop n_gen] samples every fitted cell with the DE-MC population sampler instead of DRAM:
+%        n_pop members per cell for n_gen generations on the device (tci_mex('demc'); include/tci.h). The members
+%        start as 'presearch' draws them, or from the search's final population when 'presearch' is given with the
+%        same n_pop; the jitter is 1e-3*sqrt(J0); the run is seeded as the sampler is and keyed by cellNum - 1.
+%        n_burn counts generations and thin > 0 is needed; n_steps is not used. Every output comes from the kept
+%        rows of generations >= n_burn of all members pooled (mean_sigma and sigma_sigma included; s2chain holds
+%        every kept row). Fills the ninth output MCMCdemc, one entry per fitted cell: accept_rate, n_oob, n_evals
+%        (1 x n_pop), rhat_max, ess_min (across the members, parameters and sigma2), n_pop, n_gen, cell_index.
+%        Not with 'temper', 'diagnostics', 'logpost', 'stack' or 'predict'.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -92,6 +101,7 @@ p.addParameter('stack', 0);
 p.addParameter('temper', 1);
 p.addParameter('swap_every', 1);
 p.addParameter('presearch', []);
+p.addParameter('demc', []);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -170,6 +180,8 @@ else
 end
 MCMCchain = struct('v_chain',{},'ton_chain',{},'A_chain',{},'tau_chain',{},...
     'MS2_basal_chain',{},'PP7_basal_chain',{},'R_chain',{},'dR_chain',{},'s2chain',{});
+MCMCdiag = struct([]); MCMClp = struct([]); MCMCstack = struct([]); MCMCtemper = struct([]);
+MCMCsearch = struct([]); MCMCdemc = struct([]);
 nc = numel(setup);
 if nc == 0
     return
@@ -221,8 +233,26 @@ end
 sigma2_0 = 1;                                       % :212, :259
 MCMCsearch = struct([]);
 search = [];
-if ~isempty(o.presearch)                            % the mode search: every chain of a cell starts from its best member
+dm = o.demc;
+if ~isempty(dm)
+    if ~(isnumeric(dm) && numel(dm) == 2 && all(dm == floor(dm)) && dm(1) >= 4 && dm(1) <= 4096 && dm(2) >= 1)
+        error('tci:demc', 'demc must be [n_pop n_gen] with n_pop in [4, 4096] and n_gen >= 1');
+    end
+    if R > 1 || o.diagnostics || o.logpost || o.stack || o.predict > 0
+        error('tci:demc', 'demc cannot be combined with temper, diagnostics, logpost, stack or predict');
+    end
+    if o.thin <= 0
+        error('tci:demc', 'a DE-MC fit is reduced from the kept rows: thin > 0');
+    end
+    if ~isempty(o.presearch) && o.presearch(1) ~= dm(1)
+        error('tci:demc', 'presearch n_pop must be the sampler''s n_pop');
+    end
+end
+if ~isempty(o.presearch) || ~isempty(dm)            % the mode search: every chain of a cell starts from its best member
     ps = o.presearch;
+    if isempty(ps)
+        ps = [dm(1) 0];                             % DE-MC alone: the population is drawn, not searched
+    end
     if ~(isnumeric(ps) && numel(ps) == 2 && all(ps == floor(ps)) && ps(1) >= 4 && ps(1) <= 4096 && ps(2) >= 0)
         error('tci:presearch', 'presearch must be [n_pop n_gen] with n_pop in [4, 4096] and n_gen >= 0');
     end
@@ -240,12 +270,63 @@ if ~isempty(o.presearch)                            % the mode search: every cha
             POP0(1:7+n, (k-1)*n_pop + i) = x;
         end
     end
-    search = tci_mex('modesearch', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), sigma2_0, ...
-        struct('n_gen', ps(2), 'seed', o.seed*1000003 + 20201028, 'keys', [setup.cellNum] - 1));
-    for c = 1:numel(cols)
-        k = cols(c);
-        X0(:, c) = search.pop(:, search.best(k), k);
+    if ~isempty(o.presearch)
+        search = tci_mex('modesearch', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), sigma2_0, ...
+            struct('n_gen', ps(2), 'seed', o.seed*1000003 + 20201028, 'keys', [setup.cellNum] - 1));
+        for c = 1:numel(cols)
+            k = cols(c);
+            X0(:, c) = search.pop(:, search.best(k), k);
+        end
+        POP0 = reshape(search.pop, P, n_pop*nc);
     end
+end
+if ~isempty(dm)                                     % ---- the DE-MC fit: every output from the members pooled ----
+    JIT = 1e-3*sqrt(J0(:, 1:nc));
+    for k = 1:nc
+        JIT(8+numel(setup(k).t):end, k) = 0;
+    end
+    D = tci_mex('demc', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, ...
+        struct('n_gen', dm(2), 'thin', o.thin, 'stats_from', n_burn, 'seed', o.seed*1000003 + 20201028, ...
+        'keys', [setup.cellNum] - 1, 'rhat', 1, 'ess', 1));
+    sel = o.thin*(0:size(D.chain, 3)-1) >= n_burn;  % kept row r is generation (r - 1)*thin
+    for k = 1:nc
+        n = numel(setup(k).t);
+        mem = (k-1)*n_pop + (1:n_pop);
+        c = reshape(D.chain(1:7+n, mem, sel), 7+n, [])';          % (rows*members) x P, the members of a row together
+        s2 = reshape(D.s2chain(mem, sel), [], 1);
+        th = mean(c, 1); sd = std(c, 1, 1);
+        r.mean_v = th(1);          r.sigma_v = sd(1);
+        r.mean_ton = th(3);        r.sigma_ton = sd(3);
+        r.mean_A = th(6);          r.sigma_A = sd(6);
+        r.mean_tau = th(2);        r.sigma_tau = sd(2);
+        r.mean_MS2_basal = th(4);  r.sigma_MS2_basal = sd(4);
+        r.mean_PP7_basal = th(5);  r.sigma_PP7_basal = sd(5);
+        r.mean_R = th(7);          r.sigma_R = sd(7);
+        r.mean_dR = th(8:end);     r.sigma_dR = sd(8:end);
+        r.mean_sigma = sqrt(mean(s2));
+        r.sigma_sigma = std(sqrt(s2), 1);
+        r.cell_index = setup(k).cellNum;
+        r.ApprovedFits = setup(k).approved;
+        MCMCresults(k) = r;
+        [simMS2, simPP7] = tci_mex('forward', h, k, th, 'raw');
+        MCMCplot(k) = struct('t_plot', setup(k).t, 'MS2_plot', setup(k).MS2, 'PP7_plot', setup(k).PP7, ...
+            'simMS2', simMS2, 'simPP7', simPP7);
+        MCMCchain(k) = struct('v_chain', c(:,1), 'ton_chain', c(:,3), 'A_chain', c(:,6), ...
+            'tau_chain', c(:,2), 'MS2_basal_chain', c(:,4), 'PP7_basal_chain', c(:,5), ...
+            'R_chain', c(:,7), 'dR_chain', c(:,8:end), 's2chain', reshape(D.s2chain(mem, :), [], 1));
+        dk = struct('accept_rate', D.accept_rate(:, k)', 'n_oob', D.n_oob(:, k)', 'n_evals', D.n_evals(:, k)', ...
+            'rhat_max', D.rhat_max(k), 'ess_min', D.ess_min(k), 'n_pop', n_pop, 'n_gen', dm(2), ...
+            'cell_index', setup(k).cellNum);
+        if isempty(MCMCdemc), MCMCdemc = dk; else, MCMCdemc(k) = dk; end
+        if ~isempty(search)
+            qk = struct('f_best', search.f_best(k), 'ss_best', search.ss_best(k), 'theta_best', search.theta_best(1:7+n, k)', ...
+                'f0_best', search.f_trace(k, 1), 'f_trace', search.f_trace(k, :), 'n_gen', size(search.f_trace, 2) - 1, ...
+                'n_pop', size(search.pop, 2), 'n_evals', size(search.pop, 2)*size(search.f_trace, 2), ...
+                'cell_index', setup(k).cellNum);
+            if isempty(MCMCsearch), MCMCsearch = qk; else, MCMCsearch(k) = qk; end
+        end
+    end
+    return
 end
 options = struct('nsimu', n_steps, 'burnintime', n_burn, 'adaptint', 100, 'method', 'dram', ...  % :263-270
     'updatesigma', 1, 'verbosity', 0, 'stats_from', max(n_burn, 1), 'thin', o.thin, ...

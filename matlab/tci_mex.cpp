@@ -116,6 +116,17 @@
 //          default 0 .. n - 1). out: pop (P x n_pop x n), f and ss (n_pop x n), best (1 x n, 1-based), theta_best
 //          (P x n), f_best, ss_best, pri_best (1 x n), f_trace (n x n_gen + 1), n_accepted (n x n_gen), n_evals,
 //          kernel_ms.
+//   out = tci_mex('demc', h, cells, POP0, LB, UB, MU, SIG, JIT[, sigma2[, options]])
+//          the DE-MC population sampler (differential-evolution Markov chain, ter Braak 2006) over a population per
+//          entry of cells (tci_demc_run, the definition is in include/tci.h). POP0 is P x (n_pop * n) as for
+//          'modesearch'; LB, UB, MU, SIG and JIT (the jitter half-widths) are P x n; sigma2 a scalar or one per entry
+//          (default 1). options: n_gen (1000), thin (1), jump_every (10), stats_from (0), updatesigma (true), CR (0.2),
+//          gamma0 (0 = 2.38), seed (0), keys (1 x n), log_rows (0), rhat (false), ess (false), max_lag (0). Member i of
+//          cells(k) is chain (k - 1) * n_pop + i. out: chain (P x n_chains x n_keep), s2chain, sschain, prichain
+//          (n_chains x n_keep), pop (P x n_pop x n), s2, ss, accept_rate, n_oob, n_evals (n_pop x n), logr, accepted,
+//          trial_oob (n_chains x min(log_rows, n_gen)), n_keep, kernel_ms; with options.rhat also rhat (P x n), s2_rhat
+//          and rhat_max (1 x n), with options.ess also ess (P x n), s2_ess and ess_min (1 x n): tci_chainrhat /
+//          tci_chainess across the members of every cell over the kept rows of generations >= stats_from.
 //   options.presearch of 'dram': a population P x (n_pop * n) laid out as POP0 above, one per chain. The search runs
 //          first (options.presearch_gen generations, default 500, options.presearch_F, options.presearch_CR; seeded by
 //          options.seed and keyed by options.chain_keys) and chain c starts from the best final member of its
@@ -1646,6 +1657,188 @@ void cmd_modesearch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   plhs[0] = ms.finish();
 }
 
+// ---- 'demc': the DE-MC population sampler over a population per cell -----------------------------------
+
+void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs < 9 || nrhs > 11)
+    mexErrMsgIdAndTxt("tci:arg", "tci_mex('demc', h, cells, POP0, LB, UB, MU, SIG, JIT[, sigma2[, options]])");
+  // every argument and option is checked before the handle (and before anything reaches the GPU)
+  const size_t n = mxGetNumberOfElements(prhs[2]);
+  const double* c = doubles(prhs[2], -1, "cells");
+  if (n == 0) mexErrMsgIdAndTxt("tci:arg", "cells must name at least one cell");
+  std::vector<int32_t> cid(n);
+  for (size_t b = 0; b < n; ++b) {
+    if (!(c[b] >= 1 && c[b] <= 2147483647.0) || c[b] != (double)(int64_t)c[b])
+      mexErrMsgIdAndTxt("tci:arg", "cells(%d) must be a positive integer", (int)b + 1);
+    cid[b] = (int32_t)c[b] - 1;
+  }
+  if (!mxIsDouble(prhs[4]) || mxGetNumberOfDimensions(prhs[4]) != 2 || mxGetN(prhs[4]) != n)
+    mexErrMsgIdAndTxt("tci:arg", "LB must be P x n: one column per entry of cells");
+  const size_t P = mxGetM(prhs[4]);
+  if (P < 7) mexErrMsgIdAndTxt("tci:arg", "LB must have at least 7 rows ([v, tau, ton, MS2_basal, PP7_basal, A, R, dR])");
+  const char* names[5] = {"LB", "UB", "MU", "SIG", "JIT"};
+  const double* in[5];
+  for (int k = 0; k < 5; ++k) in[k] = chain_matrix(prhs[4 + k], names[k], P, n);
+  size_t n_pop = 0;
+  const double* pop = pop_matrix(prhs[3], "POP0", P, n, &n_pop);
+  std::vector<double> s2v(n, 1.0);
+  if (nrhs > 9 && mxGetNumberOfElements(prhs[9]) != 0) {
+    const size_t ns2 = mxGetNumberOfElements(prhs[9]);
+    const double* s2 = doubles(prhs[9], -1, "sigma2");
+    if (ns2 != 1 && ns2 != n) mexErrMsgIdAndTxt("tci:arg", "sigma2 must be a scalar or have one entry per entry of cells");
+    for (size_t b = 0; b < n; ++b) s2v[b] = s2[ns2 == 1 ? 0 : b];
+  }
+  const mxArray* o = nullptr;
+  if (nrhs > 10 && !(mxIsDouble(prhs[10]) && mxGetNumberOfElements(prhs[10]) == 0)) {  // [] = defaults
+    if (!mxIsStruct(prhs[10]) || mxGetNumberOfElements(prhs[10]) != 1)
+      mexErrMsgIdAndTxt("tci:opts", "options must be a 1x1 struct");
+    o = prhs[10];
+    static const char* known[] = {"n_gen", "thin", "jump_every", "stats_from", "updatesigma", "CR", "gamma0", "seed",
+                                  "keys", "log_rows", "rhat", "ess", "max_lag"};
+    for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
+      const char* fn = mxGetFieldNameByNumber(o, f);
+      bool ok = false;
+      for (const char* k : known) ok = ok || strcmp(fn, k) == 0;
+      if (!ok) mexErrMsgIdAndTxt("tci:opts", "options.%s is not an option of tci_mex('demc')", fn);
+    }
+  }
+  tci_demc_options dopt;
+  tci_demc_defaults(&dopt);
+  dopt.n_gen = opt_int(o, "n_gen", dopt.n_gen, 0);
+  dopt.thin = opt_int(o, "thin", dopt.thin, 0);
+  dopt.jump_every = opt_int(o, "jump_every", dopt.jump_every, 0);
+  dopt.stats_from = opt_int(o, "stats_from", dopt.stats_from, 0);
+  dopt.updatesigma = opt_num(o, "updatesigma", 1.0) != 0.0;
+  dopt.CR = opt_num(o, "CR", dopt.CR);
+  dopt.gamma0 = opt_num(o, "gamma0", dopt.gamma0);
+  dopt.seed = (uint64_t)opt_int(o, "seed", 0, 0);
+  const int64_t log_rows = opt_int(o, "log_rows", 0, 0);
+  const bool want_rhat = opt_num(o, "rhat", 0.0) != 0.0, want_ess = opt_num(o, "ess", 0.0) != 0.0;
+  tci_chainess_options eopt;
+  tci_chainess_defaults(&eopt);
+  eopt.max_lag = opt_int(o, "max_lag", 0, 0);
+  std::vector<int64_t> keys;
+  if (const mxArray* k = o ? mxGetField(o, 0, "keys") : nullptr) {
+    const double* kv = doubles(k, (long long)n, "options.keys");
+    keys.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(kv[b] >= 0 && kv[b] <= 9.0e15) || kv[b] != (double)(int64_t)kv[b])
+        mexErrMsgIdAndTxt("tci:opts", "options.keys(%d) must be a non-negative integer", (int)b + 1);
+      keys[b] = (int64_t)kv[b];
+    }
+    dopt.keys = keys.data();
+  }
+  if (n_pop > 4096 || n > 2147483647u / n_pop) mexErrMsgIdAndTxt("tci:arg", "POP0 holds too many members");
+  tci_ctx* ctx = handle_of(prhs[1]);
+  const size_t B = n * n_pop, K = dopt.thin > 0 ? (size_t)(dopt.n_gen / dopt.thin) + 1 : 0;
+  const size_t G = (size_t)std::min<int64_t>(log_rows, dopt.n_gen);
+  static const char* fields[] = {"chain", "s2chain", "sschain", "prichain", "pop", "s2", "ss", "accept_rate", "logr",
+                                 "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms", "rhat", "s2_rhat",
+                                 "rhat_max", "ess", "s2_ess", "ess_min"};
+  mxArray* res = mxCreateStructMatrix(1, 1, 15 + (want_rhat ? 3 : 0) + (want_ess ? 3 : 0), fields);
+  if (want_ess && !want_rhat) {  // the ESS fields follow the fixed ones directly
+    mxDestroyArray(res);
+    static const char* fields_e[] = {"chain", "s2chain", "sschain", "prichain", "pop", "s2", "ss", "accept_rate", "logr",
+                                     "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms", "ess", "s2_ess",
+                                     "ess_min"};
+    res = mxCreateStructMatrix(1, 1, 18, fields_e);
+  }
+  const mwSize dc[3] = {P, B, K}, dp[3] = {P, n_pop, n};
+  mxArray* a[9] = {mxCreateNumericArray(3, dc, mxDOUBLE_CLASS, mxREAL), mxCreateDoubleMatrix(B, K, mxREAL),
+                   mxCreateDoubleMatrix(B, K, mxREAL), mxCreateDoubleMatrix(B, K, mxREAL),
+                   mxCreateNumericArray(3, dp, mxDOUBLE_CLASS, mxREAL), mxCreateDoubleMatrix(n_pop, n, mxREAL),
+                   mxCreateDoubleMatrix(n_pop, n, mxREAL), mxCreateDoubleMatrix(n_pop, n, mxREAL),
+                   mxCreateDoubleMatrix(B, G, mxREAL)};
+  for (int k = 0; k < 9; ++k) mxSetField(res, 0, fields[k], a[k]);
+  std::vector<int32_t> noob(B);
+  std::vector<int64_t> nev(B);
+  std::vector<uint8_t> acc(B * G + 1), oob(B * G + 1);
+  tci_demc_outputs out;
+  memset(&out, 0, sizeof out);
+  if (K) {
+    out.chain = mxGetPr(a[0]);
+    out.s2chain = mxGetPr(a[1]);
+    out.sschain = mxGetPr(a[2]);
+    out.prichain = mxGetPr(a[3]);
+  }
+  out.pop = mxGetPr(a[4]);
+  out.s2 = mxGetPr(a[5]);
+  out.ss = mxGetPr(a[6]);
+  out.accept_rate = mxGetPr(a[7]);
+  out.n_oob = noob.data();
+  out.n_evals = nev.data();
+  if (G) {
+    out.logr = mxGetPr(a[8]);
+    out.accepted = acc.data();
+    out.trial_oob = oob.data();
+  }
+  out.log_rows = (int64_t)G;
+  mxArray *r0 = nullptr, *r1 = nullptr, *e0 = nullptr, *e1 = nullptr;
+  tci_chainrhat_outputs rout;
+  tci_chainess_outputs eout;
+  memset(&rout, 0, sizeof rout);
+  memset(&eout, 0, sizeof eout);
+  if (want_rhat) {
+    r0 = mxCreateDoubleMatrix(P, n, mxREAL);
+    r1 = mxCreateDoubleMatrix(1, n, mxREAL);
+    rout.rhat = mxGetPr(r0);
+    rout.s2_rhat = mxGetPr(r1);
+    mxSetField(res, 0, "rhat", r0);
+    mxSetField(res, 0, "s2_rhat", r1);
+  }
+  if (want_ess) {
+    e0 = mxCreateDoubleMatrix(P, n, mxREAL);
+    e1 = mxCreateDoubleMatrix(1, n, mxREAL);
+    eout.ess = mxGetPr(e0);
+    eout.s2_ess = mxGetPr(e1);
+    mxSetField(res, 0, "ess", e0);
+    mxSetField(res, 0, "s2_ess", e1);
+  }
+  const int rc = tci_demc_run(ctx, &dopt, pop, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, in[0], in[1], in[2], in[3],
+                              in[4], s2v.data(), &out, nullptr, want_rhat ? &rout : nullptr, &eopt,
+                              want_ess ? &eout : nullptr);
+  if (rc != TCI_OK) {
+    mxDestroyArray(res);
+    check(ctx, rc, "tci_demc_run");
+  }
+  mxArray* io = mxCreateDoubleMatrix(n_pop, n, mxREAL);
+  mxArray* ie = mxCreateDoubleMatrix(n_pop, n, mxREAL);
+  for (size_t b = 0; b < B; ++b) {
+    mxGetPr(io)[b] = (double)noob[b];
+    mxGetPr(ie)[b] = (double)nev[b];
+  }
+  mxArray* la = mxCreateDoubleMatrix(B, G, mxREAL);
+  mxArray* lo = mxCreateDoubleMatrix(B, G, mxREAL);
+  for (size_t i = 0; i < B * G; ++i) {
+    mxGetPr(la)[i] = (double)acc[i];
+    mxGetPr(lo)[i] = (double)oob[i];
+  }
+  mxSetField(res, 0, "n_oob", io);
+  mxSetField(res, 0, "n_evals", ie);
+  mxSetField(res, 0, "accepted", la);
+  mxSetField(res, 0, "trial_oob", lo);
+  mxSetField(res, 0, "n_keep", mxCreateDoubleScalar((double)out.n_keep));
+  mxSetField(res, 0, "kernel_ms", mxCreateDoubleScalar(out.kernel_ms));
+  // the worst parameter of every cell (NaN entries, the padding past 7 + N, are skipped)
+  auto extreme = [&](const mxArray* m, const mxArray* s, bool largest) {
+    mxArray* v = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t k = 0; k < n; ++k) {
+      double best = mxGetPr(s)[k];
+      for (size_t j = 0; j < P; ++j) {
+        const double x = mxGetPr(m)[k * P + j];
+        if (x != x) continue;
+        if (best != best || (largest ? x > best : x < best)) best = x;
+      }
+      mxGetPr(v)[k] = best;
+    }
+    return v;
+  };
+  if (want_rhat) mxSetField(res, 0, "rhat_max", extreme(r0, r1, true));
+  if (want_ess) mxSetField(res, 0, "ess_min", extreme(e0, e1, false));
+  plhs[0] = res;
+}
+
 }  // namespace
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -1672,6 +1865,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chainess") cmd_chainess(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainlp") cmd_chainlp(nlhs, plhs, nrhs, prhs);
   else if (cmd == "modesearch") cmd_modesearch(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "demc") cmd_demc(nlhs, plhs, nrhs, prhs);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

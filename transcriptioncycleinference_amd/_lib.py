@@ -172,6 +172,19 @@ class tci_modesearch_outputs(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class tci_demc_options(C.Structure):
+    _fields_ = [("n_gen", C.c_int64), ("thin", C.c_int64), ("jump_every", C.c_int64), ("stats_from", C.c_int64),
+                ("updatesigma", C.c_int64), ("CR", C.c_double), ("gamma0", C.c_double), ("seed", C.c_uint64),
+                ("keys", C.POINTER(C.c_int64)), ("flags", C.c_int64)]
+
+
+class tci_demc_outputs(C.Structure):
+    _fields_ = [("chain", _dp), ("s2chain", _dp), ("sschain", _dp), ("prichain", _dp), ("pop", _dp), ("s2", _dp),
+                ("ss", _dp), ("accept_rate", _dp), ("n_oob", _i32p), ("n_evals", _i64p), ("logr", _dp),
+                ("accepted", _u8p), ("trial_oob", _u8p), ("log_rows", C.c_int64), ("n_keep", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
 class tci_fitcheck_options(C.Structure):
     _fields_ = [("scratch_bytes", C.c_int64), ("n_levels", C.c_int32), ("levels", C.c_double * 8)]
 
@@ -280,6 +293,11 @@ SIGNATURES = [
     ("tci_modesearch_defaults", C.c_int, [C.POINTER(tci_modesearch_options)]),
     ("tci_modesearch", C.c_int, [C.c_void_p, C.POINTER(tci_modesearch_options), _dp, C.c_int64, _i32p, C.c_int64,
                                  C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_modesearch_outputs)]),
+    ("tci_demc_defaults", C.c_int, [C.POINTER(tci_demc_options)]),
+    ("tci_demc_run", C.c_int, [C.c_void_p, C.POINTER(tci_demc_options), _dp, C.c_int64, _i32p, C.c_int64, C.c_int64, _dp,
+                               _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_demc_outputs),
+                               C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                               C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -40,6 +40,7 @@
 #include "tci_diag.h"
 #include "tci_dram_internal.h"
 #include "tci_eval.h"
+#include "tci_gamma.h"
 #include "tci_rng.h"
 #include "tci_tile16.h"
 #include "tci_adapt_map.h"
@@ -149,29 +150,9 @@ __device__ __forceinline__ double uniform_at(uint64_t seed, int64_t c, int64_t s
   return u01(r.x, r.y);
 }
 
-// Gamma(a, 1) by Marsaglia & Tsang as the product d*v, for a >= 1: a = DramState::gshape = N/2 >= 2 on a plain chain
-// and beta N/2 on a tempered rung, which dram_run_impl refuses below 1 (tci_dram_run_tempered); a Gamma(a, scale)
-// variate is (d*v)*scale. The unit variate depends only on the stream and a, so the fused engine
-// draws it ahead of the chain (k_draws) and the scale (2/SS of the current state) is applied when
-// it is used: the same bits as gamma_at.
-template <int = 0>  // the body, inlined where the caller's register budget needs it (k_draws)
-__device__ __forceinline__ double gamma_unit_t(uint64_t seed, int64_t c, int64_t step, double a) {
-  const double d = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * d);
-  for (uint32_t it = 0; it < 1024; ++it) {
-    const uint4 r = rng(seed, c, step, P_GAMMA, it);
-    const double u1 = u01(r.x, r.y), u2 = u01(r.z, r.w);
-    const double x = sqrt(-2.0 * log(u1)) * cos(2.0 * M_PI * u2);
-    const uint4 r2 = rng(seed, c, step, P_GAMMA, it | 0x80000000u);
-    const double u = u01(r2.x, r2.y);
-    double v = 1.0 + cc * x;
-    if (v <= 0.0) continue;
-    v = v * v * v;
-    const double x2 = x * x;
-    if (u < 1.0 - 0.0331 * x2 * x2) return d * v;  // squeeze (implies the log test)
-    if (log(u) < 0.5 * x2 + d - d * v + d * log(v)) return d * v;
-  }
-  return a;  // unreachable in practice (acceptance > 0.95 per try)
-}
+// gamma_unit_t, the Marsaglia & Tsang unit variate, is tci_gamma.h's (shared with tci_demc.hip); its defaults are this
+// sampler's stream (P_GAMMA).
+static_assert(kPurposeGamma == P_GAMMA, "tci_gamma.h's default stream");
 __device__ double gamma_unit(uint64_t seed, int64_t c, int64_t step, double a) { return gamma_unit_t(seed, c, step, a); }
 __device__ __forceinline__ double gamma_at(uint64_t seed, int64_t c, int64_t step, double a, double scale) {
   return gamma_unit(seed, c, step, a) * scale;

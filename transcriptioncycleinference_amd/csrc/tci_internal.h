@@ -230,4 +230,30 @@ int launch_modesearch_select(const KParams& kp, const int32_t* cell_id, const do
                              bool final_gen, double* pop, double* f, double* ss, double* pri, double* f_trace,
                              int32_t* n_acc, int32_t* best, double* best_vals, double* theta_best, void* stream);
 
+// One half-sweep of the DE-MC sampler (tci_demc.hip) on a device population [n_sel][n_pop][ld]; ss, pri, s2, n_acc and
+// n_oob are [n_sel * n_pop], laid out as the rows are. In half-sweep h (0 or 1) the n_mov = (n_pop - h + 1) / 2 members
+// with i mod 2 == h move; trial [n_sel * n_mov][ld], ss_t, pri_t and active [n_sel * n_mov] hold the moving members
+// alone, row t = k * n_mov + (i >> 1). cell_id, keys, sigma2_0 (device): [n_sel], valid ids of cells with 7 + N <= ld
+// (the host checks); lower, upper, mu, sig, jitter (device): [n_sel][ld]. 4 <= n_pop <= 4096 and n_sel * n_pop below
+// 2^31 (TCI_ERANGE). Asynchronous on `stream`; TCI_EINVAL on a bad size or a null pointer, TCI_EHIP on a HIP error.
+//   launch_demc_propose  gen == 0: pri of every member of pop ([n_sel * n_pop]; nothing else is read). gen >= 1: the trial
+//                        of every moving member, its prior into pri and its active byte (0: a crossing entry is NaN or
+//                        out of bounds, pri is NaN). The caller then launches the likelihood kernel on trial under active.
+//   launch_demc_decide   gen == 0: s2 = sigma2_0 and zero counters for every member. gen >= 1: the decision and the
+//                        sigma2 draw of every moving member; an accepted trial replaces its parent in pop, ss, pri.
+//                        log_row >= 0: logr, acc_log and oob_log (each may be null) [.][n_sel * n_pop] get the moving
+//                        members' entries of that row. keep_row >= 0: after the decisions, row keep_row of chain
+//                        [.][n_sel * n_pop][ld], s2chain, sschain and prichain [.][n_sel * n_pop] gets every member.
+int launch_demc_propose(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* pop,
+                        const double* lower, const double* upper, const double* mu, const double* sig,
+                        const double* jitter, int64_t n_sel, int64_t n_pop, int64_t ld, int64_t gen, int h, bool jump,
+                        uint64_t seed, double gamma0, double CR, double* trial, double* pri, uint8_t* active,
+                        void* stream);
+int launch_demc_decide(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* sigma2_0,
+                       const double* trial, const double* ss_t, const double* pri_t, const uint8_t* active,
+                       int64_t n_sel, int64_t n_pop, int64_t ld, int64_t gen, int h, uint64_t seed, bool updatesigma,
+                       int64_t keep_row, int64_t log_row, double* pop, double* ss, double* pri, double* s2,
+                       int32_t* n_acc, int32_t* n_oob, double* chain, double* s2chain, double* sschain,
+                       double* prichain, double* logr, uint8_t* acc_log, uint8_t* oob_log, void* stream);
+
 }  // namespace tci

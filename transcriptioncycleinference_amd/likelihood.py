@@ -478,6 +478,52 @@ class ModeSearch:
                                            I(self.n_accepted) if self.n_gen else None, 0, 0.0)
 
 
+@dataclasses.dataclass
+class Demc:
+    """A DE-MC run (``tci_demc_outputs``; the definition is in ``include/tci.h``). Member ``i`` of selected cell ``k``
+    is chain ``k * n_pop + i``. ``chain`` ``[n_keep, n_chains, ld]`` with ``s2chain``, ``sschain`` and ``prichain``
+    ``[n_keep, n_chains]``: the states after generations 0, thin, 2 thin, ..; ``pop`` ``[n_sel, n_pop, ld]``, ``s2`` and
+    ``ss`` ``[n_sel, n_pop]``: the final population; per member ``accept_rate``, ``n_oob`` (int32) and ``n_evals``
+    (int64) ``[n_sel, n_pop]``; the logs ``logr``, ``accepted`` and ``trial_oob`` (uint8) ``[log_rows, n_chains]``, row
+    ``g - 1`` for generation ``g``; ``rhat`` / ``ess``: the group reductions over the cells' members, or None."""
+
+    chain: np.ndarray
+    s2chain: np.ndarray
+    sschain: np.ndarray
+    prichain: np.ndarray
+    pop: np.ndarray
+    s2: np.ndarray
+    ss: np.ndarray
+    accept_rate: np.ndarray
+    n_oob: np.ndarray
+    n_evals: np.ndarray
+    logr: np.ndarray
+    accepted: np.ndarray
+    trial_oob: np.ndarray
+    n_gen: int = 0
+    thin: int = 0
+    kernel_ms: float = 0.0
+    rhat: Optional[ChainRhat] = None
+    ess: Optional[ChainEss] = None
+
+    @classmethod
+    def empty(cls, n: int, n_pop: int, ld: int, n_gen: int, thin: int, log_rows: int) -> "Demc":
+        d = lambda *s: np.full(s, np.nan)  # noqa: E731
+        K = n_gen // thin + 1 if thin > 0 else 0
+        B, G = n * n_pop, min(int(log_rows), int(n_gen))
+        return cls(d(K, B, ld), d(K, B), d(K, B), d(K, B), d(n, n_pop, ld), d(n, n_pop), d(n, n_pop), d(n, n_pop),
+                   np.zeros((n, n_pop), np.int32), np.zeros((n, n_pop), np.int64), d(G, B), np.zeros((G, B), np.uint8),
+                   np.zeros((G, B), np.uint8), int(n_gen), int(thin))
+
+    def to_c(self) -> "_lib.tci_demc_outputs":
+        P = lambda a: _lib.ptr(a, _lib._dp) if a.size else None  # noqa: E731
+        U = lambda a: _lib.ptr(a, _lib._u8p) if a.size else None  # noqa: E731
+        return _lib.tci_demc_outputs(P(self.chain), P(self.s2chain), P(self.sschain), P(self.prichain), P(self.pop),
+                                     P(self.s2), P(self.ss), P(self.accept_rate), _lib.ptr(self.n_oob, _lib._i32p),
+                                     _lib.ptr(self.n_evals, _lib._i64p), P(self.logr), U(self.accepted),
+                                     U(self.trial_oob), self.logr.shape[0], 0, 0.0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -936,6 +982,55 @@ class Likelihood:
                                              P(lo), P(up), P(mu), P(sig), P(s2v), C.byref(out)))
         ms.n_evals, ms.kernel_ms = int(out.n_evals), float(out.kernel_ms)
         return ms
+
+    def demc(self, pop0: np.ndarray, cell_id: Sequence[int], lower: np.ndarray, upper: np.ndarray,
+             prior_mu: np.ndarray, prior_sig: np.ndarray, jitter: np.ndarray, sigma2_0=1.0, n_gen: int = 1000,
+             thin: int = 1, jump_every: int = 10, CR: float = 0.2, gamma0: float = 0.0, updatesigma: bool = True,
+             seed: int = 0, keys=None, stats_from: int = 0, rhat: bool = False, ess: bool = False, max_lag: int = 0,
+             log_rows: int = 0, flags: int = 0) -> Demc:
+        """Differential-evolution Markov chain (ter Braak 2006) over a population per cell, on the device
+        (``tci_demc_run``; the definition is in ``include/tci.h``). ``pop0`` ``[n_sel, n_pop, ld]``: the initial members
+        of every selected cell, each inside ``[lower, upper]``; ``cell_id`` one cell per population; ``lower``,
+        ``upper``, ``prior_mu``, ``prior_sig`` and ``jitter`` ``[n_sel, ld]``; ``sigma2_0`` ``[n_sel]`` or a scalar;
+        ``keys`` ``[n_sel]``: the RNG stream key of every cell (default: its position). ``rhat`` / ``ess``: also the
+        group reductions of the kept rows of generations ``>= stats_from`` across every cell's members, taken from the
+        device chain. ``log_rows``: generations the decision logs keep. Returns a :class:`Demc`."""
+        pop0 = np.ascontiguousarray(pop0, np.float64)
+        if pop0.ndim != 3:
+            raise ValueError("pop0 must be [n_sel, n_pop, ld]")
+        n, n_pop, ld = pop0.shape
+        cid = np.ascontiguousarray(np.atleast_1d(cell_id), np.int32)
+        if cid.shape != (n,):
+            raise ValueError("cell_id must have one entry per population")
+        for name, v in (("n_gen", n_gen), ("thin", thin), ("log_rows", log_rows)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 0:
+                raise ValueError(f"{name} must be an integer >= 0")
+        f = lambda a: np.ascontiguousarray(np.asarray(a, np.float64).reshape(n, ld))  # noqa: E731
+        lo, up, mu, sig, jit = f(lower), f(upper), f(prior_mu), f(prior_sig), f(jitter)
+        s2v = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma2_0, np.float64), (n,)))
+        kv = None if keys is None else np.ascontiguousarray(keys, np.int64)
+        if kv is not None and kv.shape != (n,):
+            raise ValueError("keys must have one entry per population")
+        dm = Demc.empty(n, n_pop, ld, int(n_gen), int(thin), int(log_rows))
+        opt = _lib.tci_demc_options(int(n_gen), int(thin), int(jump_every), int(stats_from), int(updatesigma), float(CR),
+                                    float(gamma0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(kv, _lib._i64p), int(flags))
+        out = dm.to_c()
+        cr = ChainRhat.empty(n, ld) if rhat else None
+        ce = ChainEss.empty(n, ld, max_lag) if ess else None
+        ropt, rout = (cr.options(), cr.to_c()) if cr is not None else (None, None)
+        eopt, eout = (ce.options(), ce.to_c()) if ce is not None else (None, None)
+        R = lambda x: None if x is None else C.byref(x)  # noqa: E731
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        self._check(self._lib.tci_demc_run(self._h, C.byref(opt), P(pop0), ld, _lib.ptr(cid, _lib._i32p), n, n_pop, P(lo),
+                                           P(up), P(mu), P(sig), P(jit), P(s2v), C.byref(out), R(ropt), R(rout), R(eopt),
+                                           R(eout)))
+        dm.kernel_ms = float(out.kernel_ms)
+        if cr is not None:
+            cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
+        if ce is not None:
+            ce.n_rows, ce.kernel_ms = int(eout.n_rows), float(eout.kernel_ms)
+        dm.rhat, dm.ess = cr, ce
+        return dm
 
     # -- evaluation (device buffers, asynchronous) --------------------------
     def ss_batch_device(self, theta, cell_id, out, active=None, stream=None) -> None:

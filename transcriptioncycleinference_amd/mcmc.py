@@ -29,7 +29,7 @@ import numpy as np
 from . import _lib
 from .data import Cells, draw_x0
 from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainLp, ChainQuant, ChainRhat, ChainStats,
-                         FitCheck, ModeSearch, rhat_groups)
+                         Demc, FitCheck, ModeSearch, rhat_groups)
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -90,6 +90,9 @@ TEMPER_FIELDS = ("beta", "swap_rate", "swap_tried", "accept_rate", "swap_every",
 # [n_gen + 1] the best f after every generation, n_evals the cell's SS evaluations
 SEARCH_FIELDS = ("f_best", "ss_best", "theta_best", "f0_best", "f_trace", "n_gen", "n_pop", "n_evals", "cell_index")
 PRESEARCH_KEYS = ("n_pop", "n_gen", "F", "CR")
+# MCMCdemc (fit(..., demc=dict(...))): the DE-MC population sampler's per-cell record
+DEMC_FIELDS = ("accept_rate", "n_oob", "rhat_max", "ess_min", "n_pop", "n_gen", "n_evals", "cell_index")
+DEMC_KEYS = ("n_pop", "n_gen", "CR", "gamma0", "jump_every", "jitter", "updatesigma")
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -433,6 +436,7 @@ class FitResult:
     rows_per_lane_uniform: bool = True         # parallel.fit_sharded: every rank ran the same likelihood variant
     MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
     MCMCsearch: Optional[List[Dict]] = None    # fit(..., presearch=dict(...)): SEARCH_FIELDS per fitted cell
+    MCMCdemc: Optional[List[Dict]] = None      # fit(..., demc=dict(...)): DEMC_FIELDS per fitted cell
     MCMCtemper: Optional[List[Dict]] = None    # fit(..., temper=R): TEMPER_FIELDS per fitted cell
     MCMCstack: Optional[List[Dict]] = None     # fit(..., stack=nsample): STACK_FIELDS per fitted cell
     MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
@@ -553,7 +557,8 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         opts: Optional[DramOptions] = None, cell_offset: int = 0, diagnostics: bool = False,
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
         rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False,
-        stack: Optional[int] = None, temper=None, swap_every: int = 1, presearch: Optional[Mapping] = None) -> FitResult:
+        stack: Optional[int] = None, temper=None, swap_every: int = 1, presearch: Optional[Mapping] = None,
+        demc: Optional[Mapping] = None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -638,10 +643,28 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     holds every replicate's usual start, and replicate ``r`` of a cell starts from the ``r``-th best final member (by
     ``f``, ties by index; needs ``replicates <= n_pop``); the rungs of a tempered replicate start from their replicate's
     member. Everything else is unchanged. ``MCMCsearch`` holds one dict of ``SEARCH_FIELDS`` per fitted cell.
-    ``presearch=None`` (the default) takes no new code path."""
+    ``presearch=None`` (the default) takes no new code path.
+
+    ``demc``: a dict with keys among ``DEMC_KEYS`` (``n_pop`` and ``n_gen`` default to :func:`demc`'s): the cells are
+    sampled by the DE-MC population sampler (include/tci.h, ``tci_demc_run``) instead of DRAM; ``n_steps`` and ``opts``
+    are not used, ``n_burn`` counts generations and ``thin >= 1`` is needed. Every field of the result comes from the
+    kept rows of generations ``>= n_burn`` of all members pooled (``MCMCchain``'s ``s2chain`` alone holds every kept
+    row, as the reference's is not sliced by n_burn; ``final_theta``: member 0's last state;
+    ``accept_rate``: the members' mean), and ``MCMCdemc`` holds one dict of ``DEMC_FIELDS`` per fitted cell, R-hat and
+    the multi-chain ESS across the members reduced on the device. With ``presearch`` the population starts from the
+    search's final one (its ``n_pop`` is the sampler's). It cannot be combined with ``temper`` or ``replicates``, which
+    are DRAM's, nor with the DRAM reductions. ``demc=None`` (the default) is today's fit bit for bit."""
     M = int(replicates)
     ps = _presearch_arg(presearch, M)
     betas, R = _temper_arg(temper)
+    if demc is not None:
+        if M != 1 or R > 1:
+            raise ValueError("demc is a population sampler of its own: it cannot be combined with temper or replicates "
+                             "(its members are the cell's chains)")
+        if diagnostics or covariance or quantiles is not None or density or logpost or stack is not None or rhat or ess:
+            raise ValueError("demc does not take the DRAM reductions (diagnostics, covariance, quantiles, density, rhat, "
+                             "ess, logpost, stack): MCMCdemc holds R-hat and ESS across the members")
+        return _fit_demc(lk, demc, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag)
     if R > 1 and (isinstance(swap_every, bool) or int(swap_every) != swap_every or int(swap_every) < 0):
         raise ValueError("swap_every must be an integer >= 0")
     if M != replicates or M < 1:
@@ -849,6 +872,159 @@ def modesearch(lk, n_pop: int = 64, n_gen: int = 500, seed: int = 0, cells: Opti
                         n_gen=n_gen, F=F, CR=CR, seed=int(seed) * 1000003 + 20201028,
                         keys=np.array(sp.cells, np.int64) + int(cell_offset))
     return res, sp
+
+
+def _demc_arg(demc):
+    """``fit``'s ``demc`` as keyword arguments of :func:`demc`."""
+    if not isinstance(demc, Mapping):
+        raise ValueError(f"demc must be a dict with keys among {DEMC_KEYS}")
+    bad = sorted(set(demc) - set(DEMC_KEYS))
+    if bad:
+        raise ValueError(f"demc has unknown keys {bad}: the keys are {DEMC_KEYS}")
+    d = dict(demc)
+    n_pop = d.setdefault("n_pop", 64)
+    if isinstance(n_pop, bool) or int(n_pop) != n_pop or not 4 <= int(n_pop) <= 4096:
+        raise ValueError("demc n_pop must be an integer in [4, 4096]")
+    n_gen = d.setdefault("n_gen", 1000)
+    if isinstance(n_gen, bool) or int(n_gen) != n_gen or int(n_gen) < 1:
+        raise ValueError("demc n_gen must be an integer >= 1")
+    return d
+
+
+def demc_jitter(cl: Cells, ids: Sequence[int], ratePriorWidth: float = 50.0, v0=None, approved=None,
+                cell_offset: int = 0) -> np.ndarray:
+    """The default jitter half-width of :func:`demc`, ``[K, ld]``: ``1e-3 * sqrt(qcov_diag)`` of :func:`cell_setup`
+    (padding 0). A starting value, not a measured optimum."""
+    plan = plan_fit(cl, ids, 0, ratePriorWidth, v0, approved, cell_offset=cell_offset)
+    jit = 1e-3 * np.sqrt(plan.qcov_diag)
+    for k, c in enumerate(plan.cells):
+        jit[k, 7 + int(cl.lengths[c]):] = 0.0
+    return jit
+
+
+def demc(lk, n_pop: int = 64, n_gen: int = 1000, thin: int = 1, n_burn: int = 0, seed: int = 0,
+         cells: Optional[Sequence[int]] = None, v0=None, presearch=None, cell_offset: int = 0,
+         ratePriorWidth: float = 50.0, jitter=None, CR: float = 0.2, gamma0: float = 0.0, jump_every: int = 10,
+         updatesigma: bool = True, sigma2_0=1.0, rhat: bool = True, ess: bool = True, max_lag: int = 0,
+         log_rows: int = 0, approved=None):
+    """A DE-MC run (``Likelihood.demc``; include/tci.h, ``tci_demc_run``) of the cells ``cells`` (default: all) of
+    ``lk`` from :func:`search_population`, or from the final population of a mode search when ``presearch`` is given: a
+    dict of ``n_gen`` / ``F`` / ``CR`` for :func:`modesearch` (run here with the same ``n_pop`` and ``seed``), or the
+    ``(ModeSearch, SearchPlan)`` such a call returned. Everything random is keyed by the dataset-wide cell index (the
+    population by ``default_rng``, the run by RNG stream ``cell_offset + cell``) and seeded as :func:`fit` seeds its
+    sampler, so a shard reproduces its cells of the full run bit for bit. ``jitter``: ``[K, ld]`` half-widths, a scalar
+    factor on :func:`demc_jitter`'s default, or None. ``n_burn``: the reductions (``rhat`` / ``ess``, across a cell's
+    members) use the kept rows of generations ``>= n_burn``. Returns ``(Demc, SearchPlan)``; row ``k`` of either is cell
+    ``plan.cells[k]``."""
+    cl: Cells = lk.cells
+    ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
+    if isinstance(presearch, tuple):
+        sr, sp = presearch
+        if sr.pop.shape[1] != int(n_pop):
+            raise ValueError("the mode search's n_pop is not the sampler's")
+        pop0 = sr.pop
+    elif presearch is not None:
+        if not isinstance(presearch, Mapping) or set(presearch) - {"n_gen", "F", "CR"}:
+            raise ValueError("presearch must be a dict with keys among ('n_gen', 'F', 'CR') or a modesearch result")
+        sr, sp = modesearch(lk, n_pop=n_pop, seed=seed, cells=ids, v0=v0, cell_offset=cell_offset,
+                            ratePriorWidth=ratePriorWidth, approved=approved, **presearch)
+        pop0 = sr.pop
+    else:
+        sp = search_population(cl, ids, seed, n_pop, ratePriorWidth, v0, approved, cell_offset)
+        pop0 = sp.pop0
+    if not sp.cells:
+        return Demc.empty(0, int(n_pop), sp.pop0.shape[2], int(n_gen), int(thin), 0), sp
+    jit = jitter
+    if jit is None or np.ndim(jit) == 0:
+        base = demc_jitter(cl, sp.cells, ratePriorWidth, v0, approved, cell_offset)
+        jit = base if jit is None else float(jit) * base
+    res = lk.demc(pop0, np.array(sp.cells, np.int32), sp.lower, sp.upper, sp.prior_mu, sp.prior_sig, jit,
+                  sigma2_0=sigma2_0, n_gen=n_gen, thin=thin, jump_every=jump_every, CR=CR, gamma0=gamma0,
+                  updatesigma=updatesigma, seed=int(seed) * 1000003 + 20201028,
+                  keys=np.array(sp.cells, np.int64) + int(cell_offset), stats_from=n_burn, rhat=rhat, ess=ess,
+                  max_lag=max_lag, log_rows=log_rows)
+    return res, sp
+
+
+def demc_entry(res: Demc, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCdemc`` entry (``DEMC_FIELDS``) from selected cell ``k`` of ``res``, a cell of ``n`` points: per member
+    ``accept_rate``, ``n_oob`` and ``n_evals``; ``rhat_max`` / ``ess_min``: the largest classic R-hat and the least
+    multi-chain ESS over the cell's parameters and s2 (NaN without the reduction)."""
+    P = 7 + n
+    rm = em = float("nan")
+    if res.rhat is not None:
+        rm = float(np.nanmax(np.append(res.rhat.rhat[k, :P], res.rhat.s2_rhat[k])))
+    if res.ess is not None:
+        em = float(np.nanmin(np.append(res.ess.ess[k, :P], res.ess.s2_ess[k])))
+    d = dict(accept_rate=res.accept_rate[k].copy(), n_oob=res.n_oob[k].copy(), rhat_max=rm, ess_min=em,
+             n_pop=int(res.pop.shape[1]), n_gen=int(res.n_gen), n_evals=res.n_evals[k].copy(), cell_index=int(cell_index))
+    return {f: d[f] for f in DEMC_FIELDS}
+
+
+def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag):
+    """:func:`fit` with the DE-MC sampler: every result field from the kept rows of all members pooled."""
+    kw = _demc_arg(demc_arg)
+    if int(thin) < 1:
+        raise ValueError("a DE-MC fit is reduced from the kept rows: demc needs thin >= 1")
+    n_gen, n_pop = int(kw["n_gen"]), int(kw["n_pop"])
+    if n_gen // int(thin) + 1 - -(-int(n_burn) // int(thin)) < 2:
+        raise ValueError("demc needs at least 2 kept generations at or past n_burn")
+    cl: Cells = lk.cells
+    off = int(cell_offset)
+    ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
+    keep = kept_cells(cl, ids, v0, off)
+    if not keep:
+        return FitResult(cl.name, [], [], [], np.zeros(0), 0, 0.0)
+    ps = None
+    searched = None
+    if presearch is not None:
+        pk = _presearch_arg({**presearch, "n_pop": presearch.get("n_pop", n_pop)}, 1)
+        if int(pk.pop("n_pop")) != n_pop:
+            raise ValueError("presearch n_pop must be the sampler's n_pop")
+        ps = modesearch(lk, n_pop=n_pop, seed=seed, cells=keep, v0=v0, cell_offset=off, ratePriorWidth=ratePriorWidth,
+                        approved=approved, **pk)
+        searched = [search_entry(ps[0], k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
+    res, sp = demc(lk, thin=int(thin), n_burn=int(n_burn), seed=seed, cells=keep, v0=v0, presearch=ps, cell_offset=off,
+                   ratePriorWidth=ratePriorWidth, max_lag=max_lag, approved=approved, **kw)
+    if sp.cells != keep:
+        raise RuntimeError(f"demc sampled cells {sp.cells}, the fit keeps {keep}")
+    K = len(keep)
+    ld = res.pop.shape[2]
+    sel = int(thin) * np.arange(res.chain.shape[0]) >= int(n_burn)
+    chain = res.chain[sel].reshape(-1, K, n_pop, ld)         # [rows, cell, member, ld]
+    s2 = res.s2chain.reshape(-1, K, n_pop)                   # s2chain is not sliced by n_burn (:323)
+    mean = np.zeros((K, ld))
+    for k, c in enumerate(keep):
+        P = 7 + int(cl.lengths[c])
+        mean[k, :P] = chain[:, k, :, :P].reshape(-1, P).mean(axis=0)
+    ms2, pp7 = lk.forward(mean, np.array(keep, np.int32), grid="raw")
+    results, plots, chains, entries = [], [], [], []
+    for k, c in enumerate(keep):
+        t, m, p = cl.cell(c)
+        n = len(t)
+        th = chain[:, k, :, :7 + n].reshape(-1, 7 + n)       # the members of a row side by side, rows ascending
+        std = th.std(axis=0)
+        r = {}
+        for name in _SCALARS:
+            r["mean_" + name] = float(mean[k, THETA_INDEX[name]])
+            r["sigma_" + name] = float(std[THETA_INDEX[name]])
+        r["mean_dR"], r["sigma_dR"] = mean[k, 7:7 + n].copy(), std[7:].copy()
+        sq = s2[:, k].reshape(-1)
+        sq_sel = s2[sel, k].reshape(-1)                      # the summaries: generations >= n_burn, as every other one
+        r["mean_sigma"], r["sigma_sigma"] = float(np.sqrt(sq_sel.mean())), float(np.sqrt(sq_sel).std())
+        r["cell_index"] = off + c + 1
+        r["ApprovedFits"] = _previous(v0, approved, off + c)[2]
+        results.append({f: r[f] for f in RESULT_FIELDS})
+        plots.append({"t_plot": t.copy(), "MS2_plot": m.copy(), "PP7_plot": p.copy(),
+                      "simMS2": ms2[k, :n].copy(), "simPP7": pp7[k, :n].copy()})
+        ch = {name + "_chain": th[:, THETA_INDEX[name]].copy() for name in _SCALARS}
+        ch["dR_chain"] = th[:, 7:].copy()
+        ch["s2chain"] = sq.copy()
+        chains.append(ch)
+        entries.append(demc_entry(res, k, n, off + c + 1))
+    return FitResult(cl.name, results, plots, chains, res.accept_rate.mean(axis=1), int(res.n_evals.sum()),
+                     res.kernel_ms, np.array(keep, np.int64) + off, res.pop[:, 0].copy(), MCMCsearch=searched,
+                     MCMCdemc=entries)
 
 
 def search_order(f: np.ndarray) -> np.ndarray:
