@@ -636,6 +636,109 @@ int tci_dram_run_ess(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains
                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
                      tci_chainess_outputs* eout);
 
+/* ---- Replicate chains ranked: rank-normalised split R-hat, bulk and tail ESS, pooled quantiles ----
+ * The diagnostics of Vehtari, Gelman, Simpson, Carpenter and Buerkner, "Rank-normalization, folding, and localization:
+ * an improved R-hat for assessing convergence of MCMC", Bayesian Analysis 16 (2021), and the pooled quantiles of a
+ * group, all resting on one pooled sort of the group's column on the device. The group, the column, the s2 column,
+ * padding, group ids no chain carries and the mixed-npar error are tci_chainrhat's. A non-finite entry (NaN or +-Inf)
+ * anywhere in a group's column makes every output of that column NaN and every window -1. For a finite column of one
+ * group, N = M n: the group's M chains in ascending chain index, rows [0, n) of each. All in FP64, every operation
+ * rounded once as written, never fused.
+ *   1. pooled order   key(x) is tci_chainquant's 64-bit total order (-0 sorts below +0; they do not tie); y is the N
+ *                     values sorted ascending by key.
+ *   2. q              for each p = probs[k]: tci_chainquant's plims rule on y with n := N: h = (N - 1) * p,
+ *                     lo = floor(h), f = h - lo, q = y[lo] + f * (y[lo + 1] - y[lo]), and y[N - 1] where lo + 1 == N.
+ *                     Exact: bit for bit the sorted-column definition.
+ *   3. rank scores    for an element with key k: lt = the number of keys below k, eq = the number equal to k,
+ *                     R2 = 2 lt + eq + 1 (twice the average rank, an integer),
+ *                     p = ((double)R2 - 0.75) / ((double)(2 N) + 0.5): Blom's (r - 3/8) / (N + 1/4) with one division,
+ *                     z = PPND16(p), Wichura's algorithm AS241 written as CPython's statistics.NormalDist().inv_cdf
+ *                     writes it (the same expression and coefficients, every Horner step a multiplication, then an
+ *                     addition). Where |p - 0.5| <= 0.425 the expression has no transcendental: z is the library's bit
+ *                     for bit. Elsewhere r = sqrt(-log(min(p, 1 - p))) goes through the device's log, and z lies
+ *                     within 72 ulp of the expression evaluated with any log that is good to 1 ulp (DESIGN.md
+ *                     section 7n and tests/chainrank_oracle.py have the derivation; the largest difference seen is
+ *                     recorded there).
+ *   4. bulk           rhat_bulk = tci_chainrhat's SPLIT rhat of the z chain; ess_bulk, tau_bulk, window_bulk =
+ *                     tci_chainess's SPLIT outputs on the z chain with max_lag.
+ *   5. folded         med = the pooled quantile at p = 0.5 (rule 2); zeta = fabs(x - med), one subtraction; z_folded =
+ *                     the rank scores (rule 3) of zeta; rhat_folded = its split rhat;
+ *                     rhat_rank = max(rhat_bulk, rhat_folded), NaN if either is NaN.
+ *   6. tail           q_tail = the pooled quantiles at tail_lo and tail_hi; the indicator chains
+ *                     I_lo = (x <= q_tail[0]) ? 1.0 : 0.0 and I_hi = (x <= q_tail[1]) ? 1.0 : 0.0; ess_tail_lo and
+ *                     ess_tail_hi = their split ESS with max_lag (window_tail_lo, window_tail_hi the lags summed);
+ *                     ess_tail = min of the two, NaN if either is NaN. A constant indicator column gives NaN by
+ *                     tci_chainess's vplus == 0 rule; nothing is special-cased.
+ *   7. z, z_folded    optional: the rank-score chains themselves, laid out as the chain (what rank plots draw). Padding
+ *                     columns, chains of no group and columns with a non-finite entry are NaN there.
+ * Consequences: n < 4 has no split sequence of two rows: every rhat and ess output is NaN and the windows are 0, as
+ * tci_chainrhat / tci_chainess give; q, q_tail, z and z_folded are defined for every n >= 1. M = 1 is allowed: the
+ * two halves of the one chain are compared. A constant column has every R2 = N + 1, p = 0.5 exactly and z = 0: rhat
+ * NaN (0/0), ess NaN.
+ * Deviations from Vehtari et al.: (a) they split each chain before ranking, which changes nothing for an even n (the
+ * pooled set is the same); for an odd n the middle row is ranked here and belongs to no half, as in tci_chainrhat.
+ * (b) Their ESS truncates Geyer's sequence as Stan does (initial positive, then monotone, with a tail correction
+ * term); bulk and tail ESS here are tci_chainess's estimator on the transformed chains. (c) Their tail-ESS indicator
+ * quantiles are taken per call of the quantile function of the pooled draws with R's type 7 rule, which is plims.
+ * Bits. An output's bits depend on the group's columns in chain order, on n and on the options alone: not on n_chains,
+ * where the chains sit, how groups interleave, ld, or which sort path ran (up to tci_chainrank_lds_cap() values of a
+ * group are sorted in LDS, more in global memory; the sorted keys are one sequence either way).
+ * Device memory beyond the chain: one transformed chain (the size of chain and s2chain), reused by the four passes
+ * (z, z_folded, I_lo, I_hi); for groups above the cap, 8 N_max bytes per (group, column); and tci_chainess's scratch. */
+typedef struct {
+  int32_t nq;         /* 1 .. 16; default 3 */
+  double probs[16];   /* each in [0, 1]; default 0.025, 0.5, 0.975 */
+  double tail_lo;     /* 0 < tail_lo < tail_hi < 1; defaults 0.05, 0.95 */
+  double tail_hi;
+  int64_t max_lag;    /* as tci_chainess_options; default 0 */
+  int64_t flags;      /* reserved, must be 0 */
+} tci_chainrank_options;
+
+/* Host buffers (any pointer may be NULL). Per-group vectors have stride ld. */
+typedef struct {
+  double* q;                                                /* [n_groups][nq][ld] */
+  double* q_tail;                                           /* [n_groups][2][ld] */
+  double *rhat_bulk, *rhat_folded, *rhat_rank;              /* [n_groups][ld] */
+  double *ess_bulk, *tau_bulk;                              /* [n_groups][ld] */
+  double *ess_tail_lo, *ess_tail_hi, *ess_tail;             /* [n_groups][ld] */
+  int32_t *window_bulk, *window_tail_lo, *window_tail_hi;   /* [n_groups][ld] */
+  double* s2_q;                                             /* [n_groups][nq]; the s2 twins are NaN / -1 without s2 */
+  double* s2_q_tail;                                        /* [n_groups][2] */
+  double *s2_rhat_bulk, *s2_rhat_folded, *s2_rhat_rank;     /* [n_groups] */
+  double *s2_ess_bulk, *s2_tau_bulk;
+  double *s2_ess_tail_lo, *s2_ess_tail_hi, *s2_ess_tail;
+  int32_t *s2_window_bulk, *s2_window_tail_lo, *s2_window_tail_hi;
+  double *z, *z_folded;                                     /* [n_rows][n_chains][ld] */
+  double *s2_z, *s2_z_folded;                               /* [n_rows][n_chains] */
+  int64_t n_rows;    /* written: rows the reduction used */
+  double kernel_ms;  /* written: device time of the whole reduction (HIP events); with z / z_folded given, their
+                        device-to-host copies between the passes lie inside it */
+  double rank_ms;    /* written: device time of the sort, rank and indicator kernels alone */
+} tci_chainrank_outputs;
+
+int tci_chainrank_defaults(tci_chainrank_options* opt);
+
+/* The most values of one group (M * n_rows) the pooled sort holds in LDS; larger groups are sorted in global memory. */
+int64_t tci_chainrank_lds_cap(void);
+
+/* The reduction of a chain already on the host; arguments, rules, error codes and their order as for tci_chainrhat,
+ * plus TCI_EINVAL for nq outside [1, 16], a prob that is not in [0, 1], tail_lo / tail_hi that do not satisfy
+ * 0 < tail_lo < tail_hi < 1, max_lag < 0 and flags != 0 (checked after n_rows and before n_chains, as tci_chainess
+ * checks its options), and TCI_ERANGE for a group of 2^31 values or more. TCI_ENOMEM, with the byte count in the
+ * message, when the transformed chain and the sort's keys do not fit the device. */
+int tci_chainrank(tci_ctx* ctx, const tci_chainrank_options* opt, const double* chain, const double* s2chain,
+                  int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, const int32_t* group,
+                  int64_t n_groups, tci_chainrank_outputs* out);
+
+/* tci_dram_run_ess plus the rank diagnostics of the same groups over the same rows, all taken from the device chain
+ * before any copy. rout and eout may be NULL here; kout is required; ropt, eopt and kopt may be NULL. */
+int tci_dram_run_rank(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                      const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                      const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                      tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                      tci_chainess_outputs* eout, const tci_chainrank_options* kopt, tci_chainrank_outputs* kout);
+
 /* ---- Posterior predictive fit checks per cell (WAIC, PIT, coverage, reduced chi^2, Durbin-Watson) ----
  * Does the fitted model describe a cell's data? Every observed MS2 and PP7 value is scored under the Gaussian-mixture
  * posterior predictive distribution that S posterior samples (theta_s, sigma2_s) define: (1 / S) sum_s
@@ -1117,6 +1220,14 @@ int tci_demc_run(tci_ctx* ctx, const tci_demc_options* opt, const double* pop0, 
                  const double* prior_sig, const double* jitter, const double* sigma2_0, tci_demc_outputs* out,
                  const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
                  tci_chainess_outputs* eout);
+
+/* tci_demc_run plus tci_chainrank (kopt may be NULL) of the same groups over the same kept rows, from the device chain
+ * before any copy; kout NULL: exactly tci_demc_run. The options of kopt are checked with the other reductions'. */
+int tci_demc_run_rank(tci_ctx* ctx, const tci_demc_options* opt, const double* pop0, int64_t ld, const int32_t* cell_id,
+                      int64_t n_sel, int64_t n_pop, const double* lower, const double* upper, const double* prior_mu,
+                      const double* prior_sig, const double* jitter, const double* sigma2_0, tci_demc_outputs* out,
+                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                      tci_chainess_outputs* eout, const tci_chainrank_options* kopt, tci_chainrank_outputs* kout);
 
 const char* tci_version(void);
 

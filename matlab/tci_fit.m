@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch, MCMCdemc] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch, MCMCdemc, MCMCrank] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -69,6 +69,13 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtem
 %        every kept row). Fills the ninth output MCMCdemc, one entry per fitted cell: accept_rate, n_oob, n_evals
 %        (1 x n_pop), rhat_max, ess_min (across the members, parameters and sigma2), n_pop, n_gen, cell_index.
 %        Not with 'temper', 'diagnostics', 'logpost', 'stack' or 'predict'.)
+%     'rank' (0; 1 fills the tenth output MCMCrank, one entry per fitted cell, with the rank diagnostics of Vehtari et
+%        al. (2021) over the kept rows at or past n_burn (tci_chainrank, include/tci.h; options.rank of
+%        tci_mex('dram') / tci_mex('demc'), reduced from the device chain): across the cell's DE-MC members with
+%        'demc', else of the cell's one chain (its two halves). Fields, 7+N+1 columns wide (theta order, sigma2
+%        last): q (nq x .) at probs, q_tail (2 x .) at tail, rhat_bulk, rhat_folded, rhat_rank, ess_bulk, tau_bulk,
+%        ess_tail_lo, ess_tail_hi, ess_tail, window_bulk, window_tail_lo, window_tail_hi (1 x .), n_rows,
+%        cell_index. Needs 'thin' > 0; not with 'temper' or 'logpost'.)
 %
 %   x0 is drawn from MATLAB's global RNG exactly as :200-208 draw it (rand, normrnd); the chains use
 %   the device's Philox streams keyed by (seed, cell number), so a cell's chain does not depend on
@@ -102,6 +109,7 @@ p.addParameter('temper', 1);
 p.addParameter('swap_every', 1);
 p.addParameter('presearch', []);
 p.addParameter('demc', []);
+p.addParameter('rank', 0);
 p.parse(varargin{:});
 o = p.Results;
 n_burn = o.n_burn;
@@ -181,7 +189,10 @@ end
 MCMCchain = struct('v_chain',{},'ton_chain',{},'A_chain',{},'tau_chain',{},...
     'MS2_basal_chain',{},'PP7_basal_chain',{},'R_chain',{},'dR_chain',{},'s2chain',{});
 MCMCdiag = struct([]); MCMClp = struct([]); MCMCstack = struct([]); MCMCtemper = struct([]);
-MCMCsearch = struct([]); MCMCdemc = struct([]);
+MCMCsearch = struct([]); MCMCdemc = struct([]); MCMCrank = struct([]);
+if o.rank && o.thin <= 0
+    error('tci:rank', 'the rank diagnostics need the kept chain rows: thin > 0');
+end
 nc = numel(setup);
 if nc == 0
     return
@@ -287,7 +298,7 @@ if ~isempty(dm)                                     % ---- the DE-MC fit: every 
     end
     D = tci_mex('demc', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, ...
         struct('n_gen', dm(2), 'thin', o.thin, 'stats_from', n_burn, 'seed', o.seed*1000003 + 20201028, ...
-        'keys', [setup.cellNum] - 1, 'rhat', 1, 'ess', 1));
+        'keys', [setup.cellNum] - 1, 'rhat', 1, 'ess', 1, 'rank', double(o.rank ~= 0)));
     sel = o.thin*(0:size(D.chain, 3)-1) >= n_burn;  % kept row r is generation (r - 1)*thin
     for k = 1:nc
         n = numel(setup(k).t);
@@ -318,6 +329,10 @@ if ~isempty(dm)                                     % ---- the DE-MC fit: every 
             'rhat_max', D.rhat_max(k), 'ess_min', D.ess_min(k), 'n_pop', n_pop, 'n_gen', dm(2), ...
             'cell_index', setup(k).cellNum);
         if isempty(MCMCdemc), MCMCdemc = dk; else, MCMCdemc(k) = dk; end
+        if o.rank
+            rk = rank_entry(D.rank, k, n, setup(k).cellNum);
+            if isempty(MCMCrank), MCMCrank = rk; else, MCMCrank(k) = rk; end
+        end
         if ~isempty(search)
             qk = struct('f_best', search.f_best(k), 'ss_best', search.ss_best(k), 'theta_best', search.theta_best(1:7+n, k)', ...
                 'f0_best', search.f_trace(k, 1), 'f_trace', search.f_trace(k, :), 'n_gen', size(search.f_trace, 2) - 1, ...
@@ -351,6 +366,12 @@ if o.stack && o.thin <= 0
 end
 if o.stack
     options.stack = o.stack;
+end
+if o.rank
+    if R > 1 || o.logpost
+        error('tci:rank', 'rank cannot be combined with temper or logpost');
+    end
+    options.rank = 1;
 end
 if o.diagnostics && o.thin <= 0
     error('tci:diagnostics', 'the diagnostics need the kept chain rows: thin > 0');
@@ -452,6 +473,10 @@ for k = 1:nc
             'cell_index', setup(k).cellNum);
         if isempty(MCMCstack), MCMCstack = sk; else, MCMCstack(k) = sk; end
     end
+    if o.rank
+        rk = rank_entry(results.rank, results.rank.group(k), n, setup(k).cellNum);
+        if isempty(MCMCrank), MCMCrank = rk; else, MCMCrank(k) = rk; end
+    end
     if ~isempty(search)
         qk = struct('f_best', search.f_best(k), 'ss_best', search.ss_best(k), 'theta_best', search.theta_best(1:7+n, k)', ...
             'f0_best', search.f_trace(k, 1), 'f_trace', search.f_trace(k, :), 'n_gen', size(search.f_trace, 2) - 1, ...
@@ -477,4 +502,16 @@ for k = 1:nc
             'MS2_basal_chain', [], 'PP7_basal_chain', [], 'R_chain', [], 'dR_chain', [], 's2chain', []);
     end
 end
+end
+
+function rk = rank_entry(K, g, n, cellNum)
+% One MCMCrank entry from group g of res.rank of tci_mex('dram') / tci_mex('demc'), a cell of n points: the vectors
+% trimmed to the cell's 7 + n parameters with sigma2 appended as the last column.
+rk = struct('q', [K.q(1:7+n, :, g)', K.s2_q(:, g)], 'q_tail', [K.q_tail(1:7+n, :, g)', K.s2_q_tail(:, g)]);
+for f = {'rhat_bulk', 'rhat_folded', 'rhat_rank', 'ess_bulk', 'tau_bulk', 'ess_tail_lo', 'ess_tail_hi', 'ess_tail', ...
+         'window_bulk', 'window_tail_lo', 'window_tail_hi'}
+    rk.(f{1}) = [K.(f{1})(1:7+n, g)', K.(['s2_' f{1}])(g)];
+end
+rk.n_rows = K.n_rows;
+rk.cell_index = cellNum;
 end

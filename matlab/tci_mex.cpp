@@ -98,6 +98,18 @@
 //          include/tci.h), reduced on the device: arguments as for 'chainrhat'; max_lag: cap on the lags (default 0 =
 //          none). out: struct with ess, ess_split, tau, tau_split, mcse, window, window_split (P x n_groups; the
 //          windows as doubles; NaN / -1 past a group's npar) and n_rows.
+//   out = tci_mex('chainrank', h, chain, npar, group[, max_lag[, probs[, tail]]])
+//          the rank-normalised split R-hat, bulk and tail ESS and pooled quantiles of replicate chains (Vehtari et al.
+//          2021; tci_chainrank, the definition is in include/tci.h), from one pooled sort per group and column on the
+//          device: arguments as for 'chainess'; probs: 1 to 16 probabilities (default [0.025 0.5 0.975]); tail: [lo hi]
+//          (default [0.05 0.95]); [] = the default. out: struct with q (P x nq x n_groups), q_tail (P x 2 x n_groups),
+//          rhat_bulk, rhat_folded, rhat_rank, ess_bulk, tau_bulk, ess_tail_lo, ess_tail_hi, ess_tail, window_bulk,
+//          window_tail_lo, window_tail_hi (P x n_groups; the windows as doubles; NaN / -1 past a group's npar) and n_rows.
+//   options.rank of 'dram' and 'demc': 1, or a struct with probs and / or tail: res.rank, the 'chainrank' struct with its
+//          s2 twins (s2_q nq x n_groups, s2_q_tail 2 x n_groups, the others 1 x n_groups) and group (1 x n_chains,
+//          1-based), over the kept rows at or past stats_from, from the device chain (tci_dram_run_rank: the chains of
+//          one cell form a group, numbered by first appearance; tci_demc_run_rank: a cell's members). options.max_lag
+//          caps the lags. 'dram' refuses it with options.logpost or options.temper.
 //   out = tci_mex('chainlp', h, cells, chain, s2chain, MU, SIG)
 //          the sum-of-squares trace of chains (mcmcstat's sschain, mcmcrun's fourth output), the prior, deviance and
 //          log-posterior of every row, and per chain the best sample and DIC (tci_chainlp, the definition is in
@@ -706,6 +718,102 @@ struct StatsOut {
   }
 };
 
+// The struct of 'chainrank' and of res.rank of 'dram' / 'demc', written in place by the ABI: q P x nq x n_groups ==
+// [group][nq][P], q_tail P x 2 x n_groups, the other vectors P x n_groups == [group][P] (the windows as doubles), and
+// their s2 twins without the leading P (nq x n_groups, 2 x n_groups, 1 x n_groups) and group (1 x n_chains, 1-based:
+// the group of every chain, set by the caller) when with_s2.
+struct RankOut {
+  mxArray* res;
+  mxArray* a[13];
+  mxArray* b[13];
+  std::vector<int32_t> win, s2win;
+  size_t P, ng;
+  bool s2;
+  tci_chainrank_outputs out;
+  static const char* const* names() {
+    static const char* f[] = {"q", "q_tail", "rhat_bulk", "rhat_folded", "rhat_rank", "ess_bulk", "tau_bulk",
+                              "ess_tail_lo", "ess_tail_hi", "ess_tail", "window_bulk", "window_tail_lo", "window_tail_hi",
+                              "n_rows", "s2_q", "s2_q_tail", "s2_rhat_bulk", "s2_rhat_folded", "s2_rhat_rank",
+                              "s2_ess_bulk", "s2_tau_bulk", "s2_ess_tail_lo", "s2_ess_tail_hi", "s2_ess_tail",
+                              "s2_window_bulk", "s2_window_tail_lo", "s2_window_tail_hi", "group"};
+    return f;
+  }
+  RankOut(size_t P_, size_t ng_, size_t nq, bool with_s2) : win(3 * P_ * ng_), s2win(3 * ng_), P(P_), ng(ng_), s2(with_s2) {
+    const char* const* f = names();
+    res = mxCreateStructMatrix(1, 1, s2 ? 28 : 14, const_cast<const char**>(f));  // the samplers': s2 twins and group
+    const mwSize dq[3] = {(mwSize)P, (mwSize)nq, (mwSize)ng}, dt[3] = {(mwSize)P, 2, (mwSize)ng};
+    a[0] = mxCreateNumericArray(3, dq, mxDOUBLE_CLASS, mxREAL);
+    a[1] = mxCreateNumericArray(3, dt, mxDOUBLE_CLASS, mxREAL);
+    for (int k = 2; k < 13; ++k) a[k] = mxCreateDoubleMatrix(P, ng, mxREAL);
+    for (int k = 0; k < 13; ++k) mxSetField(res, 0, f[k], a[k]);
+    memset(&out, 0, sizeof out);
+    double** d[10] = {&out.q, &out.q_tail, &out.rhat_bulk, &out.rhat_folded, &out.rhat_rank, &out.ess_bulk, &out.tau_bulk,
+                      &out.ess_tail_lo, &out.ess_tail_hi, &out.ess_tail};
+    for (int k = 0; k < 10; ++k) *d[k] = mxGetPr(a[k]);
+    out.window_bulk = win.data();
+    out.window_tail_lo = win.data() + P * ng;
+    out.window_tail_hi = win.data() + 2 * P * ng;
+    if (s2) {
+      b[0] = mxCreateDoubleMatrix(nq, ng, mxREAL);
+      b[1] = mxCreateDoubleMatrix(2, ng, mxREAL);
+      for (int k = 2; k < 13; ++k) b[k] = mxCreateDoubleMatrix(1, ng, mxREAL);
+      for (int k = 0; k < 13; ++k) mxSetField(res, 0, f[14 + k], b[k]);
+      double** e[10] = {&out.s2_q, &out.s2_q_tail, &out.s2_rhat_bulk, &out.s2_rhat_folded, &out.s2_rhat_rank,
+                        &out.s2_ess_bulk, &out.s2_tau_bulk, &out.s2_ess_tail_lo, &out.s2_ess_tail_hi, &out.s2_ess_tail};
+      for (int k = 0; k < 10; ++k) *e[k] = mxGetPr(b[k]);
+      out.s2_window_bulk = s2win.data();
+      out.s2_window_tail_lo = s2win.data() + ng;
+      out.s2_window_tail_hi = s2win.data() + 2 * ng;
+    }
+  }
+  mxArray* finish() {
+    for (int f = 0; f < 3; ++f) {
+      for (size_t e = 0; e < P * ng; ++e) mxGetPr(a[10 + f])[e] = (double)win[f * P * ng + e];
+      if (s2)
+        for (size_t e = 0; e < ng; ++e) mxGetPr(b[10 + f])[e] = (double)s2win[f * ng + e];
+    }
+    mxSetField(res, 0, "n_rows", mxCreateDoubleScalar((double)out.n_rows));
+    return res;
+  }
+};
+
+// options.rank of 'dram' / 'demc': 0 / absent = none, 1 = the defaults, or a struct with probs (1 to 16 in [0, 1]) and
+// tail ([lo hi], 0 < lo < hi < 1), either optional. *want: whether the rank diagnostics are asked for.
+void rank_option(const mxArray* o, tci_chainrank_options* k, bool* want) {
+  tci_chainrank_defaults(k);
+  const mxArray* r = o ? mxGetField(o, 0, "rank") : nullptr;
+  *want = false;
+  if (!r || mxGetNumberOfElements(r) == 0) return;
+  if (mxIsStruct(r)) {
+    if (mxGetNumberOfElements(r) != 1) mexErrMsgIdAndTxt("tci:opts", "options.rank must be 0, 1 or a 1x1 struct");
+    for (int f = 0; f < mxGetNumberOfFields(r); ++f) {
+      const char* fn = mxGetFieldNameByNumber(r, f);
+      if (strcmp(fn, "probs") != 0 && strcmp(fn, "tail") != 0)
+        mexErrMsgIdAndTxt("tci:opts", "options.rank.%s is not a field of options.rank (probs, tail)", fn);
+    }
+    if (const mxArray* pr = mxGetField(r, 0, "probs")) {
+      const size_t nq = mxGetNumberOfElements(pr);
+      if (nq < 1 || nq > 16) mexErrMsgIdAndTxt("tci:opts", "options.rank.probs must hold 1 to 16 probabilities");
+      const double* v = doubles(pr, (long long)nq, "options.rank.probs");
+      for (size_t q = 0; q < nq; ++q) {
+        if (!(v[q] >= 0 && v[q] <= 1)) mexErrMsgIdAndTxt("tci:opts", "options.rank.probs(%d) must be in [0, 1]", (int)q + 1);
+        k->probs[q] = v[q];
+      }
+      k->nq = (int32_t)nq;
+    }
+    if (const mxArray* tl = mxGetField(r, 0, "tail")) {
+      const double* v = doubles(tl, 2, "options.rank.tail");
+      if (!(v[0] > 0 && v[0] < v[1] && v[1] < 1))
+        mexErrMsgIdAndTxt("tci:opts", "options.rank.tail must be [lo hi] with 0 < lo < hi < 1");
+      k->tail_lo = v[0];
+      k->tail_hi = v[1];
+    }
+    *want = true;
+    return;
+  }
+  *want = doubles(r, 1, "options.rank")[0] != 0.0;
+}
+
 // The struct of 'chainlp' and of 'dram''s res.logpost, written in place by the ABI: the traces n x rows == [row][chain],
 // the per-chain scalars 1 x n, theta_best and theta_mean P x n == [chain][P]; best_row 1-based (0 = none).
 struct LpOut {
@@ -830,7 +938,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"nsimu", "burnintime", "adaptint", "method", "updatesigma", "drscale", "adascale",
                                   "qcovadj", "burnin_scale", "stats_from", "thin", "seed", "engine", "max_chunk",
-                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "temper", "swap_every", "presearch", "presearch_gen",
+                                  "chain_keys", "adapt_pmax", "max_lag", "logpost", "stack", "rank", "temper", "swap_every", "presearch", "presearch_gen",
                                   "presearch_F", "presearch_CR", "verbosity",
                                   "waitbar",
                                   "printint"};
@@ -868,7 +976,15 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   const bool want_lp = opt_num(o, "logpost", 0.0) != 0.0;
   const int64_t stack = opt_int(o, "stack", 0, 0);  // 0: none; else the sample count of res.stack
   if (stack != 0 && (stack < 32 || stack > 4096)) mexErrMsgIdAndTxt("tci:opts", "options.stack must be 0 or in [32, 4096]");
-  opt.thin = want_chain || want_lp || stack ? thin : 0;
+  // options.rank: tci_chainrank (with options.max_lag) of the kept rows at or past stats_from across the chains of
+  // every cell (a group per cell, numbered by first appearance), from the device chain (tci_dram_run_rank)
+  tci_chainrank_options kopt;
+  bool want_rank = false;
+  rank_option(o, &kopt, &want_rank);
+  kopt.max_lag = opt_int(o, "max_lag", 0, 0);
+  opt.thin = want_chain || want_lp || stack || want_rank ? thin : 0;
+  if (want_rank && opt.thin < 1) mexErrMsgIdAndTxt("tci:opts", "options.rank needs the kept rows: options.thin must be >= 1");
+  if (want_rank && want_lp) mexErrMsgIdAndTxt("tci:opts", "options.rank cannot be combined with options.logpost");
   int64_t st_rows = 0, st_k0 = 0;  // the kept rows at or past stats_from, and the first of them
   if (stack) {
     if (opt.thin < 1) mexErrMsgIdAndTxt("tci:opts", "options.stack needs the kept rows: options.thin must be >= 1");
@@ -890,6 +1006,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   std::vector<int32_t> t_ladder;
   const mxArray* tm = o ? mxGetField(o, 0, "temper") : nullptr;
   const bool want_temper = tm != nullptr && mxGetNumberOfElements(tm) != 0;
+  if (want_rank && want_temper) mexErrMsgIdAndTxt("tci:opts", "options.rank cannot be combined with options.temper");
   tci_temper_options topt;
   tci_temper_defaults(&topt);
   topt.swap_every = opt_int(o, "swap_every", 1, 0);
@@ -977,6 +1094,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (want_temper) fields.push_back("temper");
   else if (want_lp) fields.push_back("logpost");
   if (stack) fields.push_back("stack");
+  if (want_rank) fields.push_back("rank");
   if (want_ps) fields.push_back("presearch");
   mxArray* res = mxCreateStructMatrix(1, 1, (int)fields.size(), fields.data());
   mxArray* pn[6];
@@ -1042,7 +1160,20 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     }
     tout.swap_log_rows = (int64_t)t_ev;
   }
-  const int rc = want_temper ? tci_dram_run_tempered(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
+  std::vector<int32_t> k_group(n, -1), k_cell;  // options.rank: the chains of one cell form a group
+  for (size_t b = 0; b < n && want_rank; ++b) {
+    for (size_t g = 0; g < k_cell.size() && k_group[b] < 0; ++g)
+      if (k_cell[g] == cid[b]) k_group[b] = (int32_t)g;
+    if (k_group[b] < 0) {
+      k_group[b] = (int32_t)k_cell.size();
+      k_cell.push_back(cid[b]);
+    }
+  }
+  RankOut ro(want_rank ? P : 0, want_rank ? k_cell.size() : 0, (size_t)kopt.nq, true);
+  const int rc = want_rank ? tci_dram_run_rank(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
+                                               s2v.data(), (int64_t)P, &out, &red, k_group.data(), (int64_t)k_cell.size(),
+                                               nullptr, nullptr, nullptr, nullptr, &kopt, &ro.out)
+                 : want_temper ? tci_dram_run_tempered(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4],
                                                      in[5], s2v.data(), (int64_t)P, &out, &red, nullptr, 0, nullptr,
                                                      nullptr, &topt, &tout)
                  : want_lp ? tci_dram_run_lp(ctx, &opt, (int64_t)n, cid.data(), in[0], in[1], in[2], in[3], in[4], in[5],
@@ -1054,6 +1185,7 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                              s2v.data(), (int64_t)P, &out);
   if (rc != TCI_OK || !want_stats) mxDestroyArray(so.res);
   if (rc != TCI_OK || !want_lp) mxDestroyArray(lo.res);
+  if (rc != TCI_OK || !want_rank) mxDestroyArray(ro.res);
   if (rc != TCI_OK) {
     mxDestroyArray(res);
     if (ch) mxDestroyArray(ch);
@@ -1146,6 +1278,13 @@ void cmd_dram(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxSetField(so2.res, 0, "group", gm);
     mxSetField(so2.res, 0, "rows", rm);
     mxSetField(res, 0, "stack", so2.res);
+  }
+  if (want_rank) {
+    mxArray* gm = mxCreateDoubleMatrix(1, n, mxREAL);
+    for (size_t b = 0; b < n; ++b) mxGetPr(gm)[b] = (double)k_group[b] + 1.0;
+    mxArray* r = ro.finish();
+    mxSetField(r, 0, "group", gm);
+    mxSetField(res, 0, "rank", r);
   }
   if (want_ps) mxSetField(res, 0, "presearch", ps_res);
   plhs[0] = res;
@@ -1551,6 +1690,78 @@ void cmd_chainess(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = res;
 }
 
+// ---- 'chainrank': rank-normalised R-hat, bulk and tail ESS and pooled quantiles of every group -----------
+
+void cmd_chainrank(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  (void)nlhs;
+  if (nrhs < 5 || nrhs > 8)
+    mexErrMsgIdAndTxt("tci:arg", "tci_mex('chainrank', h, chain, npar, group[, max_lag[, probs[, tail]]])");
+  // every argument is checked before the handle (and before anything reaches the GPU)
+  const double* X = doubles(prhs[2], -1, "chain");
+  const mwSize nd = mxGetNumberOfDimensions(prhs[2]);
+  const mwSize* d = mxGetDimensions(prhs[2]);
+  const size_t P = d[0], n = nd > 1 ? d[1] : 1, rows = nd > 2 ? d[2] : 1;  // trailing singletons are dropped
+  if (nd > 3 || P < 1 || n < 1 || rows < 1) mexErrMsgIdAndTxt("tci:arg", "chain must be P x n x rows, as 'dram' returns it");
+  std::vector<int32_t> npar;
+  if (mxGetNumberOfElements(prhs[3]) != 0) {  // [] = P for every chain
+    const double* np = doubles(prhs[3], (long long)n, "npar");
+    npar.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+      if (!(np[b] >= 0 && np[b] <= (double)P) || np[b] != (double)(int64_t)np[b])
+        mexErrMsgIdAndTxt("tci:arg", "npar(%d) must be an integer in [0, P]", (int)b + 1);
+      npar[b] = (int32_t)np[b];
+    }
+  }
+  std::vector<int32_t> group;  // 0-based for the ABI; MATLAB's 0 (no group) becomes -1
+  size_t ng = 1;
+  if (mxGetNumberOfElements(prhs[4]) != 0) {  // [] = one group of all chains
+    const double* gp = doubles(prhs[4], (long long)n, "group");
+    group.resize(n);
+    ng = 0;
+    for (size_t b = 0; b < n; ++b) {
+      if (!(gp[b] >= 0 && gp[b] <= (double)n) || gp[b] != (double)(int64_t)gp[b])
+        mexErrMsgIdAndTxt("tci:arg", "group(%d) must be an integer in [0, n]", (int)b + 1);
+      group[b] = (int32_t)gp[b] - 1;
+      ng = std::max(ng, (size_t)gp[b]);
+    }
+    if (ng < 1) mexErrMsgIdAndTxt("tci:arg", "group names no group (all zero)");
+  }
+  tci_chainrank_options opt;
+  tci_chainrank_defaults(&opt);
+  if (nrhs >= 6 && mxGetNumberOfElements(prhs[5]) != 0) {
+    const double* ml = doubles(prhs[5], 1, "max_lag");
+    if (!(ml[0] >= 0 && ml[0] <= 1073741824.0) || ml[0] != (double)(int64_t)ml[0])
+      mexErrMsgIdAndTxt("tci:arg", "max_lag must be an integer in [0, 2^30]");
+    opt.max_lag = (int64_t)ml[0];
+  }
+  if (nrhs >= 7 && mxGetNumberOfElements(prhs[6]) != 0) {
+    const size_t nq = mxGetNumberOfElements(prhs[6]);
+    if (nq > 16) mexErrMsgIdAndTxt("tci:arg", "probs must hold 1 to 16 probabilities");
+    const double* pr = doubles(prhs[6], (long long)nq, "probs");
+    for (size_t q = 0; q < nq; ++q) {
+      if (!(pr[q] >= 0 && pr[q] <= 1)) mexErrMsgIdAndTxt("tci:arg", "probs(%d) must be in [0, 1]", (int)q + 1);
+      opt.probs[q] = pr[q];
+    }
+    opt.nq = (int32_t)nq;
+  }
+  if (nrhs == 8 && mxGetNumberOfElements(prhs[7]) != 0) {
+    const double* tl = doubles(prhs[7], 2, "tail");
+    if (!(tl[0] > 0 && tl[0] < tl[1] && tl[1] < 1)) mexErrMsgIdAndTxt("tci:arg", "tail must be [lo hi] with 0 < lo < hi < 1");
+    opt.tail_lo = tl[0];
+    opt.tail_hi = tl[1];
+  }
+  tci_ctx* ctx = handle_of(prhs[1]);
+  RankOut ro(P, ng, (size_t)opt.nq, false);
+  const int rc = tci_chainrank(ctx, &opt, X, nullptr, (int64_t)rows, (int64_t)n, (int64_t)P,
+                               npar.empty() ? nullptr : npar.data(), group.empty() ? nullptr : group.data(), (int64_t)ng,
+                               &ro.out);
+  if (rc != TCI_OK) {
+    mxDestroyArray(ro.res);
+    check(ctx, rc, "tci_chainrank");
+  }
+  plhs[0] = ro.finish();
+}
+
 // ---- 'chainlp': log-posterior trace, best sample and DIC of every chain -------------------------------
 
 void cmd_chainlp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -1695,7 +1906,7 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       mexErrMsgIdAndTxt("tci:opts", "options must be a 1x1 struct");
     o = prhs[10];
     static const char* known[] = {"n_gen", "thin", "jump_every", "stats_from", "updatesigma", "CR", "gamma0", "seed",
-                                  "keys", "log_rows", "rhat", "ess", "max_lag"};
+                                  "keys", "log_rows", "rhat", "ess", "max_lag", "rank"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
       bool ok = false;
@@ -1718,6 +1929,10 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   tci_chainess_options eopt;
   tci_chainess_defaults(&eopt);
   eopt.max_lag = opt_int(o, "max_lag", 0, 0);
+  tci_chainrank_options kopt;
+  bool want_rank = false;
+  rank_option(o, &kopt, &want_rank);
+  kopt.max_lag = eopt.max_lag;
   std::vector<int64_t> keys;
   if (const mxArray* k = o ? mxGetField(o, 0, "keys") : nullptr) {
     const double* kv = doubles(k, (long long)n, "options.keys");
@@ -1733,17 +1948,12 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   tci_ctx* ctx = handle_of(prhs[1]);
   const size_t B = n * n_pop, K = dopt.thin > 0 ? (size_t)(dopt.n_gen / dopt.thin) + 1 : 0;
   const size_t G = (size_t)std::min<int64_t>(log_rows, dopt.n_gen);
-  static const char* fields[] = {"chain", "s2chain", "sschain", "prichain", "pop", "s2", "ss", "accept_rate", "logr",
-                                 "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms", "rhat", "s2_rhat",
-                                 "rhat_max", "ess", "s2_ess", "ess_min"};
-  mxArray* res = mxCreateStructMatrix(1, 1, 15 + (want_rhat ? 3 : 0) + (want_ess ? 3 : 0), fields);
-  if (want_ess && !want_rhat) {  // the ESS fields follow the fixed ones directly
-    mxDestroyArray(res);
-    static const char* fields_e[] = {"chain", "s2chain", "sschain", "prichain", "pop", "s2", "ss", "accept_rate", "logr",
-                                     "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms", "ess", "s2_ess",
-                                     "ess_min"};
-    res = mxCreateStructMatrix(1, 1, 18, fields_e);
-  }
+  std::vector<const char*> fields = {"chain", "s2chain", "sschain", "prichain", "pop", "s2", "ss", "accept_rate", "logr",
+                                     "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms"};
+  if (want_rhat) fields.insert(fields.end(), {"rhat", "s2_rhat", "rhat_max"});
+  if (want_ess) fields.insert(fields.end(), {"ess", "s2_ess", "ess_min"});
+  if (want_rank) fields.push_back("rank");
+  mxArray* res = mxCreateStructMatrix(1, 1, (int)fields.size(), fields.data());
   const mwSize dc[3] = {P, B, K}, dp[3] = {P, n_pop, n};
   mxArray* a[9] = {mxCreateNumericArray(3, dc, mxDOUBLE_CLASS, mxREAL), mxCreateDoubleMatrix(B, K, mxREAL),
                    mxCreateDoubleMatrix(B, K, mxREAL), mxCreateDoubleMatrix(B, K, mxREAL),
@@ -1795,12 +2005,21 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxSetField(res, 0, "ess", e0);
     mxSetField(res, 0, "s2_ess", e1);
   }
-  const int rc = tci_demc_run(ctx, &dopt, pop, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, in[0], in[1], in[2], in[3],
-                              in[4], s2v.data(), &out, nullptr, want_rhat ? &rout : nullptr, &eopt,
-                              want_ess ? &eout : nullptr);
+  RankOut ro(want_rank ? P : 0, want_rank ? n : 0, (size_t)kopt.nq, true);  // a group per cell: its members
+  const int rc = tci_demc_run_rank(ctx, &dopt, pop, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, in[0], in[1], in[2],
+                                   in[3], in[4], s2v.data(), &out, nullptr, want_rhat ? &rout : nullptr, &eopt,
+                                   want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr);
+  if (rc != TCI_OK || !want_rank) mxDestroyArray(ro.res);
   if (rc != TCI_OK) {
     mxDestroyArray(res);
     check(ctx, rc, "tci_demc_run");
+  }
+  if (want_rank) {
+    mxArray* gm = mxCreateDoubleMatrix(1, B, mxREAL);
+    for (size_t b = 0; b < B; ++b) mxGetPr(gm)[b] = (double)(b / n_pop) + 1.0;
+    mxArray* r = ro.finish();
+    mxSetField(r, 0, "group", gm);
+    mxSetField(res, 0, "rank", r);
   }
   mxArray* io = mxCreateDoubleMatrix(n_pop, n, mxREAL);
   mxArray* ie = mxCreateDoubleMatrix(n_pop, n, mxREAL);
@@ -1863,6 +2082,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chaindens") cmd_chaindens(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainrhat") cmd_chainrhat(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainess") cmd_chainess(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "chainrank") cmd_chainrank(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainlp") cmd_chainlp(nlhs, plhs, nrhs, prhs);
   else if (cmd == "modesearch") cmd_modesearch(nlhs, plhs, nrhs, prhs);
   else if (cmd == "demc") cmd_demc(nlhs, plhs, nrhs, prhs);

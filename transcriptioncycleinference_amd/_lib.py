@@ -151,6 +151,24 @@ class tci_chainess_outputs(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class tci_chainrank_options(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("probs", C.c_double * 16), ("tail_lo", C.c_double), ("tail_hi", C.c_double),
+                ("max_lag", C.c_int64), ("flags", C.c_int64)]
+
+
+# per-group outputs of tci_chainrank, in the struct's order: doubles, then windows; each has an s2 twin
+CHAINRANK_DOUBLES = ("q", "q_tail", "rhat_bulk", "rhat_folded", "rhat_rank", "ess_bulk", "tau_bulk", "ess_tail_lo",
+                     "ess_tail_hi", "ess_tail")
+CHAINRANK_WINDOWS = ("window_bulk", "window_tail_lo", "window_tail_hi")
+
+
+class tci_chainrank_outputs(C.Structure):
+    _fields_ = ([(f, _dp) for f in CHAINRANK_DOUBLES] + [(f, _i32p) for f in CHAINRANK_WINDOWS]
+                + [("s2_" + f, _dp) for f in CHAINRANK_DOUBLES] + [("s2_" + f, _i32p) for f in CHAINRANK_WINDOWS]
+                + [("z", _dp), ("z_folded", _dp), ("s2_z", _dp), ("s2_z_folded", _dp), ("n_rows", C.c_int64),
+                   ("kernel_ms", C.c_double), ("rank_ms", C.c_double)])
+
+
 class tci_temper_options(C.Structure):
     _fields_ = [("beta", _dp), ("ladder", _i32p), ("n_ladders", C.c_int64), ("swap_every", C.c_int64),
                 ("flags", C.c_int64)]
@@ -269,6 +287,16 @@ SIGNATURES = [
                                    C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
                                    C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                    C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs)]),
+    ("tci_chainrank_defaults", C.c_int, [C.POINTER(tci_chainrank_options)]),
+    ("tci_chainrank_lds_cap", C.c_int64, []),
+    ("tci_chainrank", C.c_int, [C.c_void_p, C.POINTER(tci_chainrank_options), _dp, _dp, C.c_int64, C.c_int64,
+                                C.c_int64, _i32p, _i32p, C.c_int64, C.POINTER(tci_chainrank_outputs)]),
+    ("tci_dram_run_rank", C.c_int, [C.c_void_p, C.POINTER(tci_dram_options), C.c_int64, _i32p, _dp, _dp, _dp, _dp,
+                                    _dp, _dp, _dp, C.c_int64, C.POINTER(tci_dram_outputs),
+                                    C.POINTER(tci_dram_reductions), _i32p, C.c_int64,
+                                    C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                    C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
+                                    C.POINTER(tci_chainrank_options), C.POINTER(tci_chainrank_outputs)]),
     ("tci_fitcheck_defaults", C.c_int, [C.POINTER(tci_fitcheck_options)]),
     ("tci_fitcheck", C.c_int, [C.c_void_p, C.POINTER(tci_fitcheck_options), _dp, C.c_int64, _dp, _i32p, C.c_int64,
                                C.c_int64, C.c_int64, C.POINTER(tci_fitcheck_outputs)]),
@@ -298,6 +326,11 @@ SIGNATURES = [
                                _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_demc_outputs),
                                C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs)]),
+    ("tci_demc_run_rank", C.c_int, [C.c_void_p, C.POINTER(tci_demc_options), _dp, C.c_int64, _i32p, C.c_int64, C.c_int64,
+                                    _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_demc_outputs),
+                                    C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                    C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
+                                    C.POINTER(tci_chainrank_options), C.POINTER(tci_chainrank_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -390,6 +390,31 @@ int chainrhat_groups(tci_ctx* ctx, const char* who, const tci_chainrhat_options*
   return TCI_OK;
 }
 
+namespace {
+
+// tci_chainess's cap = (m L) log10(m L) of every group: cap[g] classic (m = M, L = n), cap[n_groups + g] split
+// (m = 2 M, L = h).
+void ess_caps(const RhatGroups& G, int64_t n_rows, double* cap) {
+  const size_t ng = G.off.size() - 1;
+  const int64_t h = n_rows / 2;
+  for (size_t g = 0; g < ng; ++g) {
+    const int64_t M = G.off[g + 1] - G.off[g];
+    const double tc = (double)(M * n_rows), ts = (double)(2 * M * h);
+    cap[g] = tc > 0 ? tc * std::log10(tc) : 0.0;
+    cap[ng + g] = ts > 0 ? ts * std::log10(ts) : 0.0;
+  }
+}
+
+// The three vectors of G onto the device, asynchronously: G outlives the stream's next synchronisation.
+hipError_t upload_groups(const RhatGroups& G, int32_t* d_group, int32_t* d_off, int32_t* d_list, hipStream_t s) {
+  hipError_t e = hipMemcpyAsync(d_group, G.group.data(), G.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_off, G.off.data(), G.off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_list, G.list.data(), G.list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  return e;
+}
+
+}  // namespace
+
 // The group kernels on a device chain (launch_chainrhat), timed with HIP events, and their results scattered into
 // the caller's host buffers (d_npar null: ld columns for every chain; d_s2 null: the s2 twins are NaN).
 int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
@@ -420,13 +445,7 @@ int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const
       he.resize(5 * plane);
       hw.resize(2 * plane);
       hcap.assign(2 * ng, 0.0);
-      const int64_t h = n_rows / 2;
-      for (size_t g = 0; g < ng; ++g) {  // cap = (m L) log10(m L): classic m = M, L = n; split m = 2 M, L = h
-        const int64_t M = G.off[g + 1] - G.off[g];
-        const double tc = (double)(M * n_rows), ts = (double)(2 * M * h);
-        hcap[g] = tc > 0 ? tc * std::log10(tc) : 0.0;
-        hcap[ng + g] = ts > 0 ? ts * std::log10(ts) : 0.0;
-      }
+      ess_caps(G, n_rows, hcap.data());
     }
   } catch (const std::bad_alloc&) {
     return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
@@ -436,9 +455,7 @@ int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const
   const char* what_create = nullptr;
   if ((e = timer.create(&what_create)) != hipSuccess) return hip_fail(ctx, e, what_create);
   // from here every path reaches the hipStreamSynchronize below: G's vectors outlive their uploads
-  e = hipMemcpyAsync(d_group, G.group.data(), G.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_off, G.off.data(), G.off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_list, G.list.data(), G.list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  e = upload_groups(G, d_group, d_off, d_list, s);
   if (e == hipSuccess && eout) e = hipMemcpyAsync(d_cap, hcap.data(), hcap.size() * sizeof(double), hipMemcpyHostToDevice, s);
   hipError_t e1 = e == hipSuccess ? timer.start(s) : e;
   const int rc = e != hipSuccess ? TCI_OK
@@ -489,6 +506,177 @@ int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const
     eout->n_rows = n_rows;
     eout->kernel_ms = ms;
   }
+  return TCI_OK;
+}
+
+// Checks of tci_chainrank_options before any device work; *o: the options to use (the defaults for null).
+int chainrank_opts(tci_ctx* ctx, const char* who, const tci_chainrank_options* kopt, tci_chainrank_options* o) {
+  tci_chainrank_defaults(o);
+  if (kopt) *o = *kopt;
+  if (o->nq < 1 || o->nq > 16) return fail(ctx, TCI_EINVAL, std::string(who) + ": nq must be in [1, 16]");
+  for (int32_t q = 0; q < o->nq; ++q)
+    if (!(o->probs[q] >= 0.0 && o->probs[q] <= 1.0))
+      return fail(ctx, TCI_EINVAL, std::string(who) + ": probs[" + std::to_string(q) + "] is not in [0, 1]");
+  if (!(o->tail_lo > 0.0 && o->tail_lo < o->tail_hi && o->tail_hi < 1.0))
+    return fail(ctx, TCI_EINVAL, std::string(who) + ": the tails must satisfy 0 < tail_lo < tail_hi < 1");
+  if (o->max_lag < 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": max_lag must be >= 0");
+  if (o->flags != 0) return fail(ctx, TCI_EINVAL, std::string(who) + ": flags is reserved and must be 0");
+  return TCI_OK;
+}
+
+// The rank diagnostics on a device chain: four passes through one transformed chain (z, z_folded, I_lo, I_hi), each
+// launch_chainrank followed by launch_chainess (launch_chainrhat for the folded scores), timed with HIP events, and
+// their results scattered into the caller's host buffers.
+int chainrank_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                     int64_t n_chains, int64_t ld, const int32_t* d_npar, const RhatGroups& G, int64_t n_groups,
+                     const tci_chainrank_options& o, tci_chainrank_outputs* out) {
+  const size_t ldc = (size_t)ld + 1, L = (size_t)ld, ng = (size_t)n_groups, plane = ng * ldc;
+  const size_t nqq = (size_t)o.nq + 3, nch = (size_t)n_rows * (size_t)n_chains * L, ns2 = (size_t)n_rows * (size_t)n_chains;
+  int64_t stride = 0;
+  size_t keys = 0;
+  int rc = tci::chainrank_scratch_keys(n_rows, ld, n_groups, G.off.data(), &stride, &keys);
+  if (rc == TCI_ENOMEM) return fail(ctx, TCI_ENOMEM, std::string(who) + ": the sort's keys are larger than any device memory");
+  if (rc != TCI_OK)
+    return fail(ctx, TCI_ERANGE, std::string(who) + ": a group of 2^31 values or more, or a launch of 2^31 workgroups");
+  DevAllocs A;
+  hipError_t e = hipSuccess;
+  void* d_scratch = A.alloc<uint8_t>(G.scratch, &e);
+  double* d_z = e == hipSuccess ? A.alloc<double>(nch, &e) : nullptr;
+  double* d_zs2 = e == hipSuccess && d_s2 ? A.alloc<double>(ns2, &e) : nullptr;
+  uint64_t* d_gk = e == hipSuccess && keys ? A.alloc<uint64_t>(keys, &e) : nullptr;
+  double* d_q = e == hipSuccess ? A.alloc<double>(nqq * plane, &e) : nullptr;
+  double* d_o = e == hipSuccess ? A.alloc<double>(16 * plane, &e) : nullptr;   // launch_chainrhat's out of every pass
+  double* d_ed = e == hipSuccess ? A.alloc<double>(15 * plane, &e) : nullptr;  // launch_chainess's: z, I_lo, I_hi
+  int32_t* d_ew = e == hipSuccess ? A.alloc<int32_t>(6 * plane, &e) : nullptr;
+  double* d_cap = e == hipSuccess ? A.alloc<double>(2 * ng, &e) : nullptr;
+  int32_t* d_group = e == hipSuccess ? A.alloc<int32_t>(G.group.size(), &e) : nullptr;
+  int32_t* d_off = e == hipSuccess ? A.alloc<int32_t>(G.off.size(), &e) : nullptr;
+  int32_t* d_list = e == hipSuccess ? A.alloc<int32_t>(G.list.size(), &e) : nullptr;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": device allocation of the transformed chain and the sort's keys (" +
+                                     std::to_string(G.scratch + (nch + (d_s2 ? ns2 : 0) + keys + (nqq + 31) * plane + 2 * ng) *
+                                                                    sizeof(double) +
+                                                    (6 * plane + G.group.size() + G.off.size() + G.list.size()) *
+                                                        sizeof(int32_t)) +
+                                     " bytes) failed");
+  }
+  std::vector<double> ho, he, hq, hcap;
+  std::vector<int32_t> hw;
+  try {
+    ho.resize(16 * plane);
+    he.resize(15 * plane);
+    hw.resize(6 * plane);
+    hq.resize(nqq * plane);
+    hcap.assign(2 * ng, 0.0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, TCI_ENOMEM, std::string(who) + ": host allocation failed");
+  }
+  ess_caps(G, n_rows, hcap.data());
+  hipStream_t s = ctx->stream;
+  EventTimer whole, pass[4];
+  const char* what_create = nullptr;
+  if ((e = whole.create(&what_create)) != hipSuccess) return hip_fail(ctx, e, what_create);
+  for (EventTimer& t : pass)
+    if ((e = t.create(&what_create)) != hipSuccess) return hip_fail(ctx, e, what_create);
+  // from here every path reaches the hipStreamSynchronize below: G's vectors outlive their uploads
+  e = upload_groups(G, d_group, d_off, d_list, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cap, hcap.data(), hcap.size() * sizeof(double), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = whole.start(s);
+  // NaN: what padding, the chains of no group and the quantiles of unused columns keep
+  rc = e != hipSuccess ? TCI_OK : tci::launch_chainrank_fill(d_z, nch, (void*)s);
+  if (rc == TCI_OK && e == hipSuccess && d_zs2) rc = tci::launch_chainrank_fill(d_zs2, ns2, (void*)s);
+  if (rc == TCI_OK && e == hipSuccess) rc = tci::launch_chainrank_fill(d_q, nqq * plane, (void*)s);
+  double* const zdst[2] = {out->z, out->z_folded};
+  double* const zdst2[2] = {out->s2_z, out->s2_z_folded};
+  for (int m = 0; m < 4 && rc == TCI_OK && e == hipSuccess; ++m) {
+    e = pass[m].start(s);
+    rc = tci::launch_chainrank(d_chain, d_s2, n_rows, n_chains, ld, d_npar, n_groups, G.off.data(), d_off, d_list, m,
+                               o.probs, o.nq, o.tail_lo, o.tail_hi, d_q, d_gk, d_z, d_zs2, (void*)s);
+    if (e == hipSuccess) e = pass[m].stop(s);
+    if (rc != TCI_OK || e != hipSuccess) break;
+    const int k = m == 0 ? 0 : m - 1;  // the pass's slot of d_ed / d_ew
+    rc = m == 1 ? tci::launch_chainrhat(d_z, d_zs2, n_rows, n_chains, ld, d_npar, d_group, n_groups, d_off, d_list,
+                                        d_scratch, d_o + (size_t)m * 4 * plane, (void*)s)
+                : tci::launch_chainess(d_z, d_zs2, n_rows, n_chains, ld, d_npar, d_group, n_groups, d_off, d_list,
+                                       o.max_lag, d_cap, d_scratch, d_o + (size_t)m * 4 * plane,
+                                       d_ed + (size_t)k * 5 * plane, d_ew + (size_t)k * 2 * plane, (void*)s);
+    if (rc == TCI_OK && m < 2 && zdst[m]) e = hipMemcpyAsync(zdst[m], d_z, nch * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (rc == TCI_OK && e == hipSuccess && m < 2 && zdst2[m] && d_zs2)
+      e = hipMemcpyAsync(zdst2[m], d_zs2, ns2 * sizeof(double), hipMemcpyDeviceToHost, s);
+  }
+  hipError_t e1 = e;
+  if (e1 == hipSuccess) e1 = whole.stop(s);
+  const bool ok = rc == TCI_OK && e1 == hipSuccess;
+  if (ok) e1 = hipMemcpyAsync(ho.data(), d_o, ho.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (ok && e1 == hipSuccess) e1 = hipMemcpyAsync(he.data(), d_ed, he.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (ok && e1 == hipSuccess) e1 = hipMemcpyAsync(hw.data(), d_ew, hw.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  if (ok && e1 == hipSuccess) e1 = hipMemcpyAsync(hq.data(), d_q, hq.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  float ms = 0.f, rank_ms = 0.f;
+  if (ok && e1 == hipSuccess && e2 == hipSuccess) e1 = whole.elapsed_ms(&ms);
+  for (EventTimer& t : pass) {
+    float pm = 0.f;
+    if (ok && e1 == hipSuccess && e2 == hipSuccess) e1 = t.elapsed_ms(&pm);
+    rank_ms += pm;
+  }
+  if (rc == TCI_EHIP) return hip_fail(ctx, hipGetLastError(), "chain rank kernel launch");
+  if (rc != TCI_OK) return fail(ctx, rc, std::string(who) + ": rows x chains x ld too large for one launch");
+  if (e2 != hipSuccess) return hip_fail(ctx, e2, "chain rank kernels");
+  if (e1 != hipSuccess) return hip_fail(ctx, e1, "chain rank copy");
+  if (!d_s2) {  // no s2 chain: its z twins are NaN
+    for (int m = 0; m < 2; ++m)
+      if (zdst2[m]) std::fill(zdst2[m], zdst2[m] + ns2, std::nan(""));
+  }
+  // rhat_split is plane 1 of a pass's launch_chainrhat out; ess_split, tau_split planes 1 and 3 of launch_chainess's
+  // doubles and window_split plane 1 of its windows
+  const auto rh = [&](int m, size_t g) { return ho.data() + (((size_t)m * 4 + 1) * ng + g) * ldc; };
+  const auto ed = [&](int k, int t, size_t g) { return he.data() + (((size_t)k * 5 + (size_t)t) * ng + g) * ldc; };
+  const auto ew = [&](int k, size_t g) { return hw.data() + (((size_t)k * 2 + 1) * ng + g) * ldc; };
+  const auto put = [&](double* dst, double* dst2, size_t g, const double* src) {
+    if (dst) std::memcpy(dst + g * L, src, L * sizeof(double));
+    if (dst2) dst2[g] = src[L];
+  };
+  const auto putw = [&](int32_t* dst, int32_t* dst2, size_t g, const int32_t* src) {
+    if (dst) std::memcpy(dst + g * L, src, L * sizeof(int32_t));
+    if (dst2) dst2[g] = src[L];
+  };
+  std::vector<double> both(ldc);
+  for (size_t g = 0; g < ng; ++g) {
+    for (size_t q = 0; q < nqq; ++q) {
+      const double* src = hq.data() + (g * nqq + q) * ldc;
+      if (q < (size_t)o.nq) {
+        if (out->q) std::memcpy(out->q + (g * (size_t)o.nq + q) * L, src, L * sizeof(double));
+        if (out->s2_q) out->s2_q[g * (size_t)o.nq + q] = src[L];
+      } else if (q > (size_t)o.nq) {
+        const size_t t = q - (size_t)o.nq - 1;
+        if (out->q_tail) std::memcpy(out->q_tail + (g * 2 + t) * L, src, L * sizeof(double));
+        if (out->s2_q_tail) out->s2_q_tail[g * 2 + t] = src[L];
+      }
+    }
+    put(out->rhat_bulk, out->s2_rhat_bulk, g, rh(0, g));
+    put(out->rhat_folded, out->s2_rhat_folded, g, rh(1, g));
+    for (size_t j = 0; j < ldc; ++j) {  // the larger, NaN if either is NaN
+      const double a = rh(0, g)[j], b = rh(1, g)[j];
+      both[j] = a != a || b != b ? std::nan("") : (a > b ? a : b);
+    }
+    put(out->rhat_rank, out->s2_rhat_rank, g, both.data());
+    put(out->ess_bulk, out->s2_ess_bulk, g, ed(0, 1, g));
+    put(out->tau_bulk, out->s2_tau_bulk, g, ed(0, 3, g));
+    put(out->ess_tail_lo, out->s2_ess_tail_lo, g, ed(1, 1, g));
+    put(out->ess_tail_hi, out->s2_ess_tail_hi, g, ed(2, 1, g));
+    for (size_t j = 0; j < ldc; ++j) {  // the smaller, NaN if either is NaN
+      const double a = ed(1, 1, g)[j], b = ed(2, 1, g)[j];
+      both[j] = a != a || b != b ? std::nan("") : (a < b ? a : b);
+    }
+    put(out->ess_tail, out->s2_ess_tail, g, both.data());
+    putw(out->window_bulk, out->s2_window_bulk, g, ew(0, g));
+    putw(out->window_tail_lo, out->s2_window_tail_lo, g, ew(1, g));
+    putw(out->window_tail_hi, out->s2_window_tail_hi, g, ew(2, g));
+  }
+  out->n_rows = n_rows;
+  out->kernel_ms = ms;
+  out->rank_ms = rank_ms;
   return TCI_OK;
 }
 
@@ -621,6 +809,40 @@ int tci_chainess(tci_ctx* ctx, const tci_chainess_options* opt, const double* ch
   if ((rc = d.upload(ctx, "tci_chainess", chain, s2chain, n_rows, n_chains, ld, npar)) != TCI_OK) return rc;
   return chainrhat_device(ctx, "tci_chainess", d.d_chain, d.d_s2, n_rows, n_chains, ld, d.d_npar, G, n_groups, nullptr,
                           opt ? opt->max_lag : 0, out);
+}
+
+int tci_chainrank_defaults(tci_chainrank_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  o->nq = 3;
+  o->probs[0] = 0.025;
+  o->probs[1] = 0.5;
+  o->probs[2] = 0.975;
+  o->tail_lo = 0.05;
+  o->tail_hi = 0.95;
+  return TCI_OK;
+}
+
+int64_t tci_chainrank_lds_cap(void) { return tci::kRankLdsCap; }
+
+int tci_chainrank(tci_ctx* ctx, const tci_chainrank_options* opt, const double* chain, const double* s2chain,
+                  int64_t n_rows, int64_t n_chains, int64_t ld, const int32_t* npar, const int32_t* group,
+                  int64_t n_groups, tci_chainrank_outputs* out) {
+  if (!ctx) return TCI_EINVAL;
+  if (!chain || !out) return fail(ctx, TCI_EINVAL, "tci_chainrank: null argument");
+  if (n_rows < 1) return fail(ctx, TCI_EINVAL, "tci_chainrank: n_rows must be >= 1");
+  tci_chainrank_options o;
+  int rc = chainrank_opts(ctx, "tci_chainrank", opt, &o);
+  if (rc != TCI_OK) return rc;
+  if (n_chains < 1 || ld < 1) return fail(ctx, TCI_EINVAL, "tci_chainrank: n_chains and ld must be >= 1");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_chainrank: n_groups must be in [1, n_chains]");
+  if ((rc = check_npar(ctx, "tci_chainrank", npar, n_chains, ld)) != TCI_OK) return rc;
+  RhatGroups G;
+  if ((rc = chainrhat_groups(ctx, "tci_chainrank", nullptr, n_rows, n_chains, ld, npar, group, n_groups, &G)) != TCI_OK) return rc;
+  DeviceChain d;
+  if ((rc = d.upload(ctx, "tci_chainrank", chain, s2chain, n_rows, n_chains, ld, npar)) != TCI_OK) return rc;
+  return chainrank_device(ctx, "tci_chainrank", d.d_chain, d.d_s2, n_rows, n_chains, ld, d.d_npar, G, n_groups, o, out);
 }
 
 int tci_chainlp_defaults(tci_chainlp_options* o) {

@@ -24,8 +24,8 @@ std::string at(int64_t k, int64_t j) { return "cell " + std::to_string(k) + ", i
 int demc_check(tci_ctx* ctx, const tci_demc_options& o, const double* pop0, int64_t ld, const int32_t* cell_id,
                int64_t n_sel, int64_t n_pop, const double* lower, const double* upper, const double* mu,
                const double* sig, const double* jitter, const double* s2, int64_t log_rows, bool reduce,
-               const tci_chainrhat_options* ropt, const tci_chainess_options* eopt, bool ess, int64_t* keep_k0,
-               int64_t* keep_rows) {
+               const tci_chainrhat_options* ropt, const tci_chainess_options* eopt, bool ess,
+               const tci_chainrank_options* kopt, tci_chainrank_options* k_opt, int64_t* keep_k0, int64_t* keep_rows) {
   const std::string who = std::string(kWho) + ": ";
   if (n_sel < 1) return fail(ctx, TCI_EINVAL, who + "n_sel must be >= 1");
   if (o.flags != 0) return fail(ctx, TCI_EINVAL, who + "flags is reserved and must be 0");
@@ -85,6 +85,10 @@ int demc_check(tci_ctx* ctx, const tci_demc_options& o, const double* pop0, int6
     if (ropt && ropt->flags != 0) return fail(ctx, TCI_EINVAL, who + "flags is reserved and must be 0");
     if (ess && eopt && eopt->max_lag < 0) return fail(ctx, TCI_EINVAL, who + "max_lag must be >= 0");
     if (ess && eopt && eopt->flags != 0) return fail(ctx, TCI_EINVAL, who + "flags is reserved and must be 0");
+    if (k_opt) {
+      const int rc = chainrank_opts(ctx, kWho, kopt, k_opt);
+      if (rc != TCI_OK) return rc;
+    }
   }
   return TCI_OK;
 }
@@ -109,16 +113,27 @@ int tci_demc_run(tci_ctx* ctx, const tci_demc_options* opt, const double* pop0, 
                  const double* prior_sig, const double* jitter, const double* sigma2_0, tci_demc_outputs* out,
                  const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
                  tci_chainess_outputs* eout) {
+  return tci_demc_run_rank(ctx, opt, pop0, ld, cell_id, n_sel, n_pop, lower, upper, prior_mu, prior_sig, jitter, sigma2_0,
+                           out, ropt, rout, eopt, eout, nullptr, nullptr);
+}
+
+int tci_demc_run_rank(tci_ctx* ctx, const tci_demc_options* opt, const double* pop0, int64_t ld, const int32_t* cell_id,
+                      int64_t n_sel, int64_t n_pop, const double* lower, const double* upper, const double* prior_mu,
+                      const double* prior_sig, const double* jitter, const double* sigma2_0, tci_demc_outputs* out,
+                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                      tci_chainess_outputs* eout, const tci_chainrank_options* kopt, tci_chainrank_outputs* kout) {
   if (!ctx) return TCI_EINVAL;
   if (!pop0 || !cell_id || !lower || !upper || !prior_mu || !prior_sig || !jitter || !sigma2_0 || !out)
     return fail(ctx, TCI_EINVAL, std::string(kWho) + ": null argument");
   tci_demc_options o;
   tci_demc_defaults(&o);
   if (opt) o = *opt;
-  const bool reduce = rout || eout;
+  const bool reduce = rout || eout || kout;
+  tci_chainrank_options k_opt{};
   int64_t keep_k0 = 0, keep_rows = 0;
   int rc = demc_check(ctx, o, pop0, ld, cell_id, n_sel, n_pop, lower, upper, prior_mu, prior_sig, jitter, sigma2_0,
-                      out->log_rows, reduce, ropt, eopt, eout != nullptr, &keep_k0, &keep_rows);
+                      out->log_rows, reduce, ropt, eopt, eout != nullptr, kopt, kout ? &k_opt : nullptr, &keep_k0,
+                      &keep_rows);
   if (rc != TCI_OK) return rc;
 
   const size_t n = (size_t)n_sel, L = (size_t)ld, B = n * (size_t)n_pop;
@@ -269,9 +284,14 @@ int tci_demc_run(tci_ctx* ctx, const tci_demc_options* opt, const double* pop0, 
   }
   out->n_keep = (int64_t)n_keep;
   out->kernel_ms = ms;
-  if (reduce)
-    return chainrhat_device(ctx, kWho, d_chain + (size_t)keep_k0 * B * L, d_s2c + (size_t)keep_k0 * B, keep_rows,
-                            (int64_t)B, ld, d_npar, groups, n_sel, rout, eout && eopt ? eopt->max_lag : 0, eout);
+  if (rout || eout) {
+    rc = chainrhat_device(ctx, kWho, d_chain + (size_t)keep_k0 * B * L, d_s2c + (size_t)keep_k0 * B, keep_rows, (int64_t)B,
+                          ld, d_npar, groups, n_sel, rout, eout && eopt ? eopt->max_lag : 0, eout);
+    if (rc != TCI_OK) return rc;
+  }
+  if (kout)
+    return chainrank_device(ctx, kWho, d_chain + (size_t)keep_k0 * B * L, d_s2c + (size_t)keep_k0 * B, keep_rows, (int64_t)B,
+                            ld, d_npar, groups, n_sel, k_opt, kout);
   return TCI_OK;
 }
 

@@ -26,6 +26,8 @@ struct RhatAsk {
   const char* who = "tci_dram_run_rhat";
   const tci_chainess_options* eopt = nullptr;  // tci_dram_run_ess: the effective sample size too (rout may be null)
   tci_chainess_outputs* eout = nullptr;
+  const tci_chainrank_options* kopt = nullptr;  // tci_dram_run_rank: the rank diagnostics too (rout, eout may be null)
+  tci_chainrank_outputs* kout = nullptr;
 };
 
 // One DRAM step: propose -> ssfun -> accept/propose stage 2 -> ssfun -> accept, sigma2, log the row
@@ -98,6 +100,7 @@ struct DramRun {
   std::vector<int32_t> pair_a, pair_b, pair_r;
   int64_t swap_every = 0, p_max_all = 0;
   RhatGroups r_groups;
+  tci_chainrank_options k_opt{};
   int64_t ai = 0, DW = 0, win = 0, chunk = 0, n_keep = 0;
   // ---- alloc, upload: the device side
   DevAllocs A;
@@ -177,6 +180,7 @@ struct DramRun {
         return fail(ctx, TCI_EINVAL, std::string(rhat->who) + ": max_lag must be >= 0");
       if (rhat->eout && rhat->eopt && rhat->eopt->flags != 0)
         return fail(ctx, TCI_EINVAL, std::string(rhat->who) + ": flags is reserved and must be 0");
+      if (rhat->kout && (rc = chainrank_opts(ctx, rhat->who, rhat->kopt, &k_opt)) != TCI_OK) return rc;
     }
     if ((rc = check_rows(ctx, ld, cell_id, n_chains)) != TCI_OK) return rc;
     if (ld > TCI_MAX_POINTS + 7) return fail(ctx, TCI_ERANGE, "tci_dram_run: ld too large");
@@ -721,9 +725,13 @@ struct DramRun {
     if (lout && (rc = chainlp_device(ctx, "tci_dram_run_lp", chain, s2, keep_rows, n_chains, ld, st.cell, st.npar, st.pmu,
                                      st.psig, l_scratch, lout)) != TCI_OK)
       return rc;
-    if (rhat)
-      return chainrhat_device(ctx, rhat->who, chain, s2, keep_rows, n_chains, ld, st.npar, r_groups, rhat->n_groups,
-                              rhat->rout, rhat->eout && rhat->eopt ? rhat->eopt->max_lag : 0, rhat->eout);
+    if (rhat && (rhat->rout || rhat->eout) &&
+        (rc = chainrhat_device(ctx, rhat->who, chain, s2, keep_rows, n_chains, ld, st.npar, r_groups, rhat->n_groups,
+                               rhat->rout, rhat->eout && rhat->eopt ? rhat->eopt->max_lag : 0, rhat->eout)) != TCI_OK)
+      return rc;
+    if (rhat && rhat->kout)
+      return chainrank_device(ctx, rhat->who, chain, s2, keep_rows, n_chains, ld, st.npar, r_groups, rhat->n_groups, k_opt,
+                              rhat->kout);
     return TCI_OK;
   }
 
@@ -838,6 +846,23 @@ int tci_dram_run_ess(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains
   if (n_groups < 1 || n_groups > n_chains)
     return fail(ctx, TCI_EINVAL, "tci_dram_run_ess: n_groups must be in [1, n_chains]");
   const RhatAsk ask{ropt, group, n_groups, rout, "tci_dram_run_ess", eopt, eout};
+  DramRun r{TCI_RUN_ARGS};
+  if (red) r.red = *red;
+  r.rhat = &ask;
+  return r.go();
+}
+
+int tci_dram_run_rank(tci_ctx* ctx, const tci_dram_options* opt, int64_t n_chains, const int32_t* cell_id,
+                      const double* theta0, const double* lower, const double* upper, const double* prior_mu,
+                      const double* prior_sig, const double* qcov_diag, const double* sigma2_0, int64_t ld,
+                      tci_dram_outputs* out, const tci_dram_reductions* red, const int32_t* group, int64_t n_groups,
+                      const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
+                      tci_chainess_outputs* eout, const tci_chainrank_options* kopt, tci_chainrank_outputs* kout) {
+  if (!ctx) return TCI_EINVAL;
+  if (!kout) return fail(ctx, TCI_EINVAL, "tci_dram_run_rank: null rank diagnostics outputs");
+  if (n_groups < 1 || n_groups > n_chains)
+    return fail(ctx, TCI_EINVAL, "tci_dram_run_rank: n_groups must be in [1, n_chains]");
+  const RhatAsk ask{ropt, group, n_groups, rout, "tci_dram_run_rank", eopt, eout, kopt, kout};
   DramRun r{TCI_RUN_ARGS};
   if (red) r.red = *red;
   r.rhat = &ask;

@@ -205,5 +205,11 @@ int chainrhat_groups(tci_ctx* ctx, const char* who, const tci_chainrhat_options*
 int chainrhat_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
                      int64_t n_chains, int64_t ld, const int32_t* d_npar, const RhatGroups& G, int64_t n_groups,
                      tci_chainrhat_outputs* out, int64_t max_lag = 0, tci_chainess_outputs* eout = nullptr);
+// tci_chainrank's option checks (*o: the options to use, the defaults for null) and its four passes over the groups
+// chainrhat_groups made.
+int chainrank_opts(tci_ctx* ctx, const char* who, const tci_chainrank_options* kopt, tci_chainrank_options* o);
+int chainrank_device(tci_ctx* ctx, const char* who, const double* d_chain, const double* d_s2, int64_t n_rows,
+                     int64_t n_chains, int64_t ld, const int32_t* d_npar, const RhatGroups& G, int64_t n_groups,
+                     const tci_chainrank_options& o, tci_chainrank_outputs* out);
 
 }  // namespace tci_api

@@ -186,6 +186,32 @@ int launch_chainess(const double* chain, const double* s2, int64_t n_rows, int64
                     const int32_t* g_list, int64_t max_lag, const double* cap, void* scratch, double* rhat_out,
                     double* out_d, int32_t* out_w, void* stream);
 
+// The pooled sort of every (group, column) of a device chain and the chains that follow from it (tci_chainrank.hip;
+// include/tci.h has the definition); the chain, npar and the groups (g_off, g_list device; g_off_host the same
+// offsets on the host) as for launch_chainrhat. One launch per mode, in this order on one stream:
+//   0  the pooled quantiles into qbuf (device): [n_groups][nq + 3][ld + 1] = the quantiles at probs (nq host values),
+//      then at 0.5, tail_lo and tail_hi; and the rank scores z of x into zc / zs2;
+//   1  the rank scores of |x - med| into zc / zs2, med read from qbuf;
+//   2  the indicator x <= q(tail_lo) into zc / zs2;  3  the same for tail_hi (both read qbuf, neither sorts).
+// zc (device): [n_rows][n_chains][ld]; zs2 (device): [n_rows][n_chains], required with s2. Only the entries of a
+// group's real columns are written: the caller fills both with NaN once, which is what padding and the chains of no
+// group keep (launch_chainrank_fill). A column with a non-finite entry gets NaN in qbuf and in every entry of zc / zs2.
+// A group of N = M n_rows <= kRankLdsCap keys is sorted in LDS; a larger one in its slab of gkeys (device):
+// chainrank_scratch_keys() keys of 8 bytes (0: no group is that large and gkeys may be null). Asynchronous on
+// `stream`. TCI_EINVAL on a bad size, TCI_ERANGE for a group of 2^31 values or more or a grid above 2^31 - 1
+// workgroups, TCI_ENOMEM above 2^46 bytes of keys, TCI_EHIP on a HIP error.
+// kRankLdsCap: 8,192 keys = 64 KiB of LDS, two workgroups per CU's 160 KiB; it holds the shapes the samplers make
+// (4 replicates x 1,000 rows; 64 members x 101 rows).
+constexpr int kRankLdsCap = 8192;
+int launch_chainrank(const double* chain, const double* s2, int64_t n_rows, int64_t n_chains, int64_t ld,
+                     const int32_t* npar, int64_t n_groups, const int32_t* g_off_host, const int32_t* g_off,
+                     const int32_t* g_list, int mode, const double* probs, int32_t nq, double tail_lo, double tail_hi,
+                     double* qbuf, void* gkeys, double* zc, double* zs2, void* stream);
+// n entries of p (device) set to the quiet NaN the reductions write. Asynchronous on `stream`.
+int launch_chainrank_fill(double* p, size_t n, void* stream);
+int chainrank_scratch_keys(int64_t n_rows, int64_t ld, int64_t n_groups, const int32_t* g_off, int64_t* stride,
+                           size_t* keys);
+
 // Log-posterior trace, best sample and DIC of every chain (tci_chainlp.hip) of a device chain [n_rows][n_chains][ld]
 // with its s2 [n_rows][n_chains]; the traces are laid out as s2 is. cell (device): [n_chains], valid ids of cells
 // with 7 + N <= ld (the host checks). n_rows * n_chains must stay below 2^31 (TCI_ERANGE), the likelihood launch's

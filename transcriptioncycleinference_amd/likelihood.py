@@ -281,6 +281,85 @@ class ChainEss:
                                          I(self.s2_window_split), 0, 0.0)
 
 
+@dataclasses.dataclass
+class ChainRank:
+    """Per-group rank diagnostics across replicate chains (``tci_chainrank_outputs``; Vehtari et al. 2021): the pooled
+    quantiles ``q`` ``[n_groups, nq, ld]`` and ``q_tail`` ``[n_groups, 2, ld]``, the rank-normalised split R-hat
+    (``rhat_bulk``, ``rhat_folded`` and their maximum ``rhat_rank``), bulk and tail ESS with their windows, ``[n_groups,
+    ld]``, each with an ``s2_`` twin without the last axis; padding is NaN / -1. ``z`` and ``z_folded`` (``[rows,
+    n_chains, ld]``, with ``s2_z`` / ``s2_z_folded`` ``[rows, n_chains]``) are the rank-score chains, None unless
+    asked for."""
+
+    probs: np.ndarray
+    tail: tuple
+    max_lag: int
+    arrays: dict
+    z: Optional[np.ndarray] = None
+    z_folded: Optional[np.ndarray] = None
+    s2_z: Optional[np.ndarray] = None
+    s2_z_folded: Optional[np.ndarray] = None
+    n_rows: int = 0
+    kernel_ms: float = 0.0
+    rank_ms: float = 0.0
+
+    def __getattr__(self, name):
+        arrays = self.__dict__.get("arrays")
+        if arrays is not None and name in arrays:
+            return arrays[name]
+        raise AttributeError(name)
+
+    @classmethod
+    def empty(cls, n_groups: int, ld: int, probs=(0.025, 0.5, 0.975), tail=(0.05, 0.95), max_lag: int = 0,
+              scores=None) -> "ChainRank":
+        """``scores``: None, or ``(rows, n_chains, with_s2)`` to hold the rank-score chains."""
+        pr = quant_probs(probs)
+        if len(tail) != 2 or not (0.0 < float(tail[0]) < float(tail[1]) < 1.0):
+            raise ValueError("tail must be (lo, hi) with 0 < lo < hi < 1")
+        if int(max_lag) != max_lag or int(max_lag) < 0:
+            raise ValueError("max_lag must be an integer >= 0")
+        g = int(n_groups)
+        a = {}
+        for f in _lib.CHAINRANK_DOUBLES:
+            mid = {"q": (pr.size,), "q_tail": (2,)}.get(f, ())
+            a[f] = np.full((g,) + mid + (ld,), np.nan)
+            a["s2_" + f] = np.full((g,) + mid, np.nan)
+        for f in _lib.CHAINRANK_WINDOWS:
+            a[f] = np.full((g, ld), -1, np.int32)
+            a["s2_" + f] = np.full((g,), -1, np.int32)
+        cr = cls(pr, (float(tail[0]), float(tail[1])), int(max_lag), a)
+        if scores is not None:
+            rows, n, with_s2 = scores
+            cr.z, cr.z_folded = np.full((rows, n, ld), np.nan), np.full((rows, n, ld), np.nan)
+            if with_s2:
+                cr.s2_z, cr.s2_z_folded = np.full((rows, n), np.nan), np.full((rows, n), np.nan)
+        return cr
+
+    def options(self) -> "_lib.tci_chainrank_options":
+        o = _lib.tci_chainrank_options()
+        o.nq = int(self.probs.size)
+        for k, p in enumerate(self.probs):
+            o.probs[k] = float(p)
+        o.tail_lo, o.tail_hi = self.tail
+        o.max_lag, o.flags = self.max_lag, 0
+        return o
+
+    def to_c(self) -> "_lib.tci_chainrank_outputs":
+        out = _lib.tci_chainrank_outputs()
+        for f in _lib.CHAINRANK_DOUBLES:
+            setattr(out, f, _lib.ptr(self.arrays[f], _lib._dp))
+            setattr(out, "s2_" + f, _lib.ptr(self.arrays["s2_" + f], _lib._dp))
+        for f in _lib.CHAINRANK_WINDOWS:
+            setattr(out, f, _lib.ptr(self.arrays[f], _lib._i32p))
+            setattr(out, "s2_" + f, _lib.ptr(self.arrays["s2_" + f], _lib._i32p))
+        for f in ("z", "z_folded", "s2_z", "s2_z_folded"):
+            setattr(out, f, _lib.ptr(getattr(self, f), _lib._dp))
+        return out
+
+    def taken(self, out) -> "ChainRank":
+        self.n_rows, self.kernel_ms, self.rank_ms = int(out.n_rows), float(out.kernel_ms), float(out.rank_ms)
+        return self
+
+
 FITCHECK_POINTWISE = ("lppd_i", "p_waic_i", "pit", "resid", "zbar", "z2")
 
 
@@ -485,7 +564,7 @@ class Demc:
     ``[n_keep, n_chains]``: the states after generations 0, thin, 2 thin, ..; ``pop`` ``[n_sel, n_pop, ld]``, ``s2`` and
     ``ss`` ``[n_sel, n_pop]``: the final population; per member ``accept_rate``, ``n_oob`` (int32) and ``n_evals``
     (int64) ``[n_sel, n_pop]``; the logs ``logr``, ``accepted`` and ``trial_oob`` (uint8) ``[log_rows, n_chains]``, row
-    ``g - 1`` for generation ``g``; ``rhat`` / ``ess``: the group reductions over the cells' members, or None."""
+    ``g - 1`` for generation ``g``; ``rhat`` / ``ess`` / ``rank``: the group reductions over the cells' members, or None."""
 
     chain: np.ndarray
     s2chain: np.ndarray
@@ -505,6 +584,7 @@ class Demc:
     kernel_ms: float = 0.0
     rhat: Optional[ChainRhat] = None
     ess: Optional[ChainEss] = None
+    rank: Optional["ChainRank"] = None
 
     @classmethod
     def empty(cls, n: int, n_pop: int, ld: int, n_gen: int, thin: int, log_rows: int) -> "Demc":
@@ -919,6 +999,35 @@ class Likelihood:
         ce.n_rows, ce.kernel_ms = int(out.n_rows), float(out.kernel_ms)
         return ce
 
+    def chainrank(self, chain: np.ndarray, s2chain: Optional[np.ndarray] = None, npar=None, group=None,
+                  probs=(0.025, 0.5, 0.975), tail=(0.05, 0.95), max_lag: int = 0, scores: bool = False) -> ChainRank:
+        """Rank-normalised split R-hat (bulk and folded), bulk and tail effective sample size and the pooled quantiles
+        of replicate chains held on the host (Vehtari, Gelman, Simpson, Carpenter and Buerkner 2021), from one pooled
+        sort of every group's column on the device (``tci_chainrank``; the definition is in ``include/tci.h``).
+        Arguments as in :meth:`chainess`; ``probs``: 1 to 16 probabilities of the pooled quantiles; ``tail``: the two
+        probabilities of the tail ESS; ``scores``: also return the rank-score chains ``z`` and ``z_folded``. Returns a
+        :class:`ChainRank`; padding and columns with a non-finite entry are NaN / -1."""
+        chain = np.asarray(chain, np.float64)
+        if chain.ndim == 2:
+            chain = chain[:, None, :]
+        if chain.ndim != 3:
+            raise ValueError("chain must be [rows, n_chains, ld]")
+        chain = np.ascontiguousarray(chain)
+        rows, n, ld = chain.shape
+        s2 = None
+        if s2chain is not None:
+            s2 = np.ascontiguousarray(np.asarray(s2chain, np.float64).reshape(rows, n))
+        npr = None
+        if npar is not None:
+            npr = np.ascontiguousarray(np.broadcast_to(np.asarray(npar, np.int32), (n,)))
+        grp, ng = rhat_groups(group, n, npr)
+        ck = ChainRank.empty(ng, ld, probs, tail, max_lag, (rows, n, s2 is not None) if scores else None)
+        opt, out = ck.options(), ck.to_c()
+        self._check(self._lib.tci_chainrank(self._h, C.byref(opt), _lib.ptr(chain, _lib._dp), _lib.ptr(s2, _lib._dp),
+                                            rows, n, ld, _lib.ptr(npr, _lib._i32p), _lib.ptr(grp, _lib._i32p), ng,
+                                            C.byref(out)))
+        return ck.taken(out)
+
     def chainlp(self, chain: np.ndarray, s2chain: np.ndarray, cell_id: Sequence[int], prior_mu: np.ndarray,
                 prior_sig: np.ndarray) -> ChainLp:
         """The sum-of-squares trace of chains held on the host (mcmcstat's ``sschain``, ``mcmcrun``'s fourth output),
@@ -987,14 +1096,16 @@ class Likelihood:
              prior_mu: np.ndarray, prior_sig: np.ndarray, jitter: np.ndarray, sigma2_0=1.0, n_gen: int = 1000,
              thin: int = 1, jump_every: int = 10, CR: float = 0.2, gamma0: float = 0.0, updatesigma: bool = True,
              seed: int = 0, keys=None, stats_from: int = 0, rhat: bool = False, ess: bool = False, max_lag: int = 0,
-             log_rows: int = 0, flags: int = 0) -> Demc:
+             log_rows: int = 0, flags: int = 0, rank=False) -> Demc:
         """Differential-evolution Markov chain (ter Braak 2006) over a population per cell, on the device
         (``tci_demc_run``; the definition is in ``include/tci.h``). ``pop0`` ``[n_sel, n_pop, ld]``: the initial members
         of every selected cell, each inside ``[lower, upper]``; ``cell_id`` one cell per population; ``lower``,
         ``upper``, ``prior_mu``, ``prior_sig`` and ``jitter`` ``[n_sel, ld]``; ``sigma2_0`` ``[n_sel]`` or a scalar;
         ``keys`` ``[n_sel]``: the RNG stream key of every cell (default: its position). ``rhat`` / ``ess``: also the
         group reductions of the kept rows of generations ``>= stats_from`` across every cell's members, taken from the
-        device chain. ``log_rows``: generations the decision logs keep. Returns a :class:`Demc`."""
+        device chain; ``rank``: ``True`` or a dict of ``probs`` / ``tail``: the rank diagnostics of :meth:`chainrank`
+        over the same rows and groups too (``tci_demc_run_rank``). ``log_rows``: generations the decision logs keep.
+        Returns a :class:`Demc`."""
         pop0 = np.ascontiguousarray(pop0, np.float64)
         if pop0.ndim != 3:
             raise ValueError("pop0 must be [n_sel, n_pop, ld]")
@@ -1021,9 +1132,17 @@ class Likelihood:
         eopt, eout = (ce.options(), ce.to_c()) if ce is not None else (None, None)
         R = lambda x: None if x is None else C.byref(x)  # noqa: E731
         P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
-        self._check(self._lib.tci_demc_run(self._h, C.byref(opt), P(pop0), ld, _lib.ptr(cid, _lib._i32p), n, n_pop, P(lo),
-                                           P(up), P(mu), P(sig), P(jit), P(s2v), C.byref(out), R(ropt), R(rout), R(eopt),
-                                           R(eout)))
+        ck = None
+        if rank is not None and rank is not False:
+            ck = ChainRank.empty(n, ld, max_lag=max_lag, **({} if rank is True else dict(rank)))
+        args = (self._h, C.byref(opt), P(pop0), ld, _lib.ptr(cid, _lib._i32p), n, n_pop, P(lo), P(up), P(mu), P(sig), P(jit),
+                P(s2v), C.byref(out), R(ropt), R(rout), R(eopt), R(eout))
+        if ck is not None:
+            kopt, kout = ck.options(), ck.to_c()
+            self._check(self._lib.tci_demc_run_rank(*args, C.byref(kopt), C.byref(kout)))
+            dm.rank = ck.taken(kout)
+        else:
+            self._check(self._lib.tci_demc_run(*args))
         dm.kernel_ms = float(out.kernel_ms)
         if cr is not None:
             cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)

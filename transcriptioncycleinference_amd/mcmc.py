@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .data import Cells, draw_x0
-from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainLp, ChainQuant, ChainRhat, ChainStats,
+from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainLp, ChainQuant, ChainRank, ChainRhat, ChainStats,
                          Demc, FitCheck, ModeSearch, rhat_groups)
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
@@ -60,6 +60,14 @@ RHAT_FIELDS = ("rhat", "rhat_split", "pooled_mean", "pooled_std", "mean_rep", "a
 # [P + 1] int32; ess_min: the smallest classic or split ess of the cell; max_lag: the cap the fit passed (0 = none)
 ESS_FIELDS = ("ess", "ess_split", "tau", "tau_split", "mcse", "window", "window_split", "ess_min", "max_lag", "n_rows",
               "n_chains", "cell_index")
+# MCMCrank (fit(..., replicates=M, rank=True)): the rank diagnostics of a fitted cell (include/tci.h, tci_chainrank),
+# P + 1 = 7 + N + 1 columns wide (theta order, s2 last): q [nq, P + 1] at probs [nq], q_tail [2, P + 1] at tail [2],
+# the R-hat, ESS and tau vectors [P + 1] doubles, the windows [P + 1] int32; rhat_rank_max, ess_bulk_min, ess_tail_min:
+# the cell's worst values, NaN left out; max_lag: the cap the fit passed (0 = none)
+RANK_VECTORS = ("rhat_bulk", "rhat_folded", "rhat_rank", "ess_bulk", "tau_bulk", "ess_tail_lo", "ess_tail_hi", "ess_tail",
+                "window_bulk", "window_tail_lo", "window_tail_hi")
+RANK_FIELDS = ("q", "q_tail", "probs", "tail") + RANK_VECTORS + ("rhat_rank_max", "ess_bulk_min", "ess_tail_min",
+                                                                 "max_lag", "n_rows", "n_chains", "cell_index")
 # MCMCcheck (fitcheck(lk, fit_result)): posterior predictive fit checks per fitted cell (include/tci.h): the pointwise
 # vectors [2, N] (row 0 = MS2, row 1 = PP7; NaN where a point is not scored), the per-cell scalars, coverage [n_levels]
 # at levels, dw [2] per dye
@@ -155,6 +163,7 @@ class DramResult:
     temper: Optional["TemperResult"] = None       # dram_run(beta=, ladder=): the ladders and their swap records
     lp: Optional[ChainLp] = None                  # dram_run(logpost=True): log-posterior trace, best sample, DIC
     ess: Optional[ChainEss] = None                # dram_run(group=ids, ess=True): effective sample size of every group
+    rank: Optional[ChainRank] = None              # dram_run(group=ids, rank=True): rank diagnostics of every group
     rhat: Optional[ChainRhat] = None              # dram_run(group=ids): R-hat / pooled moments of every group of chains
     dens: Optional[ChainDens] = None              # dram_run(dens=True): densities / histograms of the kept rows
     quant: Optional[ChainQuant] = None            # dram_run(quant=probs): quantiles of the kept rows
@@ -206,7 +215,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
              opts: DramOptions, want_qcov: bool = False, chain_keys=None, stats: bool = False,
              max_lag: int = 0, want_chain: bool = True, cov: bool = False,
              cov_scratch_bytes: int = 0, quant=None, dens=None, group=None, ess: bool = False,
-             logpost: bool = False, beta=None, ladder=None, swap_every: int = 1) -> DramResult:
+             logpost: bool = False, beta=None, ladder=None, swap_every: int = 1, rank=False) -> DramResult:
     """Run one chain per row on the device (``tci_dram_run``). Arrays are (n_chains, ld).
     ``want_qcov``: also return the final proposal factor R (n_chains, ld, ld). ``chain_keys``:
     RNG stream key per chain (default: the row index). ``stats``: also the chain diagnostics
@@ -237,8 +246,17 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     of a ladder, in ascending row order, are its rungs, cold first, and exchange states after every ``swap_every``-th
     window of ``adaptint`` rows (0 = never). ``sigma2_0`` is physical; every s2 output of a rung with ``beta < 1`` is
     ``sigma2 / beta``. The swap records come back as ``DramResult.temper``. Works with ``stats``, ``cov``, ``quant``,
-    ``dens`` and ``group``; ``ess`` and ``logpost`` have no tempered entry point (ValueError)."""
+    ``dens`` and ``group``; ``ess`` and ``logpost`` have no tempered entry point (ValueError).
+
+    ``rank`` (needs ``group``): ``True`` or a dict of ``probs`` / ``tail``: also the rank-normalised split R-hat, bulk
+    and tail ESS and pooled quantiles of every group over those rows (``DramResult.rank``, as ``Likelihood.chainrank``
+    gives, ``max_lag`` as its cap on the lags), through ``tci_dram_run_rank``; not with ``logpost`` or a tempered run."""
     tempered = beta is not None or ladder is not None
+    want_rank = rank is not None and rank is not False
+    if want_rank and group is None:
+        raise ValueError("rank needs group: the rank diagnostics are statistics of groups of chains")
+    if want_rank and (tempered or logpost):
+        raise ValueError("rank has no entry point with logpost or a tempered run")
     if tempered and (ess or logpost):
         raise ValueError("a tempered run (beta= / ladder=) takes stats, cov, quant, dens and group, not ess or logpost")
     if tempered and (isinstance(swap_every, bool) or int(swap_every) != swap_every or int(swap_every) < 0):
@@ -269,13 +287,15 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
     args = (lk._h, C.byref(o), n, _lib.ptr(cid, _lib._i32p), P(theta0), P(lower), P(upper), P(prior_mu), P(prior_sig),
             P(qcov_diag), P(s20), ld, C.byref(out))
-    cs = cc = cq = cd = cr = ce = clp = None
+    cs = cc = cq = cd = cr = ce = clp = ck = None
     sopt = sout = None
     if group is not None:
         grp, ng = rhat_groups(group, n)
         cr = ChainRhat.empty(ng, ld)
         if ess:
             ce = ChainEss.empty(ng, ld, max_lag)
+        if want_rank:
+            ck = ChainRank.empty(ng, ld, max_lag=max_lag, **({} if rank is True else dict(rank)))
     if quant is not None:
         cq = ChainQuant.empty(n, ld, quant)
     if dens is not None and dens is not False:
@@ -344,7 +364,17 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
                 ce.n_rows, ce.kernel_ms = int(eout.n_rows), float(eout.kernel_ms)
         elif cr is not None:
             ropt, rout = cr.options(), cr.to_c()
-            if ce is not None:
+            if ck is not None:
+                eopt, eout = (ce.options(), ce.to_c()) if ce is not None else (None, None)
+                kopt, kout = ck.options(), ck.to_c()
+                lk._check(lk._lib.tci_dram_run_rank(*args, C.byref(red), _lib.ptr(grp, _lib._i32p), ng, C.byref(ropt),
+                                                    C.byref(rout), None if eopt is None else C.byref(eopt),
+                                                    None if eout is None else C.byref(eout), C.byref(kopt),
+                                                    C.byref(kout)))
+                ck.taken(kout)
+                if ce is not None:
+                    ce.n_rows, ce.kernel_ms = int(eout.n_rows), float(eout.kernel_ms)
+            elif ce is not None:
                 eopt, eout = ce.options(), ce.to_c()
                 lk._check(lk._lib.tci_dram_run_ess(*args, C.byref(red), _lib.ptr(grp, _lib._i32p), ng, C.byref(ropt),
                                                    C.byref(rout), C.byref(eopt), C.byref(eout)))
@@ -376,7 +406,7 @@ def dram_run(lk, cell_id, theta0, lower, upper, prior_mu, prior_sig, qcov_diag, 
     return DramResult(mean, std, fin, smean, sstd, acc, nev, chain, s2c, float(out.elapsed_ms), qcov_R=qR,
                       kernel_ms=np.array(out.kernel_ms[:], np.float64),
                       kernel_launches=np.array(out.kernel_launches[:], np.int64), lp=clp, ess=ce, rhat=cr, dens=cd, quant=cq, stats=cs,
-                      cov=cc, temper=tr)
+                      cov=cc, temper=tr, rank=ck)
 
 
 # ---------------------------------------------------------------------------
@@ -441,6 +471,7 @@ class FitResult:
     MCMCstack: Optional[List[Dict]] = None     # fit(..., stack=nsample): STACK_FIELDS per fitted cell
     MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
     MCMCess: Optional[List[Dict]] = None       # fit(..., replicates=M, ess=True): ESS_FIELDS per fitted cell
+    MCMCrank: Optional[List[Dict]] = None      # fit(..., replicates=M, rank=True): RANK_FIELDS per fitted cell
     MCMCrhat: Optional[List[Dict]] = None      # fit(..., replicates=M): RHAT_FIELDS per fitted cell
     MCMCdens: Optional[List[Dict]] = None      # fit(..., density=True): DENS_FIELDS per fitted cell
     MCMCquant: Optional[List[Dict]] = None     # fit(..., quantiles=probs): QUANT_FIELDS per fitted cell
@@ -558,7 +589,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
         rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False,
         stack: Optional[int] = None, temper=None, swap_every: int = 1, presearch: Optional[Mapping] = None,
-        demc: Optional[Mapping] = None) -> FitResult:
+        demc: Optional[Mapping] = None, rank=False) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -612,6 +643,12 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     lags summed and the pooled mean's Monte-Carlo standard error, over the same rows and reduced on the device
     (:func:`ess_entry`); ``max_lag`` caps its lags as it caps the diagnostics'. Nothing else in the result changes.
 
+    ``rank`` (needs ``MCMCrhat`` as ``ess`` does): ``True`` or a dict of ``probs`` / ``tail``: also ``MCMCrank``, one
+    dict of ``RANK_FIELDS`` per fitted cell: the rank-normalised split R-hat (bulk, folded and their maximum), bulk and
+    tail ESS and the pooled quantiles of the cell's replicates (``Likelihood.chainrank``; :func:`rank_entry`), from the
+    device chain through ``tci_dram_run_rank``; with ``logpost`` or ``temper`` from the kept rows through
+    ``tci_chainrank``, the same bits. With ``demc`` the same values join every ``MCMCdemc`` entry.
+
     ``logpost``: also ``MCMClp``, one dict of ``LP_FIELDS`` per fitted cell: the sum-of-squares trace (mcmcstat's
     ``sschain``) and the log-posterior trace of the rows ``MCMCchain`` keeps (needs ``thin >= 1``), the best sample (a
     posterior-mode estimate) and DIC, all on the device (:func:`lp_entry`). With ``replicates=M`` the entry holds every
@@ -661,10 +698,14 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         if M != 1 or R > 1:
             raise ValueError("demc is a population sampler of its own: it cannot be combined with temper or replicates "
                              "(its members are the cell's chains)")
+        want_rank = rank is not None and rank is not False
+        if want_rank and not isinstance(rank, (bool, Mapping)):
+            raise ValueError("rank must be True or a dict with keys among ('probs', 'tail')")
         if diagnostics or covariance or quantiles is not None or density or logpost or stack is not None or rhat or ess:
             raise ValueError("demc does not take the DRAM reductions (diagnostics, covariance, quantiles, density, rhat, "
                              "ess, logpost, stack): MCMCdemc holds R-hat and ESS across the members")
-        return _fit_demc(lk, demc, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag)
+        return _fit_demc(lk, demc, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag,
+                         rank if want_rank else False)
     if R > 1 and (isinstance(swap_every, bool) or int(swap_every) != swap_every or int(swap_every) < 0):
         raise ValueError("swap_every must be an integer >= 0")
     if M != replicates or M < 1:
@@ -675,6 +716,13 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
                          "pass rhat=False to run the replicates without it")
     if ess and not want_rhat:
         raise ValueError("MCMCess is reduced with MCMCrhat: ess=True needs replicates > 1 or rhat=True")
+    want_rank = rank is not None and rank is not False
+    if want_rank and not want_rhat:
+        raise ValueError("MCMCrank is reduced with MCMCrhat: rank needs replicates > 1 or rhat=True")
+    if want_rank and (not isinstance(rank, (bool, Mapping)) or (isinstance(rank, Mapping) and set(rank) - {"probs", "tail"})):
+        raise ValueError("rank must be True or a dict with keys among ('probs', 'tail')")
+    rank_kw = dict(rank) if isinstance(rank, Mapping) else {}
+    rank_host = want_rank and (logpost or R > 1)   # no entry point takes rank with these: from the kept rows instead
     if logpost and int(thin) < 1:
         raise ValueError("MCMClp is reduced from the kept rows: logpost=True needs thin >= 1")
     if stack is not None:
@@ -719,9 +767,10 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
                    plan.prior_sig, plan.qcov_diag, 1.0, o, chain_keys=keys, **tk,
                    **(dict(group=cold_group) if want_rhat else {}),
                    **(dict(ess=True) if ess and R == 1 else {}),
+                   **(dict(rank=rank_kw or True) if want_rank and not rank_host else {}),
                    **(dict(logpost=True) if logpost and R == 1 else {}),
                    **(dict(stats=True) if diagnostics else {}),
-                   **(dict(max_lag=max_lag) if ess or diagnostics else {}),
+                   **(dict(max_lag=max_lag) if ess or diagnostics or want_rank else {}),
                    **(dict(cov=True) if covariance else {}),
                    **(dict(quant=quantiles) if quantiles is not None else {}),
                    **(dict(dens=density) if density is not None and density is not False else {}))
@@ -730,7 +779,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         tempers = [temper_entry(res, k, K, M, R, off + c + 1) for k, c in enumerate(keep)]
         # the tempered entry point has no effective sample size or log-posterior reduction: those of the cold rungs
         # from their kept rows on the host, through the same kernels
-        if ess or logpost:
+        if ess or logpost or rank_host:
             if res.chain is None:
                 raise ValueError("ess and logpost of a tempered fit are reduced from the kept rows: thin >= 1")
             sel = 1 + int(thin) * np.arange(res.chain.shape[0]) >= max(n_burn, 1)
@@ -741,6 +790,9 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
                                       max_lag=max_lag)
             if logpost:
                 res.lp = lk.chainlp(cold_chain, cold_s2, cid, plan.prior_mu[:MK], plan.prior_sig[:MK])
+            if rank_host:
+                res.rank = lk.chainrank(cold_chain, cold_s2, npar=7 + lk.cells.lengths[cid], group=cold_group[:MK],
+                                        max_lag=max_lag, **rank_kw)
         # every per-chain field below is read by cell and replicate: the cold rungs'
         res.mean, res.accept_rate = res.mean[:MK], res.accept_rate[:MK]
         if res.chain is not None:
@@ -793,6 +845,13 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     es = None
     if res.ess is not None:
         es = [ess_entry(res.ess, k, int(cl.lengths[c]), off + c + 1, M) for k, c in enumerate(keep)]
+    if rank_host and R == 1:
+        sel = 1 + int(thin) * np.arange(res.chain.shape[0]) >= max(n_burn, 1)
+        res.rank = lk.chainrank(res.chain[sel], res.s2chain[sel], npar=7 + cl.lengths[np.tile(np.array(keep), M)],
+                                group=cold_group, max_lag=max_lag, **rank_kw)
+    rk = None
+    if res.rank is not None:
+        rk = [rank_entry(res.rank, k, int(cl.lengths[c]), off + c + 1, M) for k, c in enumerate(keep)]
     lps = None
     if res.lp is not None:
         grp = lp_group_stats(lk, res.lp, K, M, max_lag) if M > 1 else None
@@ -803,7 +862,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         stk = stack_entries(lk, res.chain[rows_idx >= max(n_burn, 1)], res.s2chain, res.mean, keep, M, int(stack), off)
     return FitResult(cl.name, results, plots, chains, res.accept_rate[:K].copy(), int(res.n_evals.sum()),
                      res.elapsed_ms, np.array(keep, np.int64) + off, res.final_theta[:K].copy(), MCMClp=lps, MCMCess=es,
-                     MCMCrhat=rh, MCMCstack=stk, MCMCtemper=tempers, MCMCsearch=searched,
+                     MCMCrank=rk, MCMCrhat=rh, MCMCstack=stk, MCMCtemper=tempers, MCMCsearch=searched,
                      MCMCdens=dens, MCMCquant=quant, MCMCdiag=diag, MCMCcov=cov)
 
 
@@ -906,7 +965,7 @@ def demc(lk, n_pop: int = 64, n_gen: int = 1000, thin: int = 1, n_burn: int = 0,
          cells: Optional[Sequence[int]] = None, v0=None, presearch=None, cell_offset: int = 0,
          ratePriorWidth: float = 50.0, jitter=None, CR: float = 0.2, gamma0: float = 0.0, jump_every: int = 10,
          updatesigma: bool = True, sigma2_0=1.0, rhat: bool = True, ess: bool = True, max_lag: int = 0,
-         log_rows: int = 0, approved=None):
+         log_rows: int = 0, approved=None, rank=False):
     """A DE-MC run (``Likelihood.demc``; include/tci.h, ``tci_demc_run``) of the cells ``cells`` (default: all) of
     ``lk`` from :func:`search_population`, or from the final population of a mode search when ``presearch`` is given: a
     dict of ``n_gen`` / ``F`` / ``CR`` for :func:`modesearch` (run here with the same ``n_pop`` and ``seed``), or the
@@ -914,7 +973,9 @@ def demc(lk, n_pop: int = 64, n_gen: int = 1000, thin: int = 1, n_burn: int = 0,
     population by ``default_rng``, the run by RNG stream ``cell_offset + cell``) and seeded as :func:`fit` seeds its
     sampler, so a shard reproduces its cells of the full run bit for bit. ``jitter``: ``[K, ld]`` half-widths, a scalar
     factor on :func:`demc_jitter`'s default, or None. ``n_burn``: the reductions (``rhat`` / ``ess``, across a cell's
-    members) use the kept rows of generations ``>= n_burn``. Returns ``(Demc, SearchPlan)``; row ``k`` of either is cell
+    members) use the kept rows of generations ``>= n_burn``; ``rank``: ``True`` or a dict of ``probs`` / ``tail``: the rank
+    diagnostics and pooled quantiles of those rows too (``Demc.rank``, as ``Likelihood.chainrank`` gives). Returns
+    ``(Demc, SearchPlan)``; row ``k`` of either is cell
     ``plan.cells[k]``."""
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
@@ -942,7 +1003,7 @@ def demc(lk, n_pop: int = 64, n_gen: int = 1000, thin: int = 1, n_burn: int = 0,
                   sigma2_0=sigma2_0, n_gen=n_gen, thin=thin, jump_every=jump_every, CR=CR, gamma0=gamma0,
                   updatesigma=updatesigma, seed=int(seed) * 1000003 + 20201028,
                   keys=np.array(sp.cells, np.int64) + int(cell_offset), stats_from=n_burn, rhat=rhat, ess=ess,
-                  max_lag=max_lag, log_rows=log_rows)
+                  max_lag=max_lag, log_rows=log_rows, rank=rank)
     return res, sp
 
 
@@ -961,7 +1022,8 @@ def demc_entry(res: Demc, k: int, n: int, cell_index: int) -> Dict:
     return {f: d[f] for f in DEMC_FIELDS}
 
 
-def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag):
+def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag,
+              rank=False):
     """:func:`fit` with the DE-MC sampler: every result field from the kept rows of all members pooled."""
     kw = _demc_arg(demc_arg)
     if int(thin) < 1:
@@ -985,7 +1047,7 @@ def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, ce
                         approved=approved, **pk)
         searched = [search_entry(ps[0], k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
     res, sp = demc(lk, thin=int(thin), n_burn=int(n_burn), seed=seed, cells=keep, v0=v0, presearch=ps, cell_offset=off,
-                   ratePriorWidth=ratePriorWidth, max_lag=max_lag, approved=approved, **kw)
+                   ratePriorWidth=ratePriorWidth, max_lag=max_lag, approved=approved, rank=rank, **kw)
     if sp.cells != keep:
         raise RuntimeError(f"demc sampled cells {sp.cells}, the fit keeps {keep}")
     K = len(keep)
@@ -1022,6 +1084,9 @@ def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, ce
         ch["s2chain"] = sq.copy()
         chains.append(ch)
         entries.append(demc_entry(res, k, n, off + c + 1))
+        if res.rank is not None:   # the rank diagnostics across the members, beside rhat_max / ess_min
+            rk = rank_entry(res.rank, k, n, off + c + 1, n_pop)
+            entries[-1].update({f: rk[f] for f in RANK_FIELDS if f not in DEMC_FIELDS})
     return FitResult(cl.name, results, plots, chains, res.accept_rate.mean(axis=1), int(res.n_evals.sum()),
                      res.kernel_ms, np.array(keep, np.int64) + off, res.pop[:, 0].copy(), MCMCsearch=searched,
                      MCMCdemc=entries)
@@ -1152,6 +1217,23 @@ def lp_entry(clp: ChainLp, k: int, n: int, cell_index: int, K: int = 1, M: int =
     d["n_chains"] = int(M)
     d["cell_index"] = int(cell_index)
     return {f: d[f] for f in fields}
+
+
+def rank_entry(ck: ChainRank, k: int, n: int, cell_index: int, n_chains: int) -> Dict:
+    """One ``MCMCrank`` entry (``RANK_FIELDS``) from group ``k`` of ``ck``, a cell of ``n`` points: the vectors trimmed
+    to the cell's ``P = 7 + n`` theta columns with s2 appended as the last column, as :func:`ess_entry` lays columns out
+    (``q`` ``[nq, P + 1]``, ``q_tail`` ``[2, P + 1]``). ``rhat_rank_max``, ``ess_bulk_min``, ``ess_tail_min``: the worst
+    value over the ``P + 1`` columns, NaN left out (NaN when there is none)."""
+    P = 7 + n
+    d = {f: np.concatenate([getattr(ck, f)[k, :P], [getattr(ck, "s2_" + f)[k]]]) for f in RANK_VECTORS}
+    for f in ("q", "q_tail"):
+        d[f] = np.concatenate([getattr(ck, f)[k, :, :P], getattr(ck, "s2_" + f)[k][:, None]], axis=1)
+    worst = lambda a, fn: float(fn(a[~np.isnan(a)])) if not np.all(np.isnan(a)) else float("nan")  # noqa: E731
+    d["rhat_rank_max"] = worst(d["rhat_rank"], np.max)
+    d["ess_bulk_min"], d["ess_tail_min"] = worst(d["ess_bulk"], np.min), worst(d["ess_tail"], np.min)
+    d["probs"], d["tail"] = ck.probs.copy(), np.array(ck.tail, np.float64)
+    d["max_lag"], d["n_rows"], d["n_chains"], d["cell_index"] = int(ck.max_lag), int(ck.n_rows), int(n_chains), int(cell_index)
+    return {f: d[f] for f in RANK_FIELDS}
 
 
 def ess_entry(ce: ChainEss, k: int, n: int, cell_index: int, n_chains: int) -> Dict:
@@ -1408,6 +1490,8 @@ def save_results(fit_result: FitResult, save_loc: str = ".", date: Optional[str]
         variables["MCMCrhat"] = _struct_array(fit_result.MCMCrhat, RHAT_FIELDS)
     if fit_result.MCMCess is not None:  # only a fit with ess=True
         variables["MCMCess"] = _struct_array(fit_result.MCMCess, ESS_FIELDS)
+    if fit_result.MCMCrank is not None:  # only a fit with rank=True
+        variables["MCMCrank"] = _struct_array(fit_result.MCMCrank, RANK_FIELDS)
     if fit_result.MCMCdens is not None:  # only a fit with density=True
         variables["MCMCdens"] = _struct_array(fit_result.MCMCdens, DENS_FIELDS)
     if fit_result.MCMClp is not None:  # only a fit with logpost=True

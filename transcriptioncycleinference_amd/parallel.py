@@ -364,7 +364,7 @@ def fit_sharded(lk, group=None, device: Optional[str] = None, v0=None, approved=
     of its own cells (a replicate's x0 and RNG stream are keyed by the dataset-wide cell index and the replicate, :func:`mcmc.replicate_keys`), the
     gathered ``MCMCresults`` / ``MCMCplot`` are replicate 0's, and every rank's ``local`` carries the ``MCMCrhat`` of
     its own cells. The gathered result's ``MCMCrhat`` stays ``None``. ``ess=True`` goes the same way: ``MCMCess`` is
-    on every rank's ``local``, and the gathered one stays ``None``.
+    on every rank's ``local``, and the gathered one stays ``None``; ``rank=...`` likewise (``MCMCrank``).
 
     ``logpost=True`` (passed on to :func:`mcmc.fit`): every rank's ``MCMClp`` rows are gathered in an all-gather of
     their own (:func:`pack_lp`; ``gather_bytes`` counts it): the scalars, the best samples, the ``ss`` and ``lp``
