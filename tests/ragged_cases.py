@@ -83,6 +83,16 @@ def context_cells(ctx):
     return cl, np.array(twin)
 
 
+def primary_cells(ctx):
+    """point count -> cell index of the context's primary (non-twin) cells, in context_cells' order."""
+    lengths, _ = CONTEXTS[ctx]
+    out, c = {}, 0
+    for n in lengths:
+        out[n] = c
+        c += 2 if n in TWIN_LENGTHS else 1
+    return out
+
+
 def nonfinite_rows(n):
     """[(row, family)]: tests/test_lk_valu_gpu.py's non-finite set for a cell of n points."""
     base = np.concatenate([[2.0, 1.5, 0.5, 2.0, 1.0, 0.7, 9.0], np.zeros(n)])

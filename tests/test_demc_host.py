@@ -71,6 +71,37 @@ def test_index_draw_takes_two_distinct_resting_members():
                 assert r1 != r2 and r1 % 2 != h and r2 % 2 != h and 0 <= r1 < n_pop and 0 <= r2 < n_pop and 0 <= jr < 120
 
 
+@pytest.mark.parametrize("n_pop", [4, 5, 2049, 4095, 4096])
+def test_index_draw_at_the_largest_populations(n_pop):
+    """Every moving member of both half-sweeps, up to the 4,096 members the host admits: an odd population moves
+    (n_pop + 1) / 2 members in half-sweep 0 and n_pop / 2 in half-sweep 1, and the pair comes from the other half."""
+    P = 2055
+    for h in (0, 1):
+        movers = range(h, n_pop, 2)
+        assert len(movers) == (n_pop - h + 1) // 2
+        seen = set()
+        for i in movers:
+            r1, r2, jr = O.index_draw(7, 3, 2 * 5 + h, i, h, n_pop, P)
+            assert r1 != r2 and r1 % 2 != h and r2 % 2 != h and 0 <= r1 < n_pop and 0 <= r2 < n_pop and 0 <= jr < P
+            seen.add((r1, r2))
+        assert len(seen) > 1 or n_pop < 6    # 4 or 5 members: two resting ones, so two ordered pairs in all
+
+
+def test_coordinate_counters_are_one_per_member_and_coordinate():
+    """The counter i * 4096 + j of the last member of the largest population on the longest row stays below 2^24, no
+    two (i, j) share one, and coord_uniforms reads exactly that counter."""
+    P = 2055
+    ctr = np.arange(4096, dtype=np.int64)[:, None] * 4096 + np.arange(P, dtype=np.int64)[None, :]
+    assert ctr[4095].max() == 4095 * 4096 + P - 1 < 2 ** 24
+    assert len(np.unique(ctr)) == ctr.size
+    u, v = O.coord_uniforms(7, 3, 11, 4095, P)
+    assert u.shape == v.shape == (P,) and np.all((u > 0) & (u < 1) & (v > 0) & (v < 1))
+    assert len(np.unique(np.concatenate([u, v]))) == 2 * P
+    for j in (0, 63, 64, 2047, 2048, P - 1):
+        w = O.rng(7, 3, 11, O.P_COORD, int(ctr[4095, j]))
+        assert u[j] == O.u01(w[0], w[1]) and v[j] == O.u01(w[2], w[3])
+
+
 def test_vector_philox_is_the_scalar_one():
     q = O.rng_vec(2 ** 40 + 5, 2 ** 33 + 9, 13, O.P_COORD, 3 * 4096 + np.arange(5))
     for j in range(5):
