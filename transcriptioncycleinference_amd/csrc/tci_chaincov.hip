@@ -1,8 +1,6 @@
 // tci_chaincov.hip -- posterior mean, covariance and correlation of every chain (MATLAB's mean / cov / corrcoef
 // of the chain matrix), reduced on the device; formulas in include/tci.h.
 //
-// The chain lies as [rows][n_chains][ld], contiguous along the parameter.
-//
 //   k_cc_mean  one lane per column, as k_cs_moments: the compensated sum of the column in row order, the
 //              finite / constant checks. NaN marks padding and a column holding a non-finite value.
 //   k_cc_cov   one workgroup (4 wavefronts) per (chain, tile row I). Wavefront w owns the tiles J = I + w,
@@ -19,7 +17,9 @@
 
 #include <cmath>
 
+#include "tci_chain_dev.h"
 #include "tci_csum.h"
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_tile16.h"
 
@@ -30,59 +30,42 @@ namespace {
 constexpr int kCcJ = 4;    // tiles a wavefront accumulates per sweep over the rows (4 accumulator registers each)
 constexpr int kCcRU = 4;   // groups of four rows whose loads are issued together
 
-__device__ __forceinline__ double cc_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-struct CcView {
-  const double* chain;   // [rows][n_chains][ld]
-  const int32_t* npar;   // [n_chains] or null
-  int64_t n_chains, ld, c0;  // c0: the first chain of this launch (mean is indexed by chain, cov / corr by chain - c0)
-};
-
-__device__ __forceinline__ int64_t cc_npar(const CcView& v, int64_t c) { return v.npar ? (int64_t)v.npar[c] : v.ld; }
-
-__global__ __launch_bounds__(64) void k_cc_mean(CcView v, int64_t n, int tiles, double* __restrict__ mean) {
-  const int64_t c = v.c0 + blockIdx.x / tiles;
-  const int64_t j = (int64_t)(blockIdx.x % tiles) * 64 + threadIdx.x;
+// The view's s2 is null: the covariance is of the parameters. c0 is the first chain of a launch: mean is indexed by
+// chain, cov / corr by chain - c0.
+__global__ __launch_bounds__(kChainCols) void k_cc_mean(ChainView v, int64_t c0, int64_t n, int tiles,
+                                                        double* __restrict__ mean) {
+  const int64_t c = c0 + blockIdx.x / tiles;
+  const int64_t j = (int64_t)(blockIdx.x % tiles) * kChainCols + threadIdx.x;
   if (j >= v.ld) return;
   double* out = mean + c * v.ld + j;
-  if (j >= cc_npar(v, c)) {  // padding
-    *out = cc_nan();
+  if (!chain_live(v, c, j)) {  // padding
+    *out = qnan();
     return;
   }
-  const double* col = v.chain + c * v.ld + j;
-  const int64_t rs = v.n_chains * v.ld;
+  const ChainCol col = chain_col(v, c, j, true);
   CSum all;
-  const double x0 = col[0];
+  const double x0 = col.ptr[0];
   bool finite = true, same = true;
-  auto add = [&](double x) {
-    finite &= (x - x) == 0.0;
+  col_sweep(n, [&](int64_t r) { return col.ptr[r * col.rs]; }, [&](double x, int64_t) {
+    finite &= is_finite(x);
     same &= x == x0;
     all.add(x);
-  };
-  int64_t r = 0;
-  for (; r + 8 <= n; r += 8) {
-    double x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = col[(r + u) * rs];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) add(x[u]);
-  }
-  for (; r < n; ++r) add(col[r * rs]);
+  });
   // a constant column is centred on its value exactly (cov 0, corr 0/0)
-  *out = !finite ? cc_nan() : same ? x0 : all.total() / (double)n;
+  *out = !finite ? qnan() : same ? x0 : all.total() / (double)n;
 }
 
 // cov: [chains of the launch][ld][ld]. NT = ceil(ld / 16).
-__global__ __launch_bounds__(256) void k_cc_cov(CcView v, int64_t n, int NT, const double* __restrict__ mean,
-                                                double* __restrict__ cov) {
+__global__ __launch_bounds__(256) void k_cc_cov(ChainView v, int64_t c0, int64_t n, int NT,
+                                                const double* __restrict__ mean, double* __restrict__ cov) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, jl = lane & 15;
-  const int64_t cl = blockIdx.x / NT, c = v.c0 + cl, ld = v.ld;
+  const int64_t cl = blockIdx.x / NT, c = c0 + cl, ld = v.ld;
   const int I = (int)(blockIdx.x % NT);
-  const int64_t P = cc_npar(v, c);
+  const int64_t P = chain_npar(v, c);
   const int NTP = (int)((P + 15) / 16);  // tiles holding a real column
   const double* mc = mean + c * ld;
   double* covc = cov + cl * ld * ld;
-  const double nan = cc_nan();
+  const double nan = qnan();
   if (I < NTP) {
     const int64_t rs = v.n_chains * ld;
     const double* base = v.chain + c * ld;
@@ -167,19 +150,20 @@ __global__ __launch_bounds__(256) void k_cc_cov(CcView v, int64_t n, int NT, con
 }
 
 // One workgroup per (chain, row i).
-__global__ __launch_bounds__(128) void k_cc_corr(CcView v, const double* __restrict__ cov, double* __restrict__ corr) {
+__global__ __launch_bounds__(128) void k_cc_corr(ChainView v, int64_t c0, const double* __restrict__ cov,
+                                                 double* __restrict__ corr) {
   const int64_t ld = v.ld, cl = blockIdx.x / ld, i = blockIdx.x % ld;
-  const int64_t P = cc_npar(v, v.c0 + cl);
+  const int64_t P = chain_npar(v, c0 + cl);
   const double* covc = cov + cl * ld * ld;
   double* out = corr + cl * ld * ld + i * ld;
-  const double nan = cc_nan();
+  const double nan = qnan();
   const double cii = covc[i * ld + i];
   const double si = sqrt(cii);
   for (int64_t j = threadIdx.x; j < ld; j += 128) {
     double r = nan;
     if (i < P && j < P) {
       if (i == j) {
-        r = (cii > 0.0 && cii - cii == 0.0) ? 1.0 : nan;
+        r = (cii > 0.0 && is_finite(cii)) ? 1.0 : nan;
       } else {
         r = covc[i * ld + j] / (si * sqrt(covc[j * ld + j]));
         r = r > 1.0 ? 1.0 : r < -1.0 ? -1.0 : r;  // keeps NaN
@@ -197,14 +181,15 @@ int launch_chaincov(const double* chain, int64_t n_rows, int64_t n_chains, int64
       ld > ((int64_t)1 << 24) || c0 < 0 || nc < 1 || c0 + nc > n_chains)
     return TCI_EINVAL;
   if (nc > chaincov_max_chains(ld)) return TCI_EINVAL;
-  const int64_t tiles = (ld + 63) / 64, NT = (ld + 15) / 16;
-  const CcView v{chain, npar, n_chains, ld, c0};
+  const int64_t tiles = (ld + kChainCols - 1) / kChainCols, NT = (ld + 15) / 16;
+  const ChainView v{chain, nullptr, npar, n_chains, ld};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_cc_mean, dim3((unsigned)(nc * tiles)), dim3(64), 0, s, v, n_rows, (int)tiles, mean);
+  hipLaunchKernelGGL(k_cc_mean, dim3((unsigned)(nc * tiles)), dim3(kChainCols), 0, s, v, c0, n_rows, (int)tiles,
+                     mean);
   if (hipGetLastError() != hipSuccess) return TCI_EHIP;
-  hipLaunchKernelGGL(k_cc_cov, dim3((unsigned)(nc * NT)), dim3(256), 0, s, v, n_rows, (int)NT, mean, cov);
+  hipLaunchKernelGGL(k_cc_cov, dim3((unsigned)(nc * NT)), dim3(256), 0, s, v, c0, n_rows, (int)NT, mean, cov);
   if (hipGetLastError() != hipSuccess) return TCI_EHIP;
-  hipLaunchKernelGGL(k_cc_corr, dim3((unsigned)(nc * ld)), dim3(128), 0, s, v, cov, corr);
+  hipLaunchKernelGGL(k_cc_corr, dim3((unsigned)(nc * ld)), dim3(128), 0, s, v, c0, cov, corr);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 
@@ -212,11 +197,11 @@ int launch_chain_mean(const double* chain, int64_t n_rows, int64_t n_chains, int
                       double* mean, void* stream) {
   if (!chain || !mean || n_rows < 1 || n_rows > ((int64_t)1 << 30) || n_chains < 1 || ld < 1 || ld > ((int64_t)1 << 24))
     return TCI_EINVAL;
-  const int64_t tiles = (ld + 63) / 64;
+  const int64_t tiles = (ld + kChainCols - 1) / kChainCols;
   if (n_chains * tiles > 2147483647) return TCI_EINVAL;
-  const CcView v{chain, npar, n_chains, ld, 0};
-  hipLaunchKernelGGL(k_cc_mean, dim3((unsigned)(n_chains * tiles)), dim3(64), 0, (hipStream_t)stream, v, n_rows,
-                     (int)tiles, mean);
+  const ChainView v{chain, nullptr, npar, n_chains, ld};
+  hipLaunchKernelGGL(k_cc_mean, dim3((unsigned)(n_chains * tiles)), dim3(kChainCols), 0, (hipStream_t)stream, v,
+                     (int64_t)0, n_rows, (int)tiles, mean);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 

@@ -1,20 +1,16 @@
 // tci_chaindens.hip -- marginal posterior density (a Gaussian kernel estimate, mcmcstat's density.m) and
 // histogram of every chain column, reduced on the device; the definition is in include/tci.h.
 //
-// The chain lies as [rows][n_chains][ld], contiguous along the parameter; a chain's s2 is column ld. As in
-// tci_chainquant.hip one workgroup (4 wavefronts) takes 64 consecutive columns of one chain, lane l of every
-// wavefront column 64 t + l, so a row read is one 512 B segment. The rows are cut into segments of kCdSeg rows;
-// a workgroup takes one segment of its 64 columns, so a long column spreads over many workgroups. The segment
-// count and boundaries follow from n_rows alone, every partial result of a segment is stored, and the small
-// combine kernels add the partials in segment order: an output's bits do not depend on how many workgroups ran.
+// One workgroup (4 wavefronts) takes one segment of a column tile of one chain (tci_chain_dev.h), so a long column
+// spreads over many workgroups; the small combine kernels add the segments' partials in segment order.
 //
 //   k_cd_pass1   per segment: key-order min / max, the non-finite flag and the compensated sum. The wavefronts
-//                split the rows (wavefront w the blocks of kCdRU rows w, w + 4, ..) and are combined in order.
+//                split the rows (seg_walk) and are combined in order.
 //   k_cd_mean    per column: the segments combined; xmin, xmax, the mean and the column's state.
 //   k_cd_pass2   per segment: the centred sum of squares.
 //   (launch_chainquant gives the quartiles: the project's one quantile definition.)
 //   k_cd_params  per column: sd, iqr and the bandwidth.
-//   k_cd_dens    per segment: the segment's rows are staged once in LDS (kCdSeg x 64 doubles, 128 KiB), every
+//   k_cd_dens    per segment: the segment's rows are staged once in LDS (kChainSeg x 64 doubles, 128 KiB), every
 //                row's histogram bin next to them (one byte). The four wavefronts split the grid points in groups
 //                of four (four independent exp chains per lane); each (column, k) sum runs over the segment's
 //                rows in row order. Then the staging area becomes the counter table [B][64] (as k_cq_select's)
@@ -27,7 +23,9 @@
 #include <algorithm>
 #include <cmath>
 
+#include "tci_chain_dev.h"
 #include "tci_csum.h"
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_key.h"
 
@@ -35,22 +33,13 @@ namespace tci {
 
 namespace {
 
-constexpr int kCdCols = 64;    // columns per workgroup: one per lane
-constexpr int kCdWaves = 4;    // wavefronts per workgroup
-constexpr int kCdRU = 8;       // rows a wavefront loads together in the moments passes
-constexpr int kCdSeg = 256;    // rows per segment: the row block k_cd_dens stages in LDS
 constexpr int kCdKU = 4;       // grid points a wavefront evaluates together
-constexpr int kCdThreads = kCdCols * kCdWaves;
 constexpr int kCdPar = 4;      // per-column parameters: xmin, xmax, mean, bw
-
-enum : int32_t { CD_PAD = 0, CD_OK = 1, CD_BAD = 2 };
-
-struct CdView {
-  const double* chain;  // [rows][n_chains][ld]
-  const double* s2;     // [rows][n_chains] or null
-  const int32_t* npar;  // [n_chains] or null
-  int64_t n_chains, ld;
-};
+// k_cd_dens stages a whole segment of its 64 columns in LDS, a bin byte next to every row, and reuses the rows'
+// area for up to 256 bins of 64 counters
+constexpr size_t kCdStage = kChainSeg * kChainCols * sizeof(double);  // 128 KiB
+static_assert(kCdStage + kChainSeg * kChainCols * sizeof(uint8_t) <= 160 * 1024, "the stage fits a CU's LDS");
+static_assert(256 * kChainCols * sizeof(uint32_t) <= kCdStage, "the counters fit the stage");
 
 // The scratch of one call, carved from one allocation (8-byte items first).
 struct CdScratch {
@@ -64,55 +53,27 @@ struct CdScratch {
   uint32_t* pc;           // [S][n_chains][B][ld + 1] count partials
 };
 
-__device__ __forceinline__ double cd_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-__device__ __forceinline__ bool cd_live(const CdView& v, int64_t c, int64_t j) {
-  return j < v.ld ? j < (v.npar ? (int64_t)v.npar[c] : v.ld) : (j == v.ld && v.s2 != nullptr);
-}
-
-// The workgroup's chain, column and segment: blockIdx.x = (chain * tiles + tile) * S + segment.
-struct CdWhere {
-  int64_t c, j, r0;
-  int nr, seg;
-};
-__device__ __forceinline__ CdWhere cd_where(int64_t n, int tiles, int S, int lane) {
-  CdWhere w;
-  const int64_t ct = (int64_t)blockIdx.x / S;
-  w.seg = (int)((int64_t)blockIdx.x % S);
-  w.c = ct / tiles;
-  w.j = (ct % tiles) * kCdCols + lane;
-  w.r0 = (int64_t)w.seg * kCdSeg;
-  w.nr = (int)(n - w.r0 < kCdSeg ? n - w.r0 : kCdSeg);
-  return w;
-}
-
-__global__ __launch_bounds__(kCdThreads) void k_cd_pass1(CdView v, int64_t n, int tiles, int S, CdScratch sc) {
-  __shared__ uint64_t r_mn[kCdThreads], r_mx[kCdThreads];
-  __shared__ double r_s[kCdThreads], r_c[kCdThreads];
-  __shared__ uint32_t r_bad[kCdThreads];
+__global__ __launch_bounds__(kChainThreads) void k_cd_pass1(ChainView v, int64_t n, int tiles, int S, CdScratch sc) {
+  __shared__ uint64_t r_mn[kChainThreads], r_mx[kChainThreads];
+  __shared__ double r_s[kChainThreads], r_c[kChainThreads];
+  __shared__ uint32_t r_bad[kChainThreads];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const CdWhere w = cd_where(n, tiles, S, lane);
+  const SegWhere w = seg_where(n, tiles, S, lane);
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
-  const bool live = w.j < ldc && cd_live(v, w.c, w.j);
-  const double* col = !live ? nullptr : w.j < v.ld ? v.chain + w.c * v.ld + w.j : v.s2 + w.c;
-  const int64_t rs = w.j < v.ld ? v.n_chains * v.ld : v.n_chains;
+  const bool live = w.j < ldc && chain_live(v, w.c, w.j);
+  const ChainCol col = chain_col(v, w.c, w.j, live);
   uint64_t mn = ~0ull, mx = 0;
   bool bad = false;
   CSum cs;
-  for (int i0 = wave * kCdRU; i0 < w.nr; i0 += kCdWaves * kCdRU) {
-    double x[kCdRU];
-#pragma unroll
-    for (int u = 0; u < kCdRU; ++u) x[u] = (live && i0 + u < w.nr) ? col[(w.r0 + i0 + u) * rs] : 0.0;
-#pragma unroll
-    for (int u = 0; u < kCdRU; ++u)
-      if (live && i0 + u < w.nr) {
-        const uint64_t k = to_key(x[u]);
-        mn = k < mn ? k : mn;
-        mx = k > mx ? k : mx;
-        bad |= (x[u] - x[u]) != 0.0;
-        cs.add(x[u]);
-      }
-  }
+  seg_walk(col, w, wave, live, 0.0, [&](double x, int i) {
+    if (live && i < w.nr) {
+      const uint64_t k = to_key(x);
+      mn = k < mn ? k : mn;
+      mx = k > mx ? k : mx;
+      bad |= !is_finite(x);
+      cs.add(x);
+    }
+  });
   r_mn[tid] = mn;
   r_mx[tid] = mx;
   r_s[tid] = cs.s;
@@ -121,13 +82,12 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_pass1(CdView v, int64_t n, in
   __syncthreads();
   if (wave == 0 && w.j < ldc) {  // the wavefronts in order
     uint32_t anybad = r_bad[lane];
-    for (int k = 1; k < kCdWaves; ++k) {
-      const uint64_t m0 = r_mn[k * kCdCols + lane], m1 = r_mx[k * kCdCols + lane];
+    for (int k = 1; k < kChainWaves; ++k) {
+      const uint64_t m0 = r_mn[k * kChainCols + lane], m1 = r_mx[k * kChainCols + lane];
       mn = m0 < mn ? m0 : mn;
       mx = m1 > mx ? m1 : mx;
-      anybad |= r_bad[k * kCdCols + lane];
-      cs.add(r_s[k * kCdCols + lane]);
-      cs.c += r_c[k * kCdCols + lane];
+      anybad |= r_bad[k * kChainCols + lane];
+      cs.merge(r_s[k * kChainCols + lane], r_c[k * kChainCols + lane]);
     }
     const int64_t o = (int64_t)w.seg * ncol + w.c * ldc + w.j;
     sc.p_mn[o] = mn;
@@ -138,11 +98,11 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_pass1(CdView v, int64_t n, in
   }
 }
 
-__global__ __launch_bounds__(kCdThreads) void k_cd_mean(CdView v, int64_t n, int S, CdScratch sc) {
+__global__ __launch_bounds__(kChainThreads) void k_cd_mean(ChainView v, int64_t n, int S, CdScratch sc) {
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
-  const int64_t e = (int64_t)blockIdx.x * kCdThreads + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
   if (e >= ncol) return;
-  const bool live = cd_live(v, e / ldc, e % ldc);
+  const bool live = chain_live(v, e / ldc, e % ldc);
   uint64_t mn = ~0ull, mx = 0;
   uint32_t bad = 0;
   CSum cs;
@@ -152,11 +112,10 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_mean(CdView v, int64_t n, int
     mn = m0 < mn ? m0 : mn;
     mx = m1 > mx ? m1 : mx;
     bad |= sc.p_bad[o];
-    cs.add(sc.p_s[o]);
-    cs.c += sc.p_c[o];
+    cs.merge(sc.p_s[o], sc.p_c[o]);
   }
   const bool ok = live && !bad;
-  sc.state[e] = !live ? CD_PAD : bad ? CD_BAD : CD_OK;
+  sc.state[e] = !live ? COL_PAD : bad ? COL_BAD : COL_OK;
   sc.par[0 * ncol + e] = ok ? from_key(mn) : 0.0;
   sc.par[1 * ncol + e] = ok ? from_key(mx) : 0.0;
   // a constant column is centred on its value exactly, as tci_chaincov does: sd 0, bw 0
@@ -164,41 +123,34 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_mean(CdView v, int64_t n, int
   sc.par[3 * ncol + e] = 0.0;
 }
 
-__global__ __launch_bounds__(kCdThreads) void k_cd_pass2(CdView v, int64_t n, int tiles, int S, CdScratch sc) {
-  __shared__ double r_s[kCdThreads];
+__global__ __launch_bounds__(kChainThreads) void k_cd_pass2(ChainView v, int64_t n, int tiles, int S, CdScratch sc) {
+  __shared__ double r_s[kChainThreads];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const CdWhere w = cd_where(n, tiles, S, lane);
+  const SegWhere w = seg_where(n, tiles, S, lane);
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
   const int64_t e = w.c * ldc + w.j;
-  const bool ok = w.j < ldc && sc.state[e] == CD_OK;
-  const double* col = !ok ? nullptr : w.j < v.ld ? v.chain + w.c * v.ld + w.j : v.s2 + w.c;
-  const int64_t rs = w.j < v.ld ? v.n_chains * v.ld : v.n_chains;
+  const bool ok = w.j < ldc && sc.state[e] == COL_OK;
+  const ChainCol col = chain_col(v, w.c, w.j, ok);
   const double mean = ok ? sc.par[2 * ncol + e] : 0.0;
   double ss = 0.0;
-  for (int i0 = wave * kCdRU; i0 < w.nr; i0 += kCdWaves * kCdRU) {
-    double x[kCdRU];
-#pragma unroll
-    for (int u = 0; u < kCdRU; ++u) x[u] = (ok && i0 + u < w.nr) ? col[(w.r0 + i0 + u) * rs] : mean;
-#pragma unroll
-    for (int u = 0; u < kCdRU; ++u) {
-      const double d = x[u] - mean;
-      ss += d * d;
-    }
-  }
+  seg_walk(col, w, wave, ok, mean, [&](double x, int) {  // a padded row adds +0.0
+    const double d = x - mean;
+    ss += d * d;
+  });
   r_s[tid] = ss;
   __syncthreads();
   if (wave == 0 && w.j < ldc) {
-    for (int k = 1; k < kCdWaves; ++k) ss += r_s[k * kCdCols + lane];
+    for (int k = 1; k < kChainWaves; ++k) ss += r_s[k * kChainCols + lane];
     sc.p_s[(int64_t)w.seg * ncol + e] = ss;
   }
 }
 
-__global__ __launch_bounds__(kCdThreads) void k_cd_params(int64_t n_chains, int64_t ld, int64_t n, int S, double bw_scale,
-                                                           double npow, CdScratch sc) {
+__global__ __launch_bounds__(kChainThreads) void k_cd_params(int64_t n_chains, int64_t ld, int64_t n, int S,
+                                                             double bw_scale, double npow, CdScratch sc) {
   const int64_t ldc = ld + 1, ncol = n_chains * ldc;
-  const int64_t e = (int64_t)blockIdx.x * kCdThreads + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
   if (e >= ncol) return;
-  if (sc.state[e] != CD_OK) return;
+  if (sc.state[e] != COL_OK) return;
   double ss = 0.0;
   for (int s = 0; s < S; ++s) ss += sc.p_s[(int64_t)s * ncol + e];
   const double sd = sqrt(ss / (double)(n - 1));
@@ -208,37 +160,38 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_params(int64_t n_chains, int6
   sc.par[3 * ncol + e] = __dmul_rn(__dmul_rn(__dmul_rn(bw_scale, 1.06), s), npow);
 }
 
-__global__ __launch_bounds__(kCdThreads) void k_cd_dens(CdView v, int64_t n, int tiles, int S, int G, int B,
+__global__ __launch_bounds__(kChainThreads) void k_cd_dens(ChainView v, int64_t n, int tiles, int S, int G, int B,
                                                          CdScratch sc) {
-  __shared__ double xs[kCdSeg * kCdCols];    // [row][lane]; afterwards the counter table [bin][lane]
-  __shared__ uint8_t bins[kCdSeg * kCdCols];  // [row][lane]
+  __shared__ double xs[kChainSeg * kChainCols];    // [row][lane]; afterwards the counter table [bin][lane]
+  __shared__ uint8_t bins[kChainSeg * kChainCols];  // [row][lane]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const CdWhere w = cd_where(n, tiles, S, lane);
+  const SegWhere w = seg_where(n, tiles, S, lane);
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
   const int64_t e = w.c * ldc + w.j;
   const bool in_out = w.j < ldc;
-  const bool ok = in_out && sc.state[e] == CD_OK;
-  const double* col = !ok ? nullptr : w.j < v.ld ? v.chain + w.c * v.ld + w.j : v.s2 + w.c;
-  const int64_t rs = w.j < v.ld ? v.n_chains * v.ld : v.n_chains;
+  const bool ok = in_out && sc.state[e] == COL_OK;
+  const ChainCol col = chain_col(v, w.c, w.j, ok);
   const double xmin = ok ? sc.par[0 * ncol + e] : 0.0, xmax = ok ? sc.par[1 * ncol + e] : 0.0;
   const double bw = ok ? sc.par[3 * ncol + e] : 1.0;
   const double r = __dsub_rn(xmax, xmin);
   const double fb = (double)B;
   // stage the segment's rows and their bins
-  for (int i0 = wave * kCdRU; i0 < w.nr; i0 += kCdWaves * kCdRU) {
-    double x[kCdRU];
+  // seg_walk's loop, written out: this kernel is the reduction's hot spot, and through the helper the compiler
+  // schedules it differently (7 % on the whole reduction, profiles/chain_layout/unshared.json)
+  for (int i0 = wave * kChainRU; i0 < w.nr; i0 += kChainWaves * kChainRU) {
+    double x[kChainRU];
 #pragma unroll
-    for (int u = 0; u < kCdRU; ++u) x[u] = (ok && i0 + u < w.nr) ? col[(w.r0 + i0 + u) * rs] : xmin;
+    for (int u = 0; u < kChainRU; ++u) x[u] = (ok && i0 + u < w.nr) ? col.ptr[(w.r0 + i0 + u) * col.rs] : xmin;
 #pragma unroll
-    for (int u = 0; u < kCdRU; ++u)
+    for (int u = 0; u < kChainRU; ++u)
       if (i0 + u < w.nr) {
         int b = 0;
         if (r > 0.0) {
           b = (int)floor(__dmul_rn(__ddiv_rn(__dsub_rn(x[u], xmin), r), fb));
           b = b > B - 1 ? B - 1 : b < 0 ? 0 : b;
         }
-        xs[(i0 + u) * kCdCols + lane] = x[u];
-        bins[(i0 + u) * kCdCols + lane] = (uint8_t)b;
+        xs[(i0 + u) * kChainCols + lane] = x[u];
+        bins[(i0 + u) * kChainCols + lane] = (uint8_t)b;
       }
   }
   __syncthreads();
@@ -247,7 +200,7 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_dens(CdView v, int64_t n, int
   const double lo = __dsub_rn(xmin, w8), hi = __dadd_rn(xmax, w8);
   const double step = __ddiv_rn(__dsub_rn(hi, lo), (double)(G - 1));
   const double inv = 1.0 / bw;
-  for (int kb = wave * kCdKU; kb < G; kb += kCdWaves * kCdKU) {
+  for (int kb = wave * kCdKU; kb < G; kb += kChainWaves * kCdKU) {
     double g[kCdKU], a[kCdKU];
 #pragma unroll
     for (int u = 0; u < kCdKU; ++u) {
@@ -255,7 +208,7 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_dens(CdView v, int64_t n, int
       a[u] = 0.0;
     }
     for (int i = 0; i < w.nr; ++i) {
-      const double x = xs[i * kCdCols + lane];
+      const double x = xs[i * kChainCols + lane];
 #pragma unroll
       for (int u = 0; u < kCdKU; ++u) {
         const double z = (g[u] - x) * inv;
@@ -270,32 +223,33 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_dens(CdView v, int64_t n, int
   }
   __syncthreads();  // every wavefront is done with the rows
   uint32_t* tab = reinterpret_cast<uint32_t*>(xs);  // B * 64 counters <= 64 KiB
-  for (int b = wave; b < B; b += kCdWaves) tab[b * kCdCols + lane] = 0u;
+  for (int b = wave; b < B; b += kChainWaves) tab[b * kChainCols + lane] = 0u;
   __syncthreads();
-  for (int i = wave; i < w.nr; i += kCdWaves) atomicAdd(&tab[(int)bins[i * kCdCols + lane] * kCdCols + lane], 1u);
+  for (int i = wave; i < w.nr; i += kChainWaves)
+    atomicAdd(&tab[(int)bins[i * kChainCols + lane] * kChainCols + lane], 1u);
   __syncthreads();
   if (in_out)
-    for (int b = wave; b < B; b += kCdWaves)
-      sc.pc[(((int64_t)w.seg * v.n_chains + w.c) * B + b) * ldc + w.j] = tab[b * kCdCols + lane];
+    for (int b = wave; b < B; b += kChainWaves)
+      sc.pc[(((int64_t)w.seg * v.n_chains + w.c) * B + b) * ldc + w.j] = tab[b * kChainCols + lane];
 }
 
 // out_d: [n_chains][G + 3][ldc] (dens rows, xmin, xmax, bw); out_c: [n_chains][B][ldc]
-__global__ __launch_bounds__(kCdThreads) void k_cd_out(int64_t n_chains, int64_t ld, int64_t n, int S, int G, int B,
+__global__ __launch_bounds__(kChainThreads) void k_cd_out(int64_t n_chains, int64_t ld, int64_t n, int S, int G, int B,
                                                         CdScratch sc, double* __restrict__ out_d,
                                                         int32_t* __restrict__ out_c) {
   const int64_t ldc = ld + 1, ncol = n_chains * ldc;
   const int64_t rows = G + B + 3;
-  const int64_t id = (int64_t)blockIdx.x * kCdThreads + threadIdx.x;
+  const int64_t id = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
   if (id >= ncol * rows) return;
   const int64_t j = id % ldc, t = (id / ldc) % rows, c = id / ldc / rows;
   const int64_t e = c * ldc + j;
-  const bool ok = sc.state[e] == CD_OK;
+  const bool ok = sc.state[e] == COL_OK;
   const double bw = sc.par[3 * ncol + e];
   if (t < G) {
     double sum = 0.0;
     for (int s = 0; s < S; ++s) sum += sc.pd[(((int64_t)s * n_chains + c) * G + t) * ldc + j];
     const double d = sum / ((double)n * bw) * 0.3989422804014327;  // 1 / sqrt(2 pi)
-    out_d[(c * (G + 3) + t) * ldc + j] = ok && bw > 0.0 ? d : cd_nan();
+    out_d[(c * (G + 3) + t) * ldc + j] = ok && bw > 0.0 ? d : qnan();
   } else if (t < G + B) {
     const int64_t b = t - G;
     uint32_t cnt = 0;
@@ -303,7 +257,7 @@ __global__ __launch_bounds__(kCdThreads) void k_cd_out(int64_t n_chains, int64_t
     out_c[(c * B + b) * ldc + j] = ok ? (int32_t)cnt : -1;
   } else {
     const int64_t k = t - G - B;  // xmin, xmax, bw
-    out_d[(c * (G + 3) + G + k) * ldc + j] = !ok ? cd_nan() : k == 2 ? bw : sc.par[k * ncol + e];
+    out_d[(c * (G + 3) + G + k) * ldc + j] = !ok ? qnan() : k == 2 ? bw : sc.par[k * ncol + e];
   }
 }
 
@@ -316,12 +270,12 @@ int cd_sizes(int64_t n_rows, int64_t n_chains, int64_t ld, int32_t G, int32_t B,
   if (n_rows < 2 || n_rows > ((int64_t)1 << 30) || n_chains < 1 || n_chains > ((int64_t)1 << 30) || ld < 1 ||
       ld > ((int64_t)1 << 24) || G < 2 || G > 256 || B < 1 || B > 256)
     return TCI_EINVAL;
-  z->S = (n_rows + kCdSeg - 1) / kCdSeg;  // <= 2^22
-  z->tiles = (ld + 1 + kCdCols - 1) / kCdCols;
+  z->S = (n_rows + kChainSeg - 1) / kChainSeg;  // <= 2^22
+  z->tiles = (ld + 1 + kChainCols - 1) / kChainCols;
   const long double lim = 2147483647.0L;
   const long double ncol = (long double)n_chains * (long double)(ld + 1);
   if (n_chains > ((int64_t)1 << 30) / z->tiles ||  // launch_chainquant's limit
-      (long double)n_chains * z->tiles * z->S > lim || ncol * (G + B + 3) / kCdThreads + 1 > lim)
+      (long double)n_chains * z->tiles * z->S > lim || ncol * (G + B + 3) / kChainThreads + 1 > lim)
     return TCI_ERANGE;
   const long double i8 = (4.0L * z->S + kCdPar + 2) * ncol + (long double)z->S * ncol * G;
   const long double i4 = ((long double)z->S + 1) * ncol + (long double)z->S * ncol * B;
@@ -365,9 +319,10 @@ int launch_chaindens(const double* chain, const double* s2, int64_t n_rows, int6
   sc.p_bad = p4;
   sc.state = (int32_t*)(p4 + sn);
   sc.pc = p4 + sn + nc;
-  const CdView v{chain, s2, npar, n_chains, ld};
+  const ChainView v{chain, s2, npar, n_chains, ld};
   hipStream_t st = (hipStream_t)stream;
-  const dim3 blk(kCdThreads), seg_grid((unsigned)z.blocks), col_grid((unsigned)((z.ncol + kCdThreads - 1) / kCdThreads));
+  const dim3 blk(kChainThreads), seg_grid((unsigned)z.blocks);
+  const dim3 col_grid((unsigned)((z.ncol + kChainThreads - 1) / kChainThreads));
   const int S = (int)z.S, tiles = (int)z.tiles;
   hipLaunchKernelGGL(k_cd_pass1, seg_grid, blk, 0, st, v, n_rows, tiles, S, sc);
   hipLaunchKernelGGL(k_cd_mean, col_grid, blk, 0, st, v, n_rows, S, sc);
@@ -379,8 +334,8 @@ int launch_chaindens(const double* chain, const double* s2, int64_t n_rows, int6
   hipLaunchKernelGGL(k_cd_params, col_grid, blk, 0, st, n_chains, ld, n_rows, S, bw_scale, npow, sc);
   hipLaunchKernelGGL(k_cd_dens, seg_grid, blk, 0, st, v, n_rows, tiles, S, (int)G, (int)B, sc);
   const int64_t out_items = z.ncol * (int64_t)(G + B + 3);
-  hipLaunchKernelGGL(k_cd_out, dim3((unsigned)((out_items + kCdThreads - 1) / kCdThreads)), blk, 0, st, n_chains, ld,
-                     n_rows, S, (int)G, (int)B, sc, out_d, out_c);
+  hipLaunchKernelGGL(k_cd_out, dim3((unsigned)((out_items + kChainThreads - 1) / kChainThreads)), blk, 0, st, n_chains,
+                     ld, n_rows, S, (int)G, (int)B, sc, out_d, out_c);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 

@@ -2,16 +2,14 @@
 // initial monotone sequence), its autocorrelation time, its window and the pooled mean's Monte-Carlo standard error,
 // reduced on the device; the definition is in include/tci.h.
 //
-// The chain lies as [rows][n_chains][ld], contiguous along the parameter; a chain's s2 is column ld. The moments
-// (mu_j, s2_j of the whole chains and of their halves, the columns' states, pooled_std) are tci_chainrhat.hip's:
-// launch_chainess runs launch_chainrhat first and reads its scratch, so both statistics see the same bits.
+// The moments (mu_j, s2_j of the whole chains and of their halves, the columns' states, pooled_std) are
+// tci_chainrhat.hip's: launch_chainess runs launch_chainrhat first and reads its scratch, so both statistics see the
+// same bits.
 //
-//   k_ce_lags   one workgroup (4 wavefronts) per (group, 64 columns, classic or split); lane l of every wavefront
-//               is column 64 t + l, so a row read is one 512 B segment. A sequence is (chain, first row, length):
-//               a whole chain (0, n) or a half (0, h) / (n - h, h). Lags go in tiles of 64, 16 per wavefront; rows
-//               in tiles of 32: the centred rows t and t + k0 .. t + k0 + 94 of a sequence (0 past its end: the sum
-//               is linear, not circular) are staged in LDS once and every lane forms its column's 16 lagged
-//               products per row from there, as k_cs_iact does. A lag tile walks the group's sequences in order,
+//   k_ce_lags   one workgroup (4 wavefronts) per (group, column tile, classic or split). A sequence is (chain, first
+//               row, length): a whole chain (0, n) or a half (0, h) / (n - h, h). The lagged products are
+//               tci_chain_dev.h's lag tile, as in k_cs_iact, with 0 past a sequence's end: the sum is linear, not
+//               circular. A lag tile walks the group's sequences in order,
 //               adding c_j(k) / L to a(k); rows past L - k0 have no partner at any lag of the tile and are not
 //               read. After a lag tile wavefront 0 advances every column's pair sum (Geyer's P_i, Q_i); a column
 //               that stopped is masked, and the workgroup ends with its last live column.
@@ -26,50 +24,40 @@
 
 #include <cmath>
 
+#include "tci_chain_dev.h"
 #include "tci_chainrhat_dev.h"
+#include "tci_fp.h"
 #include "tci_internal.h"
 
 namespace tci {
 
 namespace {
 
-constexpr int kCeCols = 64;                  // columns per workgroup: one per lane
-constexpr int kCeRT = 32;                    // rows per LDS tile
-constexpr int kCeKT = 64;                    // lags per tile (even: a tile holds whole pairs)
-constexpr int kCeLW = 16;                    // lags per wavefront (kCeKT / 4)
-constexpr int kCeBRows = kCeRT + kCeKT - 1;  // shifted rows a tile needs
-constexpr size_t kCeLds = (size_t)(kCeRT + kCeBRows) * kCeCols * sizeof(double);  // 65,024 B: two workgroups per CU
-
-struct CeView {
-  const double* chain;   // [rows][n_chains][ld]
-  const double* s2;      // [rows][n_chains] or null
-  const int32_t* npar;   // [n_chains] or null
-  int64_t n_chains, ld;
-};
+static_assert(kLagKT % 2 == 0, "a lag tile holds whole Geyer pairs");
 
 struct CeMoments {
   const double *mu, *var;  // [kCrSeq][ncol]
   const int32_t* state;    // [ncol]
 };
 
-__device__ __forceinline__ double ce_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
-
 // out_d: [5][n_groups][ldc] = ess, ess_split, tau, tau_split, mcse; out_w: [2][n_groups][ldc].
-__global__ __launch_bounds__(256) void k_ce_lags(CeView v, int64_t n, int64_t h, int64_t max_lag, int tiles,
-                                                 int64_t n_groups, const int32_t* __restrict__ g_off,
-                                                 const int32_t* __restrict__ g_list, CeMoments mo,
-                                                 const double* __restrict__ cap, const double* __restrict__ rhat_out,
-                                                 double* __restrict__ out_d, int32_t* __restrict__ out_w) {
+__global__ __launch_bounds__(kChainThreads) void k_ce_lags(ChainView v, int64_t n, int64_t h, int64_t max_lag,
+                                                           int tiles, int64_t n_groups,
+                                                           const int32_t* __restrict__ g_off,
+                                                           const int32_t* __restrict__ g_list, CeMoments mo,
+                                                           const double* __restrict__ cap,
+                                                           const double* __restrict__ rhat_out,
+                                                           double* __restrict__ out_d, int32_t* __restrict__ out_w) {
   extern __shared__ __align__(16) double ce_lds[];
-  __shared__ int s_live[kCeCols];
+  __shared__ int s_live[kChainCols];
   __shared__ int s_any;
-  double* A = ce_lds;                    // [kCeRT][64]: centred rows t0 ..
-  double* B = ce_lds + kCeRT * kCeCols;  // [kCeBRows][64]: centred rows t0 + k0 ..; then a(k) [kCeKT][64]
+  double* A = ce_lds;                        // [kLagRT][64]: centred rows t0 ..
+  double* B = ce_lds + kLagRT * kChainCols;  // [kLagBRows][64]: centred rows t0 + k0 ..; then a(k) [kLagKT][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int split = (int)(blockIdx.x & 1u);
   const int64_t gt = (int64_t)(blockIdx.x >> 1);
   const int64_t g = gt / tiles;
-  const int64_t j = (gt % tiles) * kCeCols + lane;
+  const int64_t j = (gt % tiles) * kChainCols + lane;
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc, plane = n_groups * ldc;
   const int64_t id = g * ldc + j;
   const int32_t b = g_off[g];
@@ -80,11 +68,8 @@ __global__ __launch_bounds__(256) void k_ce_lags(CeView v, int64_t n, int64_t h,
   const int32_t* list = g_list + b;
   // the column's state: padding, a non-finite entry in a chain of the group and an empty group are done here
   bool ok = j < ldc && M > 0;
-  if (ok) {
-    const int64_t c0 = list[0];  // the group's chains have one npar (the host checked)
-    ok = j < v.ld ? j < (v.npar ? (int64_t)v.npar[c0] : v.ld) : v.s2 != nullptr;
-  }
-  for (int64_t k = 0; ok && k < M; ++k) ok = mo.state[(int64_t)list[k] * ldc + j] == CR_OK;
+  if (ok) ok = chain_live(v, list[0], j);  // the group's chains have one npar (the host checked)
+  for (int64_t k = 0; ok && k < M; ++k) ok = mo.state[(int64_t)list[k] * ldc + j] == COL_OK;
   bool live = ok && L >= 2;
   double W = 0.0, vplus = 0.0;
   if (live) {
@@ -94,74 +79,49 @@ __global__ __launch_bounds__(256) void k_ce_lags(CeView v, int64_t n, int64_t h,
     const double T = m >= 2 ? dv / (double)(m - 1) : 0.0;
     vplus = ((double)(L - 1) / (double)L) * W + T;
   } else if (wave == 0 && j < ldc) {
-    out_d[split * plane + id] = cr_nan();
-    out_d[(2 + split) * plane + id] = cr_nan();
-    if (!split) out_d[4 * plane + id] = cr_nan();
+    out_d[split * plane + id] = qnan();
+    out_d[(2 + split) * plane + id] = qnan();
+    if (!split) out_d[4 * plane + id] = qnan();
     out_w[split * plane + id] = ok ? 0 : -1;  // L < 2: a column, with no lag to sum
   }
   bool any = __ballot(live) != 0;  // every wavefront holds the same 64 columns: the same answer in all four
   // Geyer's running state (wavefront 0)
   double Q = 0.0, sum = 0.0;
-  for (int64_t k0 = 0; any && k0 <= K; k0 += kCeKT) {
-    double a_k[kCeLW];
+  for (int64_t k0 = 0; any && k0 <= K; k0 += kLagKT) {
+    double a_k[kLagLW];
 #pragma unroll
-    for (int k = 0; k < kCeLW; ++k) a_k[k] = 0.0;
+    for (int k = 0; k < kLagLW; ++k) a_k[k] = 0.0;
     for (int64_t sq = 0; sq < m; ++sq) {
       const int64_t c = list[sq / nq];
       const int64_t r0 = split && (sq & 1) ? n - h : 0;
       const double muj = live ? mo.mu[(int64_t)(q0 + (int)(sq % nq)) * ncol + c * ldc + j] : 0.0;
-      const double* col = !live ? nullptr : j < v.ld ? v.chain + (r0 * v.n_chains + c) * v.ld + j
-                                                    : v.s2 + r0 * v.n_chains + c;
-      const int64_t rs = j < v.ld ? v.n_chains * v.ld : v.n_chains;
-      double acc[kCeLW];
+      const ChainCol col = chain_col(v, c, j, live);
+      const double* seq = live ? col.ptr + r0 * col.rs : nullptr;
+      // row t of the sequence, centred; 0 past its end: the sum is linear, not circular
+      auto y = [&](int64_t t) { return live && t < L ? seq[t * col.rs] - muj : 0.0; };
+      double acc[kLagLW];
 #pragma unroll
-      for (int k = 0; k < kCeLW; ++k) acc[k] = 0.0;
-      for (int64_t t0 = 0; t0 < L - k0; t0 += kCeRT) {  // a row t >= L - k0 has no partner t + k < L, k >= k0
-        __syncthreads();  // the previous tile (or the previous lag tile's a(k)) has been read
-        for (int i = wave; i < kCeRT; i += 4) {
-          const int64_t t = t0 + i;
-          A[i * kCeCols + lane] = live && t < L ? col[t * rs] - muj : 0.0;
-        }
-        for (int r = wave; r < kCeBRows; r += 4) {
-          const int64_t t = t0 + k0 + r;
-          B[r * kCeCols + lane] = live && t < L ? col[t * rs] - muj : 0.0;
-        }
-        __syncthreads();
-        if (live) {
+      for (int k = 0; k < kLagLW; ++k) acc[k] = 0.0;
+      for (int64_t t0 = 0; t0 < L - k0; t0 += kLagRT)  // a row t >= L - k0 has no partner t + k < L, k >= k0
+        lag_tile(A, B, lane, wave, live, t0, t0 + k0, y, y, acc);
 #pragma unroll
-          for (int ib = 0; ib < kCeRT; ib += kCeLW) {
-            double a[kCeLW], bb[2 * kCeLW - 1];
-#pragma unroll
-            for (int u = 0; u < kCeLW; ++u) a[u] = A[(ib + u) * kCeCols + lane];
-#pragma unroll
-            for (int u = 0; u < 2 * kCeLW - 1; ++u) bb[u] = B[(ib + kCeLW * wave + u) * kCeCols + lane];
-#pragma unroll
-            for (int i = 0; i < kCeLW; ++i)  // rows in order: lag k sums y[t] * y[t + k] over increasing t
-#pragma unroll
-              for (int k = 0; k < kCeLW; ++k) acc[k] = fma(a[i], bb[i + k], acc[k]);
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kCeLW; ++k) a_k[k] += acc[k] / (double)L;
+      for (int k = 0; k < kLagLW; ++k) a_k[k] += acc[k] / (double)L;
     }
-    __syncthreads();
-    if (live)
 #pragma unroll
-      for (int k = 0; k < kCeLW; ++k) B[(kCeLW * wave + k) * kCeCols + lane] = a_k[k] / (double)m;
-    __syncthreads();
+    for (int k = 0; k < kLagLW; ++k) a_k[k] = a_k[k] / (double)m;
+    lag_hand(B, lane, wave, live, a_k);
     if (wave == 0) {
       if (live) {
         bool fin = false, stopped = false;
         int64_t s = 0;
-        for (int ii = 0; ii < kCeKT / 2; ++ii) {
+        for (int ii = 0; ii < kLagKT / 2; ++ii) {
           const int64_t i = k0 / 2 + ii;
           if (2 * i + 1 > K) {  // the pairs ran out
             s = i;
             fin = true;
             break;
           }
-          const double ae = B[(2 * ii) * kCeCols + lane], ao = B[(2 * ii + 1) * kCeCols + lane];
+          const double ae = B[(2 * ii) * kChainCols + lane], ao = B[(2 * ii + 1) * kChainCols + lane];
           const double re = i == 0 ? 1.0 : 1.0 - (W - ae) / vplus;
           const double ro = 1.0 - (W - ao) / vplus;
           const double P = re + ro;
@@ -178,16 +138,16 @@ __global__ __launch_bounds__(256) void k_ce_lags(CeView v, int64_t n, int64_t h,
           Q = P < Q ? P : Q;  // a NaN Q_0 stays
           sum += Q;
         }
-        if (!fin && k0 + kCeKT + 1 > K) {  // the next tile's first pair is past K
-          s = k0 / 2 + kCeKT / 2;
+        if (!fin && k0 + kLagKT + 1 > K) {  // the next tile's first pair is past K
+          s = k0 / 2 + kLagKT / 2;
           fin = true;
         }
         if (fin) {
           const bool capped = !stopped && K < L - 1;
-          const double tau = capped ? ce_inf() : -1.0 + 2.0 * sum;
+          const double tau = capped ? pinf() : -1.0 + 2.0 * sum;
           const double cp = cap[split * n_groups + g];
           const double q = (double)(m * L) / tau;
-          const double ess = tau != tau ? cr_nan() : tau > 0.0 ? (q < cp ? q : cp) : cp;
+          const double ess = tau != tau ? qnan() : tau > 0.0 ? (q < cp ? q : cp) : cp;
           out_d[split * plane + id] = ess;
           out_d[(2 + split) * plane + id] = tau;
           if (!split) out_d[4 * plane + id] = rhat_out[3 * plane + id] / sqrt(ess);
@@ -195,9 +155,7 @@ __global__ __launch_bounds__(256) void k_ce_lags(CeView v, int64_t n, int64_t h,
           live = false;
         }
       }
-      s_live[lane] = live;
-      const bool a2 = __ballot(live) != 0;
-      if (lane == 0) s_any = a2;
+      lag_publish(s_live, &s_any, lane, live);
     }
     __syncthreads();
     live = s_live[lane] != 0;
@@ -218,12 +176,13 @@ int launch_chainess(const double* chain, const double* s2, int64_t n_rows, int64
   CeMoments mo;
   rc = chainrhat_scratch_moments(scratch, n_rows, n_chains, ld, n_groups, &mo.mu, &mo.var, &mo.state);
   if (rc != TCI_OK) return rc;
-  const int64_t tiles = (ld + 1 + kCeCols - 1) / kCeCols;
+  const int64_t tiles = (ld + 1 + kChainCols - 1) / kChainCols;
   if ((long double)n_groups * tiles * 2 > 2147483647.0L) return TCI_ERANGE;
-  if (ensure_dyn_lds((const void*)k_ce_lags, kCeLds) != TCI_OK) return TCI_EHIP;
-  const CeView v{chain, s2, npar, n_chains, ld};
-  hipLaunchKernelGGL(k_ce_lags, dim3((unsigned)(n_groups * tiles * 2)), dim3(256), kCeLds, (hipStream_t)stream, v,
-                     n_rows, n_rows / 2, max_lag, (int)tiles, n_groups, g_off, g_list, mo, cap, rhat_out, out_d, out_w);
+  if (ensure_dyn_lds((const void*)k_ce_lags, kLagLds) != TCI_OK) return TCI_EHIP;
+  const ChainView v{chain, s2, npar, n_chains, ld};
+  hipLaunchKernelGGL(k_ce_lags, dim3((unsigned)(n_groups * tiles * 2)), dim3(kChainThreads), kLagLds,
+                     (hipStream_t)stream, v, n_rows, n_rows / 2, max_lag, (int)tiles, n_groups, g_off, g_list, mo, cap,
+                     rhat_out, out_d, out_w);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 

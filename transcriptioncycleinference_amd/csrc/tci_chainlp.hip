@@ -21,6 +21,7 @@
 
 #include <cmath>
 
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_prior.h"
 
@@ -32,12 +33,6 @@ constexpr int kLpSeg = 256;      // rows per segment
 constexpr int kLpWaves = 4;      // k_chainlp_rows: (row, chain) pairs per workgroup, one per wavefront
 constexpr int kLpThreads = 256;
 constexpr int kLpSegVals = 4;    // doubles a segment stores: sum ss (pass 2: the centred squares), sum dev, min ss, max lp
-
-__device__ __forceinline__ double lp_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-// x - x is 0 for a finite x and NaN for NaN and +-Inf: the library is built without any fast-math flag (build.py),
-// so the compiler may not fold it (the test tci_chaincov.hip and tci_chainrhat.hip use)
-__device__ __forceinline__ bool lp_finite(double x) { return (x - x) == 0.0; }
 
 // dev of include/tci.h: ss / s2 + nobs * log(2 pi s2), every operation rounded once
 __device__ __forceinline__ double lp_deviance(double ss, double s2, double nobs) {
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(kLpThreads) void k_chainlp_reduce(
     for (int i = 0; i < nr; ++i) {
       const int64_t e = (r0 + i) * nc + c;
       const double x = ss[e], p = pri[e], d = dev[e], l = lp[e];
-      bad |= !lp_finite(x) | !lp_finite(p) | !lp_finite(d);
+      bad |= !is_finite(x) | !is_finite(p) | !is_finite(d);
       a_ss += x;
       a_dev += d;
       mn = x < mn ? x : mn;
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(kLpThreads) void k_chainlp_reduce(
   }
   __syncthreads();
   const int64_t best = sh_best;
-  const double nan = lp_nan();
+  const double nan = qnan();
   if (best < 0) {  // the whole workgroup: every reduced output of the chain is NaN
     for (int k = tid; k < kChainlpScalars; k += kLpThreads) scal[k * nc + c] = nan;
     for (int64_t j = tid; j < ld; j += kLpThreads) {

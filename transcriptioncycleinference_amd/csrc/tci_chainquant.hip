@@ -1,11 +1,9 @@
 // tci_chainquant.hip -- exact posterior quantiles of every chain column (mcmcstat's plims), selected on the
 // device; the definition is in include/tci.h.
 //
-// The chain lies as [rows][n_chains][ld], contiguous along the parameter; a chain's s2 is column ld. One
-// workgroup (4 wavefronts) takes 64 consecutive columns of one chain, lane l of every wavefront column 64 t + l,
-// so a row read is one 512 B segment. The wavefronts split the rows (wavefront w the blocks of kCqRU rows
-// w, w + 4, ..): they only count, and integer counts do not depend on the order of the rows, so the result is
-// the same however the rows are split.
+// One workgroup (4 wavefronts) takes a column tile of one chain (tci_chain_dev.h). The wavefronts split the rows
+// (wavefront w the blocks of kChainRU rows w, w + 4, ..): they only count, and integer counts do not depend on the
+// order of the rows, so the result is the same however the rows are split.
 //
 // An order statistic is found by an MSB-first radix selection on the 64-bit keys of tci_key.h, 8 bits a pass:
 //   count  every key that matches the lane's prefix adds 1 to tab[next byte][lane] (an LDS table of 256 x 64
@@ -26,6 +24,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "tci_chain_dev.h"
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_key.h"
 
@@ -33,19 +33,9 @@ namespace tci {
 
 namespace {
 
-constexpr int kCqCols = 64;    // columns per workgroup: one per lane
-constexpr int kCqWaves = 4;    // wavefronts per workgroup, each counting its share of the rows
-constexpr int kCqRU = 8;       // rows a wavefront loads together; the workgroup advances kCqWaves * kCqRU rows
 constexpr int kCqBins = 256;   // 8 bits per pass
 constexpr int kCqDepth = 8;    // passes that make a 64-bit key
 constexpr int kCqRanks = 32;   // lo and lo + 1 of 16 probs
-
-struct CqView {
-  const double* chain;  // [rows][n_chains][ld]
-  const double* s2;     // [rows][n_chains] or null
-  const int32_t* npar;  // [n_chains] or null
-  int64_t n_chains, ld;
-};
 
 struct CqArgs {
   int32_t nq, n_ranks;
@@ -54,23 +44,20 @@ struct CqArgs {
   double f[16];
 };
 
-__device__ __forceinline__ double cq_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
 // out: [n_chains][nq][ld + 1]
-__global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int64_t n, int tiles, CqArgs a,
-                                                                    double* __restrict__ out) {
-  __shared__ uint32_t tab[kCqBins * kCqCols];                     // [bin][lane]
-  __shared__ uint32_t stk_lo[kCqDepth * kCqCols], stk_hi[kCqDepth * kCqCols];  // [depth][lane]: ranks of the bucket
-  __shared__ uint64_t red_mn[kCqWaves * kCqCols], red_mx[kCqWaves * kCqCols];
-  __shared__ uint32_t red_bad[kCqWaves * kCqCols];
+__global__ __launch_bounds__(kChainThreads) void k_cq_select(ChainView v, int64_t n, int tiles, CqArgs a,
+                                                             double* __restrict__ out) {
+  __shared__ uint32_t tab[kCqBins * kChainCols];                     // [bin][lane]
+  __shared__ uint32_t stk_lo[kCqDepth * kChainCols], stk_hi[kCqDepth * kChainCols];  // [depth][lane]: the bucket's ranks
+  __shared__ uint64_t red_mn[kChainWaves * kChainCols], red_mx[kChainWaves * kChainCols];
+  __shared__ uint32_t red_bad[kChainWaves * kChainCols];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t c = blockIdx.x / tiles;
-  const int64_t j = (int64_t)(blockIdx.x % tiles) * kCqCols + lane;
+  const int64_t j = (int64_t)(blockIdx.x % tiles) * kChainCols + lane;
   const int64_t ldc = v.ld + 1;
   const bool in_out = j < ldc;
-  bool live = j < v.ld ? j < (v.npar ? (int64_t)v.npar[c] : v.ld) : (j == v.ld && v.s2 != nullptr);
-  const double* col = !live ? nullptr : j < v.ld ? v.chain + c * v.ld + j : v.s2 + c;
-  const int64_t rs = j < v.ld ? v.n_chains * v.ld : v.n_chains;
+  bool live = chain_live(v, c, j);
+  const ChainCol col = chain_col(v, c, j, live);
   double* outc = out + c * a.nq * ldc + j;
   const uint32_t nn = (uint32_t)n;
 
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int6
       __syncthreads();  // wavefront 0 wrote the last path
 #pragma unroll
       for (int d = 0; d < kCqDepth; ++d) {
-        const uint32_t lo = stk_lo[d * kCqCols + lane], hi = stk_hi[d * kCqCols + lane];
+        const uint32_t lo = stk_lo[d * kChainCols + lane], hi = stk_hi[d * kChainCols + lane];
         if (depth == d && t >= lo && t < hi) {
           depth = d + 1;
           base = lo;
@@ -101,38 +88,38 @@ __global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int6
       if (__ballot(mine) == 0) continue;  // the same in all four wavefronts: their state is the same
       const int shift = 56 - 8 * d;
       __syncthreads();  // the last walk is over
-      for (int b = wave; b < kCqBins; b += kCqWaves) tab[b * kCqCols + lane] = 0;
+      for (int b = wave; b < kCqBins; b += kChainWaves) tab[b * kChainCols + lane] = 0;
       __syncthreads();
       uint64_t mn = ~0ull, mx = 0;
       bool bad = false;
-      for (int64_t r0 = (int64_t)wave * kCqRU; r0 < n; r0 += kCqWaves * kCqRU) {
-        double x[kCqRU];
+      for (int64_t r0 = (int64_t)wave * kChainRU; r0 < n; r0 += kChainWaves * kChainRU) {
+        double x[kChainRU];
 #pragma unroll
-        for (int u = 0; u < kCqRU; ++u) x[u] = (mine && r0 + u < n) ? col[(r0 + u) * rs] : 0.0;
+        for (int u = 0; u < kChainRU; ++u) x[u] = (mine && r0 + u < n) ? col.ptr[(r0 + u) * col.rs] : 0.0;
 #pragma unroll
-        for (int u = 0; u < kCqRU; ++u) {
+        for (int u = 0; u < kChainRU; ++u) {
           const uint64_t k = to_key(x[u]);
-          bad |= (x[u] - x[u]) != 0.0;
+          bad |= !is_finite(x[u]);
           const bool m = mine && r0 + u < n && (d == 0 || ((k ^ prefix) >> (shift + 8)) == 0);
           if (m) {
-            atomicAdd(&tab[(int)((k >> shift) & 255) * kCqCols + lane], 1u);
+            atomicAdd(&tab[(int)((k >> shift) & 255) * kChainCols + lane], 1u);
             mn = k < mn ? k : mn;
             mx = k > mx ? k : mx;
           }
         }
       }
-      red_mn[wave * kCqCols + lane] = mn;
-      red_mx[wave * kCqCols + lane] = mx;
-      red_bad[wave * kCqCols + lane] = bad ? 1u : 0u;
+      red_mn[wave * kChainCols + lane] = mn;
+      red_mx[wave * kChainCols + lane] = mx;
+      red_bad[wave * kChainCols + lane] = bad ? 1u : 0u;
       __syncthreads();
       // every wavefront walks for itself: the same counters, the same state
       uint32_t anybad = 0;
 #pragma unroll
-      for (int w = 0; w < kCqWaves; ++w) {
-        const uint64_t m0 = red_mn[w * kCqCols + lane], m1 = red_mx[w * kCqCols + lane];
+      for (int w = 0; w < kChainWaves; ++w) {
+        const uint64_t m0 = red_mn[w * kChainCols + lane], m1 = red_mx[w * kChainCols + lane];
         mn = m0 < mn ? m0 : mn;
         mx = m1 > mx ? m1 : mx;
-        anybad |= red_bad[w * kCqCols + lane];
+        anybad |= red_bad[w * kChainCols + lane];
       }
       if (mine && d == 0 && i == 0 && anybad) {  // a non-finite value: every quantile of the column is NaN
         live = false;
@@ -142,8 +129,8 @@ __global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int6
         active = false;
         if (wave == 0)
           for (int e = d; e < kCqDepth; ++e) {
-            stk_lo[e * kCqCols + lane] = base;
-            stk_hi[e * kCqCols + lane] = base + cnt;
+            stk_lo[e * kChainCols + lane] = base;
+            stk_hi[e * kChainCols + lane] = base + cnt;
           }
       } else {
         uint32_t cum = base, blo = 0, bhi = 0;
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int6
         bool found = false;
 #pragma unroll 8
         for (int b = 0; b < kCqBins; ++b) {
-          const uint32_t cb = tab[b * kCqCols + lane];
+          const uint32_t cb = tab[b * kChainCols + lane];
           const bool here = !found && t - cum < cb;  // cum <= t always
           if (here) {
             found = true;
@@ -167,8 +154,8 @@ __global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int6
           cnt = bhi - blo;
           depth = d + 1;
           if (wave == 0) {
-            stk_lo[d * kCqCols + lane] = blo;
-            stk_hi[d * kCqCols + lane] = bhi;
+            stk_lo[d * kChainCols + lane] = blo;
+            stk_hi[d * kChainCols + lane] = bhi;
           }
           if (d == kCqDepth - 1) {
             cur = prefix;
@@ -190,7 +177,7 @@ __global__ __launch_bounds__(kCqCols * kCqWaves) void k_cq_select(CqView v, int6
           if (lo != t) continue;
           r = from_key(cur);
         }
-        outc[q * ldc] = live ? r : cq_nan();
+        outc[q * ldc] = live ? r : qnan();
       }
     }
   }
@@ -203,7 +190,7 @@ int launch_chainquant(const double* chain, const double* s2, int64_t n_rows, int
   if (!chain || !probs || !out || n_rows < 1 || n_rows > ((int64_t)1 << 30) || n_chains < 1 || ld < 1 ||
       ld > ((int64_t)1 << 24) || nq < 1 || nq > 16)
     return TCI_EINVAL;
-  const int64_t tiles = (ld + 1 + kCqCols - 1) / kCqCols;
+  const int64_t tiles = (ld + 1 + kChainCols - 1) / kChainCols;
   if (n_chains > ((int64_t)1 << 30) / tiles) return TCI_EINVAL;
   CqArgs a{};
   a.nq = nq;
@@ -221,8 +208,8 @@ int launch_chainquant(const double* chain, const double* s2, int64_t n_rows, int
   std::sort(ranks, ranks + nr);
   a.n_ranks = (int32_t)(std::unique(ranks, ranks + nr) - ranks);
   for (int k = 0; k < a.n_ranks; ++k) a.rank[k] = ranks[k];
-  const CqView v{chain, s2, npar, n_chains, ld};
-  hipLaunchKernelGGL(k_cq_select, dim3((unsigned)(n_chains * tiles)), dim3(kCqCols * kCqWaves), 0, (hipStream_t)stream,
+  const ChainView v{chain, s2, npar, n_chains, ld};
+  hipLaunchKernelGGL(k_cq_select, dim3((unsigned)(n_chains * tiles)), dim3(kChainThreads), 0, (hipStream_t)stream,
                      v, n_rows, (int)tiles, a, out);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }

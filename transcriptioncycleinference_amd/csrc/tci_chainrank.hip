@@ -3,10 +3,10 @@
 // columns, written as chains of the chain's own layout so that launch_chainrhat / launch_chainess reduce them
 // unchanged; the definition is in include/tci.h.
 //
-// The chain lies as [rows][n_chains][ld]; a chain's s2 is column ld. One workgroup (8 wavefronts) takes one
-// (group, column): the N = M n values of the group's chains, chains ascending, rows [0, n).
+// One workgroup (8 wavefronts) takes one (group, column) of the chain (tci_chain_dev.h): the N = M n values of the
+// group's chains, chains ascending, rows [0, n).
 //   gather   element i = m n + r is row r of the group's m-th chain; its key is tci_key.h's 64-bit total order
-//            (mode 1: of |x - med|). A value with (x - x) != 0 flags the column: everything it writes is NaN.
+//            (mode 1: of |x - med|). A non-finite value flags the column: everything it writes is NaN.
 //   sort     keys only, by one bitonic network in its all-ascending form (the first stage of a merge of blocks
 //            of k pairs i with its mirror image i ^ (k - 1), the later stages i with i + j): every comparator
 //            leaves the smaller key at the lower index, so the network sorts any N when the indices >= N are
@@ -28,6 +28,8 @@
 
 #include <cmath>
 
+#include "tci_chain_dev.h"
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_key.h"
 
@@ -39,20 +41,11 @@ constexpr int kCkThreads = 512;
 constexpr int kCkLog2Cap = 13;
 static_assert(kRankLdsCap == (1 << kCkLog2Cap), "the LDS tile is a power of two");
 
-struct CkView {
-  const double* chain;  // [rows][n_chains][ld]
-  const double* s2;     // [rows][n_chains] or null
-  const int32_t* npar;  // [n_chains] or null
-  int64_t n_chains, ld;
-};
-
 struct CkArgs {
   int32_t nq;
   double probs[16];
   double tail[2];
 };
-
-__device__ __forceinline__ double ck_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // Wichura's AS241 PPND16 as CPython's statistics._normal_dist_inv_cdf(p, 0.0, 1.0) writes it.
 __device__ double ck_ppnd16(double p) {
@@ -138,7 +131,7 @@ struct CkCol {
 // mode 0: ranks of x, and the pooled quantiles into qbuf; mode 1: ranks of |x - med|; mode 2, 3: the indicator
 // x <= q_lo, x <= q_hi. qbuf: [n_groups][nq + 3][ld + 1] = probs' quantiles, then med, q_lo, q_hi. zc, zs2: the
 // transformed chain, laid out as the chain. gkeys: n_blocks slabs of gstride keys (the global path; null without).
-__global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int mode, int lp_lds,
+__global__ __launch_bounds__(kCkThreads) void k_ck_rank(ChainView v, int64_t n, int mode, int lp_lds,
                                                          const int32_t* __restrict__ g_off,
                                                          const int32_t* __restrict__ g_list, CkArgs a,
                                                          double* __restrict__ qbuf, uint64_t* __restrict__ gkeys,
@@ -152,10 +145,11 @@ __global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int
   const int64_t M = g_off[g + 1] - b0;
   if (M < 1) return;
   const int32_t* list = g_list + b0;
-  if (j < v.ld ? j >= (v.npar ? (int64_t)v.npar[list[0]] : v.ld) : v.s2 == nullptr) return;  // padding: stays NaN
+  if (!chain_live(v, list[0], j)) return;  // padding: stays NaN
   const int64_t N = M * n;
   const bool s2col = j == v.ld;
-  const CkCol col{s2col ? v.s2 : v.chain + j, s2col ? 1 : v.ld, s2col ? v.n_chains : v.n_chains * v.ld, list, n};
+  const ChainCol col0 = chain_col(v, 0, j, true);
+  const CkCol col{col0.ptr, s2col ? 1 : v.ld, col0.rs, list, n};
   double* const zout = s2col ? zs2 : zc + j;  // the same strides
   const int nqq = a.nq + 3;
   double* const qg = qbuf + (g * nqq) * ldc + j;
@@ -164,7 +158,7 @@ __global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int
     const double q = qg[(a.nq + mode - 1) * ldc];
     for (int64_t i = tid; i < N; i += kCkThreads) {
       const int64_t o = col.at(i);
-      zout[o] = q != q ? ck_nan() : (col.base[o] <= q ? 1.0 : 0.0);
+      zout[o] = q != q ? qnan() : (col.base[o] <= q ? 1.0 : 0.0);
     }
     return;
   }
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int
       uint64_t k = ~0ull;
       if (i < N) {
         const double x = value(i);
-        bad |= (x - x) != 0.0;
+        bad |= !is_finite(x);
         k = to_key(x);
       }
       ck_lds[i] = k;
@@ -200,7 +194,7 @@ __global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int
         uint64_t k = ~0ull;
         if (t0 + i < N) {
           const double x = value(t0 + i);
-          bad |= (x - x) != 0.0;
+          bad |= !is_finite(x);
           k = to_key(x);
         }
         ck_lds[i] = k;
@@ -255,13 +249,13 @@ __global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int
     } else {
       r = from_key(sorted[N - 1]);
     }
-    qg[tid * ldc] = bad ? ck_nan() : r;
+    qg[tid * ldc] = bad ? qnan() : r;
   }
 
   const double den = (double)(2 * N) + 0.5;
   for (int64_t i = tid; i < N; i += kCkThreads) {
     const int64_t o = col.at(i);
-    double z = ck_nan();
+    double z = qnan();
     if (!bad) {
       const double x = col.base[o];
       const uint64_t k = to_key(mode == 1 ? fabs(x - med) : x);
@@ -287,7 +281,7 @@ __global__ __launch_bounds__(kCkThreads) void k_ck_rank(CkView v, int64_t n, int
 
 // The quiet NaN the other reductions write, in every entry.
 __global__ __launch_bounds__(256) void k_ck_fill(double* __restrict__ p, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = ck_nan();
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = qnan();
 }
 
 }  // namespace
@@ -340,7 +334,7 @@ int launch_chainrank(const double* chain, const double* s2, int64_t n_rows, int6
   for (int q = 0; q < nq; ++q) a.probs[q] = probs[q];
   a.tail[0] = tail_lo;
   a.tail[1] = tail_hi;
-  const CkView v{chain, s2, npar, n_chains, ld};
+  const ChainView v{chain, s2, npar, n_chains, ld};
   hipLaunchKernelGGL(k_ck_rank, dim3((unsigned)(n_groups * (ld + 1))), dim3(kCkThreads), lds, (hipStream_t)stream, v,
                      n_rows, mode, lp, g_off, g_list, a, qbuf, (uint64_t*)gkeys, stride, zc, zs2);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;

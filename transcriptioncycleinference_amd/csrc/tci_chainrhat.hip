@@ -2,19 +2,15 @@
 // posterior mean and standard deviation of every group of chains, reduced on the device; the definition is in
 // include/tci.h.
 //
-// The chain lies as [rows][n_chains][ld], contiguous along the parameter; a chain's s2 is column ld. The layout
-// is tci_chaindens.hip's: one workgroup (4 wavefronts) takes 64 consecutive columns of one chain, lane l of every
-// wavefront column 64 t + l, so a row read is one 512 B segment. The rows are cut into segments of kCrSeg rows; a
-// workgroup takes one segment of its 64 columns. The segment count and boundaries follow from n_rows alone, every
-// partial result of a segment is stored, and the per-column kernels add the partials in segment order: an output's
-// bits do not depend on how many workgroups ran, nor on where a chain sits.
+// One workgroup (4 wavefronts) takes one segment of a column tile of one chain (tci_chain_dev.h); the per-column
+// kernels add the segments' partials in segment order.
 //
 // Per chain column three sequences are reduced: q = 0 the whole chain, rows [0, n); q = 1 half A, rows [0, h);
 // q = 2 half B, rows [n - h, n); h = floor(n / 2).
 //
 //   k_cr_pass1   per segment: the three compensated sums (a row goes to the sequences it belongs to), the
 //                non-finite flag and, per sequence, whether a row differs from the sequence's first. The wavefronts
-//                split the rows (wavefront w the blocks of kCrRU rows w, w + 4, ..) and are combined in order.
+//                split the rows (seg_walk) and are combined in order.
 //   k_cr_mean    per column: the segments combined; the three means and the column's state.
 //   k_cr_pass2   per segment: the three centred sums of squares.
 //   k_cr_var     per column: the segments combined; the three variances.
@@ -26,87 +22,50 @@
 
 #include <cmath>
 
+#include "tci_chain_dev.h"
 #include "tci_chainrhat_dev.h"
 #include "tci_csum.h"
+#include "tci_fp.h"
 #include "tci_internal.h"
 
 namespace tci {
 
 namespace {
 
-constexpr int kCrCols = 64;   // columns per workgroup: one per lane
-constexpr int kCrWaves = 4;   // wavefronts per workgroup
-constexpr int kCrRU = 8;      // rows a wavefront loads together
-constexpr int kCrSeg = 256;   // rows per segment
-constexpr int kCrThreads = kCrCols * kCrWaves;
-
 enum : uint32_t { CR_F_BAD = 1u };  // bit 1 + q: sequence q is not constant
 
-struct CrView {
-  const double* chain;   // [rows][n_chains][ld]
-  const double* s2;      // [rows][n_chains] or null
-  const int32_t* npar;   // [n_chains] or null
-  const int32_t* group;  // [n_chains]; < 0: the chain belongs to no group
-  int64_t n_chains, ld;
-};
-
-__device__ __forceinline__ bool cr_live(const CrView& v, int64_t c, int64_t j) {
-  return j < v.ld ? j < (v.npar ? (int64_t)v.npar[c] : v.ld) : (j == v.ld && v.s2 != nullptr);
-}
-
-// The workgroup's chain, column and segment: blockIdx.x = (chain * tiles + tile) * S + segment.
-struct CrWhere {
-  int64_t c, j, r0;
-  int nr, seg;
-};
-__device__ __forceinline__ CrWhere cr_where(int64_t n, int tiles, int S, int lane) {
-  CrWhere w;
-  const int64_t ct = (int64_t)blockIdx.x / S;
-  w.seg = (int)((int64_t)blockIdx.x % S);
-  w.c = ct / tiles;
-  w.j = (ct % tiles) * kCrCols + lane;
-  w.r0 = (int64_t)w.seg * kCrSeg;
-  w.nr = (int)(n - w.r0 < kCrSeg ? n - w.r0 : kCrSeg);
-  return w;
-}
-
-__global__ __launch_bounds__(kCrThreads) void k_cr_pass1(CrView v, int64_t n, int64_t h, int tiles, int S,
-                                                          CrScratch sc) {
-  __shared__ double r_s[kCrSeq][kCrThreads], r_c[kCrSeq][kCrThreads];
-  __shared__ uint32_t r_f[kCrThreads];
+// group: [n_chains]; < 0: the chain belongs to no group.
+__global__ __launch_bounds__(kChainThreads) void k_cr_pass1(ChainView v, const int32_t* __restrict__ group, int64_t n,
+                                                            int64_t h, int tiles, int S, CrScratch sc) {
+  __shared__ double r_s[kCrSeq][kChainThreads], r_c[kCrSeq][kChainThreads];
+  __shared__ uint32_t r_f[kChainThreads];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const CrWhere w = cr_where(n, tiles, S, lane);
-  if (v.group[w.c] < 0) return;  // the whole workgroup
+  const SegWhere w = seg_where(n, tiles, S, lane);
+  if (group[w.c] < 0) return;  // the whole workgroup
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
-  const bool live = w.j < ldc && cr_live(v, w.c, w.j);
-  const double* col = !live ? nullptr : w.j < v.ld ? v.chain + w.c * v.ld + w.j : v.s2 + w.c;
-  const int64_t rs = w.j < v.ld ? v.n_chains * v.ld : v.n_chains;
+  const bool live = w.j < ldc && chain_live(v, w.c, w.j);
+  const ChainCol col = chain_col(v, w.c, w.j, live);
   // a sequence's first row: rows 0 (whole, half A) and n - h (half B; h == 0: there is no half)
-  const double f0 = live ? col[0] : 0.0;
-  const double fb = live && h > 0 ? col[(n - h) * rs] : 0.0;
+  const double f0 = live ? col.ptr[0] : 0.0;
+  const double fb = live && h > 0 ? col.ptr[(n - h) * col.rs] : 0.0;
   CSum cs[kCrSeq];
   uint32_t fl = 0;
-  for (int i0 = wave * kCrRU; i0 < w.nr; i0 += kCrWaves * kCrRU) {
-    double x[kCrRU];
-#pragma unroll
-    for (int u = 0; u < kCrRU; ++u) x[u] = (live && i0 + u < w.nr) ? col[(w.r0 + i0 + u) * rs] : 0.0;
-#pragma unroll
-    for (int u = 0; u < kCrRU; ++u)
-      if (live && i0 + u < w.nr) {
-        const int64_t r = w.r0 + i0 + u;
-        fl |= (x[u] - x[u]) != 0.0 ? CR_F_BAD : 0u;
-        cs[0].add(x[u]);
-        fl |= x[u] != f0 ? 2u : 0u;
-        if (r < h) {
-          cs[1].add(x[u]);
-          fl |= x[u] != f0 ? 4u : 0u;
-        }
-        if (r >= n - h) {
-          cs[2].add(x[u]);
-          fl |= x[u] != fb ? 8u : 0u;
-        }
+  seg_walk(col, w, wave, live, 0.0, [&](double x, int i) {
+    if (live && i < w.nr) {
+      const int64_t r = w.r0 + i;
+      fl |= !is_finite(x) ? CR_F_BAD : 0u;
+      cs[0].add(x);
+      fl |= x != f0 ? 2u : 0u;
+      if (r < h) {
+        cs[1].add(x);
+        fl |= x != f0 ? 4u : 0u;
       }
-  }
+      if (r >= n - h) {
+        cs[2].add(x);
+        fl |= x != fb ? 8u : 0u;
+      }
+    }
+  });
 #pragma unroll
   for (int q = 0; q < kCrSeq; ++q) {
     r_s[q][tid] = cs[q].s;
@@ -115,12 +74,11 @@ __global__ __launch_bounds__(kCrThreads) void k_cr_pass1(CrView v, int64_t n, in
   r_f[tid] = fl;
   __syncthreads();
   if (wave == 0 && w.j < ldc) {  // the wavefronts in order
-    for (int k = 1; k < kCrWaves; ++k) {
-      fl |= r_f[k * kCrCols + lane];
+    for (int k = 1; k < kChainWaves; ++k) {
+      fl |= r_f[k * kChainCols + lane];
 #pragma unroll
       for (int q = 0; q < kCrSeq; ++q) {
-        cs[q].add(r_s[q][k * kCrCols + lane]);
-        cs[q].c += r_c[q][k * kCrCols + lane];
+        cs[q].merge(r_s[q][k * kChainCols + lane], r_c[q][k * kChainCols + lane]);
       }
     }
     const int64_t e = w.c * ldc + w.j;
@@ -133,15 +91,16 @@ __global__ __launch_bounds__(kCrThreads) void k_cr_pass1(CrView v, int64_t n, in
   }
 }
 
-__global__ __launch_bounds__(kCrThreads) void k_cr_mean(CrView v, int64_t n, int64_t h, int S, CrScratch sc) {
+__global__ __launch_bounds__(kChainThreads) void k_cr_mean(ChainView v, const int32_t* __restrict__ group, int64_t n,
+                                                           int64_t h, int S, CrScratch sc) {
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
-  const int64_t e = (int64_t)blockIdx.x * kCrThreads + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
   if (e >= ncol) return;
   const int64_t c = e / ldc, j = e % ldc;
-  if (v.group[c] < 0) return;
-  const bool live = cr_live(v, c, j);
+  if (group[c] < 0) return;
+  const bool live = chain_live(v, c, j);
   if (!live) {
-    sc.state[e] = CR_PAD;
+    sc.state[e] = COL_PAD;
     return;
   }
   uint32_t fl = 0;
@@ -150,107 +109,100 @@ __global__ __launch_bounds__(kCrThreads) void k_cr_mean(CrView v, int64_t n, int
     fl |= sc.p_f[(int64_t)s * ncol + e];
 #pragma unroll
     for (int q = 0; q < kCrSeq; ++q) {
-      cs[q].add(sc.p_s[((int64_t)s * kCrSeq + q) * ncol + e]);
-      cs[q].c += sc.p_c[((int64_t)s * kCrSeq + q) * ncol + e];
+      cs[q].merge(sc.p_s[((int64_t)s * kCrSeq + q) * ncol + e], sc.p_c[((int64_t)s * kCrSeq + q) * ncol + e]);
     }
   }
   const bool bad = (fl & CR_F_BAD) != 0;
-  sc.state[e] = bad ? CR_BAD : CR_OK;
+  sc.state[e] = bad ? COL_BAD : COL_OK;
   if (bad) return;
-  const double* col = j < v.ld ? v.chain + c * v.ld + j : v.s2 + c;
-  const int64_t rs = j < v.ld ? v.n_chains * v.ld : v.n_chains;
-  const double f0 = col[0], fb = h > 0 ? col[(n - h) * rs] : 0.0;
+  const ChainCol col = chain_col(v, c, j, true);
+  const double f0 = col.ptr[0], fb = h > 0 ? col.ptr[(n - h) * col.rs] : 0.0;
   // a constant sequence is centred on its value exactly, as tci_chaincov does: its variance is exactly 0
   sc.mu[0 * ncol + e] = !(fl & 2u) ? f0 : cs[0].total() / (double)n;
   sc.mu[1 * ncol + e] = h < 1 ? 0.0 : !(fl & 4u) ? f0 : cs[1].total() / (double)h;
   sc.mu[2 * ncol + e] = h < 1 ? 0.0 : !(fl & 8u) ? fb : cs[2].total() / (double)h;
 }
 
-__global__ __launch_bounds__(kCrThreads) void k_cr_pass2(CrView v, int64_t n, int64_t h, int tiles, int S,
-                                                          CrScratch sc) {
-  __shared__ double r_s[kCrSeq][kCrThreads];
+__global__ __launch_bounds__(kChainThreads) void k_cr_pass2(ChainView v, const int32_t* __restrict__ group, int64_t n,
+                                                            int64_t h, int tiles, int S, CrScratch sc) {
+  __shared__ double r_s[kCrSeq][kChainThreads];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const CrWhere w = cr_where(n, tiles, S, lane);
-  if (v.group[w.c] < 0) return;  // the whole workgroup
+  const SegWhere w = seg_where(n, tiles, S, lane);
+  if (group[w.c] < 0) return;  // the whole workgroup
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
   const int64_t e = w.c * ldc + w.j;
-  const bool ok = w.j < ldc && sc.state[e] == CR_OK;
-  const double* col = !ok ? nullptr : w.j < v.ld ? v.chain + w.c * v.ld + w.j : v.s2 + w.c;
-  const int64_t rs = w.j < v.ld ? v.n_chains * v.ld : v.n_chains;
+  const bool ok = w.j < ldc && sc.state[e] == COL_OK;
+  const ChainCol col = chain_col(v, w.c, w.j, ok);
   double mu[kCrSeq], ss[kCrSeq];
 #pragma unroll
   for (int q = 0; q < kCrSeq; ++q) {
     mu[q] = ok ? sc.mu[q * ncol + e] : 0.0;
     ss[q] = 0.0;
   }
-  for (int i0 = wave * kCrRU; i0 < w.nr; i0 += kCrWaves * kCrRU) {
-    double x[kCrRU];
-#pragma unroll
-    for (int u = 0; u < kCrRU; ++u) x[u] = (ok && i0 + u < w.nr) ? col[(w.r0 + i0 + u) * rs] : 0.0;
-#pragma unroll
-    for (int u = 0; u < kCrRU; ++u)
-      if (ok && i0 + u < w.nr) {
-        const int64_t r = w.r0 + i0 + u;
-        const double d0 = x[u] - mu[0];
-        ss[0] += d0 * d0;
-        if (r < h) {
-          const double d = x[u] - mu[1];
-          ss[1] += d * d;
-        }
-        if (r >= n - h) {
-          const double d = x[u] - mu[2];
-          ss[2] += d * d;
-        }
+  seg_walk(col, w, wave, ok, 0.0, [&](double x, int i) {
+    if (ok && i < w.nr) {
+      const int64_t r = w.r0 + i;
+      const double d0 = x - mu[0];
+      ss[0] += d0 * d0;
+      if (r < h) {
+        const double d = x - mu[1];
+        ss[1] += d * d;
       }
-  }
+      if (r >= n - h) {
+        const double d = x - mu[2];
+        ss[2] += d * d;
+      }
+    }
+  });
 #pragma unroll
   for (int q = 0; q < kCrSeq; ++q) r_s[q][tid] = ss[q];
   __syncthreads();
   if (wave == 0 && w.j < ldc) {
 #pragma unroll
     for (int q = 0; q < kCrSeq; ++q) {
-      for (int k = 1; k < kCrWaves; ++k) ss[q] += r_s[q][k * kCrCols + lane];
+      for (int k = 1; k < kChainWaves; ++k) ss[q] += r_s[q][k * kChainCols + lane];
       sc.p_s[((int64_t)w.seg * kCrSeq + q) * ncol + e] = ss[q];
     }
   }
 }
 
-__global__ __launch_bounds__(kCrThreads) void k_cr_var(CrView v, int64_t n, int64_t h, int S, CrScratch sc) {
+__global__ __launch_bounds__(kChainThreads) void k_cr_var(ChainView v, const int32_t* __restrict__ group, int64_t n,
+                                                          int64_t h, int S, CrScratch sc) {
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
-  const int64_t e = (int64_t)blockIdx.x * kCrThreads + threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
   if (e >= ncol) return;
-  if (v.group[e / ldc] < 0 || sc.state[e] != CR_OK) return;
+  if (group[e / ldc] < 0 || sc.state[e] != COL_OK) return;
 #pragma unroll
   for (int q = 0; q < kCrSeq; ++q) {
     double ss = 0.0;
     for (int s = 0; s < S; ++s) ss += sc.p_s[((int64_t)s * kCrSeq + q) * ncol + e];
     const int64_t L = q == 0 ? n : h;
-    sc.var[q * ncol + e] = L < 2 ? cr_nan() : ss / (double)(L - 1);
+    sc.var[q * ncol + e] = L < 2 ? qnan() : ss / (double)(L - 1);
   }
 }
 
 __device__ __forceinline__ double cr_rhat(double sum_v, double dev, int64_t m, int64_t L) {
-  if (m < 2 || L < 2) return cr_nan();
+  if (m < 2 || L < 2) return qnan();
   const double W = sum_v / (double)m;
   const double T = dev / (double)(m - 1);
   return sqrt((double)(L - 1) / (double)L + T / W);
 }
 
 // out: [4][n_groups][ldc] = rhat, rhat_split, pooled_mean, pooled_std
-__global__ __launch_bounds__(kCrThreads) void k_cr_out(CrView v, int64_t n, int64_t h, int64_t n_groups,
-                                                        const int32_t* __restrict__ g_off,
-                                                        const int32_t* __restrict__ g_list, CrScratch sc,
-                                                        double* __restrict__ out) {
+__global__ __launch_bounds__(kChainThreads) void k_cr_out(ChainView v, int64_t n, int64_t h, int64_t n_groups,
+                                                          const int32_t* __restrict__ g_off,
+                                                          const int32_t* __restrict__ g_list, CrScratch sc,
+                                                          double* __restrict__ out) {
   const int64_t ldc = v.ld + 1, ncol = v.n_chains * ldc;
-  const int64_t id = (int64_t)blockIdx.x * kCrThreads + threadIdx.x;
+  const int64_t id = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
   if (id >= n_groups * ldc) return;
   const int64_t g = id / ldc, j = id % ldc;
   const int32_t b = g_off[g];
   const int64_t M = g_off[g + 1] - b;
   const int64_t plane = n_groups * ldc;
-  double r[4] = {cr_nan(), cr_nan(), cr_nan(), cr_nan()};
-  bool ok = M > 0 && cr_live(v, g_list[b], j);  // the group's chains have one npar (the host checked)
-  for (int64_t k = 0; ok && k < M; ++k) ok = sc.state[(int64_t)g_list[b + k] * ldc + j] == CR_OK;
+  double r[4] = {qnan(), qnan(), qnan(), qnan()};
+  bool ok = M > 0 && chain_live(v, g_list[b], j);  // the group's chains have one npar (the host checked)
+  for (int64_t k = 0; ok && k < M; ++k) ok = sc.state[(int64_t)g_list[b + k] * ldc + j] == COL_OK;
   if (ok) {
     double sv, mb, dv;
     cr_between(CrSeqs{sc.mu, sc.var, g_list + b, ldc, ncol, j, 0, 1}, M, &sv, &mb, &dv);
@@ -276,11 +228,11 @@ int cr_sizes(int64_t n_rows, int64_t n_chains, int64_t ld, int64_t n_groups, CrS
   if (n_rows < 1 || n_rows > ((int64_t)1 << 30) || n_chains < 1 || n_chains > ((int64_t)1 << 30) || ld < 1 ||
       ld > ((int64_t)1 << 24) || n_groups < 1 || n_groups > n_chains)
     return TCI_EINVAL;
-  z->S = (n_rows + kCrSeg - 1) / kCrSeg;  // <= 2^22
-  z->tiles = (ld + 1 + kCrCols - 1) / kCrCols;
+  z->S = (n_rows + kChainSeg - 1) / kChainSeg;  // <= 2^22
+  z->tiles = (ld + 1 + kChainCols - 1) / kChainCols;
   const long double lim = 2147483647.0L;
   const long double ncol = (long double)n_chains * (long double)(ld + 1);
-  if ((long double)n_chains * z->tiles * z->S > lim || ncol / kCrThreads + 1 > lim) return TCI_ERANGE;
+  if ((long double)n_chains * z->tiles * z->S > lim || ncol / kChainThreads + 1 > lim) return TCI_ERANGE;
   const long double i8 = (2.0L * kCrSeq * z->S + 2 * kCrSeq) * ncol;
   const long double i4 = ((long double)z->S + 1) * ncol;
   if (i8 * 8 + i4 * 4 > (long double)((size_t)1 << 46)) return TCI_ENOMEM;
@@ -337,18 +289,19 @@ int launch_chainrhat(const double* chain, const double* s2, int64_t n_rows, int6
   const int rc = cr_sizes(n_rows, n_chains, ld, n_groups, &z);
   if (rc != TCI_OK) return rc;
   const CrScratch sc = cr_carve(scratch, z);
-  const CrView v{chain, s2, npar, group, n_chains, ld};
+  const ChainView v{chain, s2, npar, n_chains, ld};
   const int64_t h = n_rows / 2;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 blk(kCrThreads), seg_grid((unsigned)z.blocks), col_grid((unsigned)((z.ncol + kCrThreads - 1) / kCrThreads));
+  const dim3 blk(kChainThreads), seg_grid((unsigned)z.blocks);
+  const dim3 col_grid((unsigned)((z.ncol + kChainThreads - 1) / kChainThreads));
   const int S = (int)z.S, tiles = (int)z.tiles;
-  hipLaunchKernelGGL(k_cr_pass1, seg_grid, blk, 0, st, v, n_rows, h, tiles, S, sc);
-  hipLaunchKernelGGL(k_cr_mean, col_grid, blk, 0, st, v, n_rows, h, S, sc);
-  hipLaunchKernelGGL(k_cr_pass2, seg_grid, blk, 0, st, v, n_rows, h, tiles, S, sc);
-  hipLaunchKernelGGL(k_cr_var, col_grid, blk, 0, st, v, n_rows, h, S, sc);
+  hipLaunchKernelGGL(k_cr_pass1, seg_grid, blk, 0, st, v, group, n_rows, h, tiles, S, sc);
+  hipLaunchKernelGGL(k_cr_mean, col_grid, blk, 0, st, v, group, n_rows, h, S, sc);
+  hipLaunchKernelGGL(k_cr_pass2, seg_grid, blk, 0, st, v, group, n_rows, h, tiles, S, sc);
+  hipLaunchKernelGGL(k_cr_var, col_grid, blk, 0, st, v, group, n_rows, h, S, sc);
   const int64_t out_items = n_groups * (ld + 1);
-  hipLaunchKernelGGL(k_cr_out, dim3((unsigned)((out_items + kCrThreads - 1) / kCrThreads)), blk, 0, st, v, n_rows, h,
-                     n_groups, g_off, g_list, sc, out);
+  hipLaunchKernelGGL(k_cr_out, dim3((unsigned)((out_items + kChainThreads - 1) / kChainThreads)), blk, 0, st, v, n_rows,
+                     h, n_groups, g_off, g_list, sc, out);
   return hipGetLastError() == hipSuccess ? TCI_OK : TCI_EHIP;
 }
 

@@ -1,5 +1,5 @@
 // tci_chainrhat_dev.h -- what the reductions across chains share (tci_chainrhat.hip, tci_chainess.hip): the scratch
-// of the per-sequence moments, a column's state and the between/within combination of a group's sequences. Both
+// of the per-sequence moments and the between/within combination of a group's sequences. Both
 // files take mu_j, s2_j, W, mubar and T from here, so both see the same bits.
 #pragma once
 
@@ -12,18 +12,14 @@ namespace {
 
 constexpr int kCrSeq = 3;  // sequences per chain column: whole, half A, half B
 
-enum : int32_t { CR_PAD = 0, CR_OK = 1, CR_BAD = 2 };
-
 // The scratch of one call, carved from one allocation (8-byte items first).
 struct CrScratch {
   double *p_s, *p_c;  // [S][kCrSeq][ncol] compensated sums (pass 1); p_s again: centred squares (pass 2)
   double* mu;         // [kCrSeq][ncol]
   double* var;        // [kCrSeq][ncol]
   uint32_t* p_f;      // [S][ncol] flags
-  int32_t* state;     // [ncol]
+  int32_t* state;     // [ncol] COL_PAD / COL_OK / COL_BAD (tci_chain_dev.h)
 };
-
-__device__ __forceinline__ double cr_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // The m sequences of one group column, in order: sequence k is sequence q0 + k % nq of the group's chain k / nq.
 struct CrSeqs {

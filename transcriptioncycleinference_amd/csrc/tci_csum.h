@@ -1,5 +1,5 @@
-// tci_csum.h -- the compensated column sum shared by the chain reductions (tci_chainstats.hip,
-// tci_chaincov.hip): both take a column's mean from it, so both centre a column on the same bits.
+// tci_csum.h -- the compensated column sum shared by the chain reductions: every one of them takes a column's
+// mean from it, so all centre a column on the same bits.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,11 @@ struct CSum {
     const double t = s + x;
     c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
     s = t;
+  }
+  // another sum's (s, c) joins this one: its s as one more term, its compensation as it is
+  __device__ __forceinline__ void merge(double s2, double c2) {
+    add(s2);
+    c += c2;
   }
   __device__ __forceinline__ double total() const { return s + c; }
 };

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "tci_fp.h"
 #include "tci_gamma.h"
 #include "tci_internal.h"
 #include "tci_prior.h"
@@ -48,8 +49,6 @@ constexpr uint32_t kPurposeIndex = 9, kPurposeCoord = 10, kPurposeAccept = 11, k
 static_assert(7 + TCI_MAX_POINTS <= 4096, "the coordinate counter of k_demc_propose");
 // a lane's crossing flags, one bit per stride of 64 coordinates
 static_assert((7 + TCI_MAX_POINTS + 63) / 64 <= 64, "the crossing mask of k_demc_propose");
-
-__device__ __forceinline__ double dm_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // m(w, n) of include/tci.h: a word scaled to [0, n)
 __device__ __forceinline__ uint32_t dm_scale(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * n) >> 32); }
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(kDmThreads) void k_demc_propose(
     tr[j] = tj;
   }
   const bool out = __ballot(oob) != 0;  // wave-uniform
-  double tot = dm_nan();
+  double tot = qnan();
   if (!out) tot = prior_sum64(tr, mu + (int64_t)k * ld, sig + (int64_t)k * ld, P, lane);  // its own stores, as above
   if (lane == 0) {
     pri[t] = tot;
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(kDmDecThreads) void k_demc_decide(
       const int64_t b = k * n_pop + i, t = k * n_mov + mi;
       const bool act = active[t] != 0;
       const double s2i = s2[b];
-      double ssi = ss[b], lr = dm_nan();
+      double ssi = ss[b], lr = qnan();
       bool take = false;
       if (act) {
         const double st = ss_t[t], pt = pri_t[t];

@@ -20,6 +20,7 @@
 // (20 KiB) and the wavefronts' maxima and flags.
 #include <hip/hip_runtime.h>
 
+#include "tci_fp.h"
 #include "tci_internal.h"
 
 namespace tci {
@@ -31,8 +32,6 @@ constexpr int kFcWaves = 4;    // wavefronts per workgroup, each a segment of th
 constexpr int kFcSeg = 64;     // samples per segment (include/tci.h: the order of every SUM_s)
 constexpr int kFcSums = 5;     // partial sums of the first pass: ll, pit, r, z, z * z
 constexpr int kFcU = 8;        // rows a wavefront loads together
-
-__device__ __forceinline__ double fc_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 struct FcTerm {
   double r, z, zz, ll;
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(kFcLanes * kFcWaves) void k_fitcheck(const CellMeta
   double* o = out + (k * 2 + dye) * 6 * ld_out + j;
   if ((int64_t)tile * kFcLanes >= N) {  // a tile of padding only (the same for the whole workgroup)
     if (wave == 0 && j < ld_out)
-      for (int q = 0; q < 6; ++q) o[q * ld_out] = fc_nan();
+      for (int q = 0; q < 6; ++q) o[q * ld_out] = qnan();
     return;
   }
   const bool live = j < N;  // the forward launch wrote sim[.., j] for j < N only
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(kFcLanes * kFcWaves) void k_fitcheck(const CellMeta
 #pragma unroll
         for (int u = 0; u < kFcU; ++u) {
           if (s0 + u < s1) {
-            bad |= (f[u] - f[u]) != 0.0;
+            bad |= !is_finite(f[u]);
             const FcTerm t = fc_term(y, f[u], sdk[s0 + u], lgk[s0 + u]);
             m = t.ll > m ? t.ll : m;
             acc[0] = acc[0] + t.ll;
@@ -170,7 +169,7 @@ __global__ __launch_bounds__(kFcLanes * kFcWaves) void k_fitcheck(const CellMeta
   }
 
   if (wave == 0 && j < ld_out) {
-    const bool scored = live && (y - y) == 0.0 && anybad == 0;
+    const bool scored = live && is_finite(y) && anybad == 0;
     double v[6];
     v[0] = (m + log(tot2[0])) - logS;
     v[1] = tot2[1] / (double)(S - 1);
@@ -179,7 +178,7 @@ __global__ __launch_bounds__(kFcLanes * kFcWaves) void k_fitcheck(const CellMeta
     v[4] = tot[3] / dS;
     v[5] = tot[4] / dS;
 #pragma unroll
-    for (int q = 0; q < 6; ++q) o[q * ld_out] = scored ? v[q] : fc_nan();
+    for (int q = 0; q < 6; ++q) o[q * ld_out] = scored ? v[q] : qnan();
   }
 }
 

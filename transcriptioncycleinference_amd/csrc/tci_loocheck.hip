@@ -26,6 +26,7 @@
 
 #include <cmath>
 
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_key.h"
 
@@ -36,8 +37,6 @@ namespace {
 constexpr int kLcLanes = 64;  // time points per tile: one per lane, one wavefront per workgroup
 constexpr int kLcSeg = 64;    // samples per segment (include/tci.h: the order of every SUM_s)
 constexpr int kLcU = 8;       // rows a wavefront loads together
-
-__device__ __forceinline__ double lc_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 struct LcEnt {
   uint64_t k;  // a key, or the bits of a double
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(kLcLanes) void k_loocheck(const CellMeta* __restric
   double* o = out + (k * 2 + dye) * 4 * ld_out + j;
   if ((int64_t)tile * kLcLanes >= N) {  // a tile of padding only
     if (j < ld_out)
-      for (int q = 0; q < 4; ++q) o[q * ld_out] = lc_nan();
+      for (int q = 0; q < 4; ++q) o[q * ld_out] = qnan();
     return;
   }
   // LDS: val [M][64] (8 B), Lg [G][64] (8 B), idx [M][64] (2 B)
@@ -175,16 +174,16 @@ __global__ __launch_bounds__(kLcLanes) void k_loocheck(const CellMeta* __restric
   double m = -INFINITY, mx = -INFINITY;  // mx = max_s (-ll_s)
   bool bad = false;
   lc_rows(S, col, ld_out, live, sdk, lgk, y, [&](int, double f, double ll) {
-    bad |= (f - f) != 0.0;
+    bad |= !is_finite(f);
     m = ll > m ? ll : m;
     const double nl = -ll;
     mx = nl > mx ? nl : mx;
   });
 
   // a tile with no scored point (the same for the whole wavefront): NaN everywhere, no selection and no fit
-  if (__ballot(live && (y - y) == 0.0 && !bad) == 0) {
+  if (__ballot(live && is_finite(y) && !bad) == 0) {
     if (j < ld_out)
-      for (int q = 0; q < 4; ++q) o[q * ld_out] = lc_nan();
+      for (int q = 0; q < 4; ++q) o[q * ld_out] = qnan();
     return;
   }
 
@@ -219,6 +218,7 @@ __global__ __launch_bounds__(kLcLanes) void k_loocheck(const CellMeta* __restric
   const double ec = exp(cut);
   auto x_at = [&](int jj) { return exp(from_key(val[(M - jj) * kLcLanes + lane])) - ec; };  // x_jj, jj = 1 .. M
   const double xM = x_at(M), x1 = x_at(1);
+  // spelled out: is_finite(xM) here makes the compiler order the whole kernel differently
   bool degenerate = !(xM > 0.0) || (xM - xM) != 0.0 || x1 < 0.0;
   double khat = INFINITY, sigma = 0.0;
   {
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kLcLanes) void k_loocheck(const CellMeta* __restric
     const double kk = sum / dM;
     sigma = -kk / b;
     const double kh = (kk * dM + 5.0) / (double)(M + 10);
-    if ((kh - kh) != 0.0 || (sigma - sigma) != 0.0) degenerate = true;
+    if (!is_finite(kh) || !is_finite(sigma)) degenerate = true;
     if (!degenerate) khat = kh;
   }
 
@@ -300,12 +300,12 @@ __global__ __launch_bounds__(kLcLanes) void k_loocheck(const CellMeta* __restric
   });
 
   if (j < ld_out) {
-    const bool scored = live && (y - y) == 0.0 && !bad;
+    const bool scored = live && is_finite(y) && !bad;
     const double elpd = (mA + log(totA)) - (mB + log(totB));
-    o[0] = scored ? elpd : lc_nan();
-    o[ld_out] = scored ? lppd : lc_nan();
-    o[2 * ld_out] = scored ? lppd - elpd : lc_nan();
-    o[3 * ld_out] = scored ? khat : lc_nan();
+    o[0] = scored ? elpd : qnan();
+    o[ld_out] = scored ? lppd : qnan();
+    o[2 * ld_out] = scored ? lppd - elpd : qnan();
+    o[3 * ld_out] = scored ? khat : qnan();
   }
 }
 

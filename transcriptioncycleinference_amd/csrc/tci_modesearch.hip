@@ -22,6 +22,7 @@
 // is a minimum under a total order, so the split over lanes does not matter. Every loop is bounded by an integer count.
 #include <hip/hip_runtime.h>
 
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_prior.h"
 #include "tci_rng.h"
@@ -38,8 +39,6 @@ constexpr uint32_t kPurposeIndex = 7, kPurposeCross = 8;  // 1-6 are the sampler
 // the crossover counter i * 2048 + (j >> 1) is one per (member, coordinate pair) while j < 4096; tci_create admits no
 // longer cell
 static_assert(7 + TCI_MAX_POINTS <= 4096, "the crossover counter of k_ms_trial");
-
-__device__ __forceinline__ double ms_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // m(w, n) of include/tci.h: a word scaled to [0, n)
 __device__ __forceinline__ uint32_t ms_scale(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * n) >> 32); }
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(kMsSelThreads) void k_ms_select(const CellMeta* __r
   // the rows and values the selection above stored are this workgroup's own stores, ordered by the barrier
   const int64_t bb = k * n_pop + sh_best;
   const int P = 7 + cells[cell_id[k]].n;
-  const double nan = ms_nan();
+  const double nan = qnan();
   for (int64_t j = threadIdx.x; j < ld; j += kMsSelThreads) theta_best[k * ld + j] = j < P ? pop[bb * ld + j] : nan;
   if (threadIdx.x == 0) {
     best_vals[k] = f[bb];

@@ -19,6 +19,7 @@
 //      and an add as written, never fused (plims' interp1).
 #include <hip/hip_runtime.h>
 
+#include "tci_fp.h"
 #include "tci_internal.h"
 #include "tci_key.h"
 
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(kQThreads) void k_quantile(const CellMeta* __restri
   for (int idx = tid; idx < (qa.nq << lg_t); idx += kQThreads) {
     const int q = idx >> lg_t, jj = idx & (T - 1), j = j0 + jj;
     if (j >= ld_out) continue;
-    double r = __longlong_as_double(0x7FF8000000000000ll);
+    double r = qnan();
     if (j < N) {
       const uint64_t* col = keys + jj * stride;
       const int lo = qa.lo[q];
