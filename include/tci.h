@@ -1229,6 +1229,105 @@ int tci_demc_run_rank(tci_ctx* ctx, const tci_demc_options* opt, const double* p
                       const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout, const tci_chainess_options* eopt,
                       tci_chainess_outputs* eout, const tci_chainrank_options* kopt, tci_chainrank_outputs* kout);
 
+/* ---- DE-MC(zs) sampler per cell (ter Braak & Vrugt 2008, Statistics and Computing 18:435) ----
+ * A third sampler beside DRAM and DE-MC. A few chains per cell take their difference vectors from an archive Z of past
+ * states instead of from the current population: Z starts with m0 >> P rows and grows while the run goes on, so the
+ * differences span the whole space from the first generation and shrink as the chains contract; a share of the moves
+ * are snooker updates along the line through the current state and an archive point; and the archive does not depend
+ * on the other chains' current states, so every chain moves in every generation: one likelihood launch per generation
+ * where tci_demc_run has two half-sweeps. All in FP64, every operation rounded once as written, never fused. Names not
+ * defined here (rng, m, u01, the bounds rule, f_old / f_new, the sigma2 draw, kept rows, keys) are tci_demc_run's.
+ * For each selected cell k, P = 7 + N of cell cell_id[k]: n_pop chains, 1 <= n_pop <= 4096, start at pop0[k]; the
+ *   archive of M rows of ld doubles starts as z0[k], m0 rows, 3 <= m0, each checked like a pop0 row. Chain i of cell k
+ *   is chain b = k * n_pop + i in every output (n_chains = n_sel * n_pop).
+ * Generation 0 evaluates ss and pri of pop0.
+ * Generation g = 1 .. n_gen: all chains move, from the states and the archive as they stood after generation g - 1. The
+ *   step is g. M_g = m0 + n_pop * floor((g - 1) / append_every) rows of the archive are read. After the decisions of a
+ *   generation with g mod append_every == 0 the n_pop current states are appended to the archive in ascending i.
+ *   Draws. Purposes 13 (index), 14 (coordinate), 15 (accept), 16 (sigma2). w = rng(seed, key[k], g, 13, i) and
+ *     q = rng(seed, key[k], g, 13, 4096 + i). a = m(w.x, M_g); c = m(w.y, M_g - 1), then + 1 if >= a;
+ *     e = m(w.w, M_g - 2), then + 1 if >= min(a, c), then + 1 if >= max(a, c): a, c, e distinct, each uniform given
+ *     the ones before. jrand = m(w.z, P). The move is a snooker move iff u01(q.x, q.y) < p_snooker;
+ *     gamma_s = 1.2 + u01(q.z, q.w).
+ *   Parallel move: exactly tci_demc_run's trial with x_r1 = Z[a], x_r2 = Z[c]: the coordinate uniforms are those of
+ *     rng(seed, key[k], g, 14, i * 4096 + j); crossover by CR and jrand, gamma = gamma0 / sqrt((double)(2 d')); a jump
+ *     generation (jump_every > 0 and g mod jump_every == 0) crosses every coordinate with gamma = 1; the uniform jitter
+ *     is tci_demc_run's. ljac = 0.
+ *   Snooker move: no crossover, no jitter, no coordinate draws, unaffected by jump generations. z = Z[e], z1 = Z[a],
+ *     z2 = Z[c]. For j < P: d_j = x_i[j] - z[j]; D = SUM d_j * d_j; A = SUM (z1[j] - z2[j]) * d_j (the subtraction,
+ *     the product, the sum). If D == 0 or D is not finite the move is a NULL MOVE: rejected without evaluation, counted
+ *     in n_null, logged with trial_oob = 2, logr and ljac NaN. It happens whenever a chain that has not moved since it
+ *     was archived draws its own copy, so it is no corner case. Otherwise r = A / D, s = gamma_s * r and
+ *     t_j = x_i[j] + s * d_j (the product, the addition) for every j < P; entries j >= P keep the parent's bits. The
+ *     bounds rule applies over all j < P (an out-of-bounds snooker trial has ljac NaN). D' = SUM (t_j - z[j])^2;
+ *     ljac = (0.5 * (double)(P - 1)) * (log(D') - log(D)), log the device library's. D' = 0 gives -Inf and rejects.
+ *   The three sums have one order: lane l of 64 sums its terms j = l, l + 64, .. ascending from 0.0, and the 64
+ *     partials combine by the xor butterfly p <- p + p[lane ^ d] for d = 32, 16, 8, 4, 2, 1. Addition commutes bitwise,
+ *     so every lane holds the same value, and a restatement replays it with six pairwise folds. The prior stays in
+ *     tci_chainlp's order, so prichain keeps equalling tci_chainlp's bits.
+ *   Acceptance. logr = -0.5 * (f_new - f_old) + ljac, the last addition written as such. Accept iff logr >= 0, or
+ *     u < exp(logr) with u = u01 of the x and y words of rng(seed, key[k], g, 15, i); a NaN logr rejects.
+ *   sigma2: tci_demc_run's draw on stream (seed, key[k], g, 16), calls (i << 16) | it.
+ * Validity. The chain is not Markov with a fixed kernel: the proposal depends on the archive, which grows. ter Braak &
+ *   Vrugt show ergodicity by diminishing adaptation as M grows. Rows kept while the archive is young are burn-in, and
+ *   stats_from is the caller's to set.
+ * Bits. As tci_demc_run's, with z0 among what a cell's outputs depend on. ss, exp, the two logs of a snooker move and
+ * the Gamma variate are the inexact steps; a float64 restatement that takes ss and ljac from the device reproduces
+ * every decision it can decide (tests/demczs_oracle.py). */
+typedef struct {
+  int64_t n_gen, thin, jump_every, stats_from, updatesigma; /* as tci_demc_options */
+  double CR, gamma0;                                        /* as tci_demc_options */
+  uint64_t seed;
+  const int64_t* keys;  /* optional [n_sel], as tci_demc_options.keys */
+  int64_t flags;        /* reserved, must be 0 */
+  int64_t append_every; /* the chains' states join the archive after every append_every-th generation, >= 1; default 10 */
+  double p_snooker;     /* share of snooker moves, in [0, 1]; default 0.1 */
+} tci_demczs_options;
+
+/* Host buffers (any pointer may be NULL). The first sixteen fields are tci_demc_outputs'. */
+typedef struct {
+  double *chain;                          /* [n_keep][n_chains][ld] */
+  double *s2chain, *sschain, *prichain;   /* [n_keep][n_chains] */
+  double *pop;                            /* [n_chains][ld]: the chains' final states */
+  double *s2, *ss;                        /* [n_chains]: of the final states */
+  double* accept_rate;                    /* [n_chains]: accepted proposals / n_gen (NaN for n_gen = 0) */
+  int32_t* n_oob;                         /* [n_chains]: proposals rejected at the bounds */
+  int64_t* n_evals;                       /* [n_chains]: SS evaluations, 1 + n_gen - n_oob - n_null */
+  double* logr;                           /* [log_rows][n_chains]; NaN for a proposal that was not evaluated */
+  uint8_t *accepted, *trial_oob;          /* [log_rows][n_chains]; trial_oob: 0, 1 out of bounds, 2 a null move */
+  int64_t log_rows;                       /* rows the five logs hold (the caller's) */
+  int64_t n_keep;    /* written: kept rows */
+  double kernel_ms;  /* written: device time of the run (HIP events), the likelihood launches included */
+  int32_t* n_null;   /* [n_chains]: null snooker moves */
+  double* ljac;      /* [log_rows][n_chains]: 0 for a parallel move, NaN for a null or out-of-bounds snooker move */
+  uint8_t* snooker;  /* [log_rows][n_chains]: 1 for a snooker move */
+  double* archive;   /* [n_sel][n_archive][ld]: z0 and the appended states, n_archive = m0 + n_pop * (n_gen / append_every) */
+  int64_t n_archive; /* written: the final rows of a cell's archive */
+} tci_demczs_outputs;
+
+int tci_demczs_defaults(tci_demczs_options* opt);
+
+/* HOST pointers, synchronous. pop0 is [n_sel][n_pop][ld], z0 [n_sel][m0][ld]; everything else is tci_demc_run's, the
+ * reductions with the chains of cell k as group k included. Checked in tci_demc_run's order and wording, with these
+ * differences: n_pop outside [1, 4096]; after gamma0, TCI_EINVAL for append_every < 1 and for p_snooker outside [0, 1]
+ * or NaN; after n_pop, TCI_EINVAL for m0 < 3 and for an archive of 2^24 rows or more (m0 + n_pop * (n_gen /
+ * append_every)); after the pop0 entries, TCI_EINVAL naming cell, row and index for a z0 entry with j < P that is not
+ * finite or lies outside [lower_j, upper_j]. TCI_ENOMEM, with the byte count of every device buffer of the call in the
+ * message, when the populations, the archive and the chain do not fit the device. */
+int tci_demczs_run(tci_ctx* ctx, const tci_demczs_options* opt, const double* pop0, const double* z0, int64_t ld,
+                   const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower,
+                   const double* upper, const double* prior_mu, const double* prior_sig, const double* jitter,
+                   const double* sigma2_0, tci_demczs_outputs* out, const tci_chainrhat_options* ropt,
+                   tci_chainrhat_outputs* rout, const tci_chainess_options* eopt, tci_chainess_outputs* eout);
+
+/* tci_demczs_run plus tci_chainrank of the same groups over the same kept rows, as tci_demc_run_rank. */
+int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const double* pop0, const double* z0, int64_t ld,
+                        const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower,
+                        const double* upper, const double* prior_mu, const double* prior_sig, const double* jitter,
+                        const double* sigma2_0, tci_demczs_outputs* out, const tci_chainrhat_options* ropt,
+                        tci_chainrhat_outputs* rout, const tci_chainess_options* eopt, tci_chainess_outputs* eout,
+                        const tci_chainrank_options* kopt, tci_chainrank_outputs* kout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch, MCMCdemc, MCMCrank] = tci_fit(data, varargin)
+function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtemper, MCMCsearch, MCMCdemc, MCMCrank, MCMCdemczs] = tci_fit(data, varargin)
 %TCI_FIT One dataset of TranscriptionCycleMCMC on an MI355X: every cell's DRAM chain in one launch.
 %   [MCMCresults, MCMCplot, MCMCchain] = TCI_FIT(data, Name, Value, ...) replaces the body of the
 %   parfor over cells of src/TranscriptionCycleMCMC.m:161-357 and the pruning of skipped cells
@@ -69,6 +69,14 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtem
 %        every kept row). Fills the ninth output MCMCdemc, one entry per fitted cell: accept_rate, n_oob, n_evals
 %        (1 x n_pop), rhat_max, ess_min (across the members, parameters and sigma2), n_pop, n_gen, cell_index.
 %        Not with 'temper', 'diagnostics', 'logpost', 'stack' or 'predict'.)
+%     'demczs' ([]; [n_pop n_gen] samples every fitted cell with the DE-MC(zs) sampler (tci_mex('demczs');
+%        include/tci.h): n_pop chains per cell, 1 to 4096, that propose from an archive of past states. The archive
+%        starts with m0 = min(10*P, 4096) rows, P the longest cell's 7+N, drawn as 'presearch' draws a population, and
+%        the chains start at its first n_pop rows; with 'presearch' [m0 n_gen] the search's final population is the
+%        archive and the chains start at its best members. Everything else is as for 'demc', whose place the chains
+%        take. Fills the eleventh output MCMCdemczs: MCMCdemc's fields plus n_null (1 x n_pop), snooker_rate (the
+%        share of snooker moves among the first min(n_gen, 1024) generations, the ones that are logged), m0 and
+%        n_archive. Not with 'demc'.)
 %     'rank' (0; 1 fills the tenth output MCMCrank, one entry per fitted cell, with the rank diagnostics of Vehtari et
 %        al. (2021) over the kept rows at or past n_burn (tci_chainrank, include/tci.h; options.rank of
 %        tci_mex('dram') / tci_mex('demc'), reduced from the device chain): across the cell's DE-MC members with
@@ -109,6 +117,7 @@ p.addParameter('temper', 1);
 p.addParameter('swap_every', 1);
 p.addParameter('presearch', []);
 p.addParameter('demc', []);
+p.addParameter('demczs', []);
 p.addParameter('rank', 0);
 p.parse(varargin{:});
 o = p.Results;
@@ -189,7 +198,7 @@ end
 MCMCchain = struct('v_chain',{},'ton_chain',{},'A_chain',{},'tau_chain',{},...
     'MS2_basal_chain',{},'PP7_basal_chain',{},'R_chain',{},'dR_chain',{},'s2chain',{});
 MCMCdiag = struct([]); MCMClp = struct([]); MCMCstack = struct([]); MCMCtemper = struct([]);
-MCMCsearch = struct([]); MCMCdemc = struct([]); MCMCrank = struct([]);
+MCMCsearch = struct([]); MCMCdemc = struct([]); MCMCrank = struct([]); MCMCdemczs = struct([]);
 if o.rank && o.thin <= 0
     error('tci:rank', 'the rank diagnostics need the kept chain rows: thin > 0');
 end
@@ -245,8 +254,21 @@ sigma2_0 = 1;                                       % :212, :259
 MCMCsearch = struct([]);
 search = [];
 dm = o.demc;
+zs = ~isempty(o.demczs);                            % DE-MC(zs): the DE-MC path below, with an archive beside the chains
+if zs
+    if ~isempty(dm)
+        error('tci:demczs', 'demczs and demc are two samplers: give one');
+    end
+    dm = o.demczs;
+    if ~(isnumeric(dm) && numel(dm) == 2 && all(dm == floor(dm)) && dm(1) >= 1 && dm(1) <= 4096 && dm(2) >= 1)
+        error('tci:demczs', 'demczs must be [n_pop n_gen] with n_pop in [1, 4096] and n_gen >= 1');
+    end
+    m0 = max(min(10*P, 4096), max(dm(1), 4));       % the rows of the starting archive
+end
+n_draw = [];
 if ~isempty(dm)
-    if ~(isnumeric(dm) && numel(dm) == 2 && all(dm == floor(dm)) && dm(1) >= 4 && dm(1) <= 4096 && dm(2) >= 1)
+    if zs, n_draw = m0; else, n_draw = dm(1); end   % the members drawn (and searched): the population, or the archive
+    if ~zs && ~(isnumeric(dm) && numel(dm) == 2 && all(dm == floor(dm)) && dm(1) >= 4 && dm(1) <= 4096 && dm(2) >= 1)
         error('tci:demc', 'demc must be [n_pop n_gen] with n_pop in [4, 4096] and n_gen >= 1');
     end
     if R > 1 || o.diagnostics || o.logpost || o.stack || o.predict > 0
@@ -255,14 +277,14 @@ if ~isempty(dm)
     if o.thin <= 0
         error('tci:demc', 'a DE-MC fit is reduced from the kept rows: thin > 0');
     end
-    if ~isempty(o.presearch) && o.presearch(1) ~= dm(1)
-        error('tci:demc', 'presearch n_pop must be the sampler''s n_pop');
+    if ~isempty(o.presearch) && o.presearch(1) ~= n_draw
+        error('tci:demc', 'presearch n_pop must be the sampler''s n_pop (demczs: its m0 = min(10*P, 4096))');
     end
 end
 if ~isempty(o.presearch) || ~isempty(dm)            % the mode search: every chain of a cell starts from its best member
     ps = o.presearch;
     if isempty(ps)
-        ps = [dm(1) 0];                             % DE-MC alone: the population is drawn, not searched
+        ps = [n_draw 0];                            % DE-MC alone: the population is drawn, not searched
     end
     if ~(isnumeric(ps) && numel(ps) == 2 && all(ps == floor(ps)) && ps(1) >= 4 && ps(1) <= 4096 && ps(2) >= 0)
         error('tci:presearch', 'presearch must be [n_pop n_gen] with n_pop in [4, 4096] and n_gen >= 0');
@@ -296,9 +318,25 @@ if ~isempty(dm)                                     % ---- the DE-MC fit: every 
     for k = 1:nc
         JIT(8+numel(setup(k).t):end, k) = 0;
     end
-    D = tci_mex('demc', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, ...
-        struct('n_gen', dm(2), 'thin', o.thin, 'stats_from', n_burn, 'seed', o.seed*1000003 + 20201028, ...
-        'keys', [setup.cellNum] - 1, 'rhat', 1, 'ess', 1, 'rank', double(o.rank ~= 0)));
+    dopts = struct('n_gen', dm(2), 'thin', o.thin, 'stats_from', n_burn, 'seed', o.seed*1000003 + 20201028, ...
+        'keys', [setup.cellNum] - 1, 'rhat', 1, 'ess', 1, 'rank', double(o.rank ~= 0));
+    if zs
+        Z0 = POP0;                                  % the archive: the drawn (or searched) population
+        n_pop = dm(1);
+        C0 = zeros(P, n_pop*nc);                    % the chains: its first rows, or the search's best members
+        for k = 1:nc
+            pick = 1:n_pop;
+            if ~isempty(search)
+                [~, order] = sort(search.f(:, k));  % ascending f, ties by index, NaN last
+                pick = order(1:n_pop)';
+            end
+            C0(:, (k-1)*n_pop + (1:n_pop)) = Z0(:, (k-1)*m0 + pick);
+        end
+        dopts.log_rows = min(dm(2), 1024);
+        D = tci_mex('demczs', h, 1:nc, C0, Z0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, dopts);
+    else
+        D = tci_mex('demc', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, dopts);
+    end
     sel = o.thin*(0:size(D.chain, 3)-1) >= n_burn;  % kept row r is generation (r - 1)*thin
     for k = 1:nc
         n = numel(setup(k).t);
@@ -328,7 +366,15 @@ if ~isempty(dm)                                     % ---- the DE-MC fit: every 
         dk = struct('accept_rate', D.accept_rate(:, k)', 'n_oob', D.n_oob(:, k)', 'n_evals', D.n_evals(:, k)', ...
             'rhat_max', D.rhat_max(k), 'ess_min', D.ess_min(k), 'n_pop', n_pop, 'n_gen', dm(2), ...
             'cell_index', setup(k).cellNum);
-        if isempty(MCMCdemc), MCMCdemc = dk; else, MCMCdemc(k) = dk; end
+        if zs
+            dk.n_null = D.n_null(:, k)';
+            dk.snooker_rate = mean(mean(D.snooker(mem, :)));
+            dk.m0 = m0;
+            dk.n_archive = D.n_archive;
+            if isempty(MCMCdemczs), MCMCdemczs = dk; else, MCMCdemczs(k) = dk; end
+        else
+            if isempty(MCMCdemc), MCMCdemc = dk; else, MCMCdemc(k) = dk; end
+        end
         if o.rank
             rk = rank_entry(D.rank, k, n, setup(k).cellNum);
             if isempty(MCMCrank), MCMCrank = rk; else, MCMCrank(k) = rk; end

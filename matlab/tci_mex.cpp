@@ -139,6 +139,13 @@
 //          trial_oob (n_chains x min(log_rows, n_gen)), n_keep, kernel_ms; with options.rhat also rhat (P x n), s2_rhat
 //          and rhat_max (1 x n), with options.ess also ess (P x n), s2_ess and ess_min (1 x n): tci_chainrhat /
 //          tci_chainess across the members of every cell over the kept rows of generations >= stats_from.
+//   out = tci_mex('demczs', h, cells, POP0, Z0, LB, UB, MU, SIG, JIT[, sigma2[, options]])
+//          the DE-MC(zs) sampler (ter Braak & Vrugt 2008; tci_demczs_run, the definition is in include/tci.h): POP0 is
+//          P x (n_pop * n), the chains' starts, and Z0 P x (m0 * n), the starting archive of every cell, both laid out as
+//          POP0 of 'demc'; everything else is 'demc''s, with the options append_every (10), p_snooker (0.1) and archive
+//          (false) beside its own. out: 'demc''s fields (trial_oob is 2 for a null move) plus n_null (n_pop x n), ljac
+//          and snooker (n_chains x min(log_rows, n_gen)), n_archive and, with options.archive, archive
+//          (P x n_archive x n).
 //   options.presearch of 'dram': a population P x (n_pop * n) laid out as POP0 above, one per chain. The search runs
 //          first (options.presearch_gen generations, default 500, options.presearch_F, options.presearch_CR; seeded by
 //          options.seed and keyed by options.chain_keys) and chain c starts from the best final member of its
@@ -1868,12 +1875,22 @@ void cmd_modesearch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   plhs[0] = ms.finish();
 }
 
-// ---- 'demc': the DE-MC population sampler over a population per cell -----------------------------------
+// ---- 'demc' and 'demczs': the population samplers over a population (chains and an archive) per cell -----------
+// zs: the arguments after POP0 move one place up to make room for Z0.
 
-void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs0[], bool zs) {
   (void)nlhs;
-  if (nrhs < 9 || nrhs > 11)
+  if (!zs && (nrhs < 9 || nrhs > 11))
     mexErrMsgIdAndTxt("tci:arg", "tci_mex('demc', h, cells, POP0, LB, UB, MU, SIG, JIT[, sigma2[, options]])");
+  if (zs && (nrhs < 10 || nrhs > 12))
+    mexErrMsgIdAndTxt("tci:arg", "tci_mex('demczs', h, cells, POP0, Z0, LB, UB, MU, SIG, JIT[, sigma2[, options]])");
+  // prhs: 'demc''s argument list; Z0 is taken out of 'demczs''s
+  const mxArray* z0_arg = zs ? prhs0[4] : nullptr;
+  std::vector<const mxArray*> shifted(prhs0, prhs0 + nrhs);
+  if (zs) shifted.erase(shifted.begin() + 4);
+  const mxArray* const* prhs = shifted.data();
+  nrhs = (int)shifted.size();
+  const char* const cmd_name = zs ? "demczs" : "demc";
   // every argument and option is checked before the handle (and before anything reaches the GPU)
   const size_t n = mxGetNumberOfElements(prhs[2]);
   const double* c = doubles(prhs[2], -1, "cells");
@@ -1893,6 +1910,8 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   for (int k = 0; k < 5; ++k) in[k] = chain_matrix(prhs[4 + k], names[k], P, n);
   size_t n_pop = 0;
   const double* pop = pop_matrix(prhs[3], "POP0", P, n, &n_pop);
+  size_t m0 = 0;
+  const double* z0 = zs ? pop_matrix(z0_arg, "Z0", P, n, &m0) : nullptr;
   std::vector<double> s2v(n, 1.0);
   if (nrhs > 9 && mxGetNumberOfElements(prhs[9]) != 0) {
     const size_t ns2 = mxGetNumberOfElements(prhs[9]);
@@ -1907,15 +1926,25 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o = prhs[10];
     static const char* known[] = {"n_gen", "thin", "jump_every", "stats_from", "updatesigma", "CR", "gamma0", "seed",
                                   "keys", "log_rows", "rhat", "ess", "max_lag", "rank"};
+    static const char* known_zs[] = {"append_every", "p_snooker", "archive"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
       bool ok = false;
       for (const char* k : known) ok = ok || strcmp(fn, k) == 0;
-      if (!ok) mexErrMsgIdAndTxt("tci:opts", "options.%s is not an option of tci_mex('demc')", fn);
+      if (zs)
+        for (const char* k : known_zs) ok = ok || strcmp(fn, k) == 0;
+      if (!ok) mexErrMsgIdAndTxt("tci:opts", "options.%s is not an option of tci_mex('%s')", fn, cmd_name);
     }
   }
   tci_demc_options dopt;
   tci_demc_defaults(&dopt);
+  tci_demczs_options zopt;
+  tci_demczs_defaults(&zopt);
+  if (zs) {
+    zopt.append_every = opt_int(o, "append_every", zopt.append_every, 1);
+    zopt.p_snooker = opt_num(o, "p_snooker", zopt.p_snooker);
+  }
+  const bool want_archive = zs && opt_num(o, "archive", 0.0) != 0.0;
   dopt.n_gen = opt_int(o, "n_gen", dopt.n_gen, 0);
   dopt.thin = opt_int(o, "thin", dopt.thin, 0);
   dopt.jump_every = opt_int(o, "jump_every", dopt.jump_every, 0);
@@ -1945,11 +1974,16 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     dopt.keys = keys.data();
   }
   if (n_pop > 4096 || n > 2147483647u / n_pop) mexErrMsgIdAndTxt("tci:arg", "POP0 holds too many members");
+  const size_t M_fin = zs ? m0 + n_pop * (size_t)(dopt.n_gen / zopt.append_every) : 0;
+  if (zs && (m0 >= ((size_t)1 << 24) || M_fin >= ((size_t)1 << 24)))
+    mexErrMsgIdAndTxt("tci:arg", "Z0 and the appended states must stay below 2^24 rows per cell");
   tci_ctx* ctx = handle_of(prhs[1]);
   const size_t B = n * n_pop, K = dopt.thin > 0 ? (size_t)(dopt.n_gen / dopt.thin) + 1 : 0;
   const size_t G = (size_t)std::min<int64_t>(log_rows, dopt.n_gen);
   std::vector<const char*> fields = {"chain", "s2chain", "sschain", "prichain", "pop", "s2", "ss", "accept_rate", "logr",
                                      "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms"};
+  if (zs) fields.insert(fields.end(), {"n_null", "ljac", "snooker", "n_archive"});
+  if (want_archive) fields.push_back("archive");
   if (want_rhat) fields.insert(fields.end(), {"rhat", "s2_rhat", "rhat_max"});
   if (want_ess) fields.insert(fields.end(), {"ess", "s2_ess", "ess_min"});
   if (want_rank) fields.push_back("rank");
@@ -2006,13 +2040,55 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxSetField(res, 0, "s2_ess", e1);
   }
   RankOut ro(want_rank ? P : 0, want_rank ? n : 0, (size_t)kopt.nq, true);  // a group per cell: its members
-  const int rc = tci_demc_run_rank(ctx, &dopt, pop, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, in[0], in[1], in[2],
-                                   in[3], in[4], s2v.data(), &out, nullptr, want_rhat ? &rout : nullptr, &eopt,
-                                   want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr);
+  int rc;
+  std::vector<int32_t> nnull(zs ? B : 0);
+  std::vector<uint8_t> snk(zs ? B * G + 1 : 0);
+  mxArray *lj = nullptr, *ar = nullptr;
+  if (zs) {
+    // tci_demczs_options and tci_demczs_outputs begin with the fields of their DE-MC twins (include/tci.h)
+    memcpy(&zopt, &dopt, sizeof dopt);
+    tci_demczs_outputs zout;
+    memset(&zout, 0, sizeof zout);
+    memcpy(&zout, &out, sizeof out);
+    lj = mxCreateDoubleMatrix(B, G, mxREAL);
+    zout.n_null = nnull.data();
+    if (G) {
+      zout.ljac = mxGetPr(lj);
+      zout.snooker = snk.data();
+    }
+    if (want_archive) {
+      const mwSize da[3] = {P, M_fin, n};
+      ar = mxCreateNumericArray(3, da, mxDOUBLE_CLASS, mxREAL);
+      zout.archive = mxGetPr(ar);
+    }
+    rc = tci_demczs_run_rank(ctx, &zopt, pop, z0, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, (int64_t)m0, in[0],
+                             in[1], in[2], in[3], in[4], s2v.data(), &zout, nullptr, want_rhat ? &rout : nullptr, &eopt,
+                             want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr);
+    out.n_keep = zout.n_keep;
+    out.kernel_ms = zout.kernel_ms;
+    if (rc == TCI_OK) {
+      mxArray* nn = mxCreateDoubleMatrix(n_pop, n, mxREAL);
+      for (size_t b = 0; b < B; ++b) mxGetPr(nn)[b] = (double)nnull[b];
+      mxArray* ls = mxCreateDoubleMatrix(B, G, mxREAL);
+      for (size_t i = 0; i < B * G; ++i) mxGetPr(ls)[i] = (double)snk[i];
+      mxSetField(res, 0, "n_null", nn);
+      mxSetField(res, 0, "ljac", lj);
+      mxSetField(res, 0, "snooker", ls);
+      mxSetField(res, 0, "n_archive", mxCreateDoubleScalar((double)zout.n_archive));
+      if (ar) mxSetField(res, 0, "archive", ar);
+    } else {
+      mxDestroyArray(lj);
+      if (ar) mxDestroyArray(ar);
+    }
+  } else {
+    rc = tci_demc_run_rank(ctx, &dopt, pop, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, in[0], in[1], in[2], in[3],
+                           in[4], s2v.data(), &out, nullptr, want_rhat ? &rout : nullptr, &eopt,
+                           want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr);
+  }
   if (rc != TCI_OK || !want_rank) mxDestroyArray(ro.res);
   if (rc != TCI_OK) {
     mxDestroyArray(res);
-    check(ctx, rc, "tci_demc_run");
+    check(ctx, rc, zs ? "tci_demczs_run" : "tci_demc_run");
   }
   if (want_rank) {
     mxArray* gm = mxCreateDoubleMatrix(1, B, mxREAL);
@@ -2085,7 +2161,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   else if (cmd == "chainrank") cmd_chainrank(nlhs, plhs, nrhs, prhs);
   else if (cmd == "chainlp") cmd_chainlp(nlhs, plhs, nrhs, prhs);
   else if (cmd == "modesearch") cmd_modesearch(nlhs, plhs, nrhs, prhs);
-  else if (cmd == "demc") cmd_demc(nlhs, plhs, nrhs, prhs);
+  else if (cmd == "demc") cmd_demc(nlhs, plhs, nrhs, prhs, false);
+  else if (cmd == "demczs") cmd_demc(nlhs, plhs, nrhs, prhs, true);
   else if (cmd == "device_count") {
     int n = 0;
     tci_device_count(&n);

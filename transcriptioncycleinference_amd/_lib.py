@@ -203,6 +203,15 @@ class tci_demc_outputs(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class tci_demczs_options(C.Structure):
+    _fields_ = tci_demc_options._fields_ + [("append_every", C.c_int64), ("p_snooker", C.c_double)]
+
+
+class tci_demczs_outputs(C.Structure):
+    _fields_ = tci_demc_outputs._fields_ + [("n_null", _i32p), ("ljac", _dp), ("snooker", _u8p), ("archive", _dp),
+                                            ("n_archive", C.c_int64)]
+
+
 class tci_fitcheck_options(C.Structure):
     _fields_ = [("scratch_bytes", C.c_int64), ("n_levels", C.c_int32), ("levels", C.c_double * 8)]
 
@@ -331,6 +340,16 @@ SIGNATURES = [
                                     C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                     C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
                                     C.POINTER(tci_chainrank_options), C.POINTER(tci_chainrank_outputs)]),
+    ("tci_demczs_defaults", C.c_int, [C.POINTER(tci_demczs_options)]),
+    ("tci_demczs_run", C.c_int, [C.c_void_p, C.POINTER(tci_demczs_options), _dp, _dp, C.c_int64, _i32p, C.c_int64,
+                                 C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_demczs_outputs),
+                                 C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                 C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs)]),
+    ("tci_demczs_run_rank", C.c_int, [C.c_void_p, C.POINTER(tci_demczs_options), _dp, _dp, C.c_int64, _i32p, C.c_int64,
+                                      C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_demczs_outputs),
+                                      C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                      C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
+                                      C.POINTER(tci_chainrank_options), C.POINTER(tci_chainrank_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -21,6 +21,7 @@ SOURCES = [os.path.join(CSRC, "tci_kernels.hip"), os.path.join(CSRC, "tci_dram.h
            os.path.join(CSRC, "tci_fitcheck.hip"), os.path.join(CSRC, "tci_chainlp.hip"), os.path.join(CSRC, "tci_loocheck.hip"),
            os.path.join(CSRC, "tci_modesearch.hip"), os.path.join(CSRC, "tci_api_search.cpp"),
            os.path.join(CSRC, "tci_demc.hip"), os.path.join(CSRC, "tci_api_demc.cpp"),
+           os.path.join(CSRC, "tci_demczs.hip"), os.path.join(CSRC, "tci_api_demczs.cpp"),
            os.path.join(CSRC, "tci_chainrank.hip"),
            os.path.join(CSRC, "tci_api.cpp"), os.path.join(CSRC, "tci_api_chain.cpp"), os.path.join(CSRC, "tci_api_dram.cpp")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "tci.h"), os.path.join(CSRC, "tci_internal.h"), os.path.join(CSRC, "tci_diag.h"), os.path.join(CSRC, "tci_tile16.h"), os.path.join(CSRC, "tci_adapt_map.h"),

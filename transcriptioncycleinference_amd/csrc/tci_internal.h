@@ -282,4 +282,30 @@ int launch_demc_decide(const KParams& kp, const int32_t* cell_id, const int64_t*
                        int32_t* n_acc, int32_t* n_oob, double* chain, double* s2chain, double* sschain,
                        double* prichain, double* logr, uint8_t* acc_log, uint8_t* oob_log, void* stream);
 
+// One generation of the DE-MC(zs) sampler (tci_demczs.hip) on device chains [n_sel][n_pop][ld] and a device archive
+// [n_sel][M_cap][ld] of which generation gen reads the first M_g rows (3 <= M_g <= M_cap < 2^24). ss, pri, s2, the
+// counters, trial [n_sel * n_pop][ld] and ss_t, pri_t, ljac, move, active [n_sel * n_pop] are laid out as the rows are:
+// every chain moves. cell_id, keys, sigma2_0 (device): [n_sel]; lower, upper, mu, sig, jitter (device): [n_sel][ld].
+// 1 <= n_pop <= 4096 and n_sel * n_pop below 2^31 (TCI_ERANGE). Asynchronous on `stream`; TCI_EINVAL on a bad size or a
+// null pointer, TCI_EHIP on a HIP error.
+//   launch_zs_propose  gen == 0: pri of every chain's start (nothing else is read). gen >= 1: the trial of every chain,
+//                      its prior, ljac, move (0 parallel, 1 snooker, 2 a null snooker move) and active byte (0: null, or
+//                      an entry is NaN or out of bounds; pri is NaN). The caller then launches the likelihood kernel.
+//   launch_zs_decide   gen == 0: s2 = sigma2_0 and zero counters. gen >= 1: the decision and the sigma2 draw of every
+//                      chain; an accepted trial replaces its parent. log_row >= 0: the five logs (each may be null) get
+//                      that row. app_row >= 0: after the decisions chain i's row goes to archive row app_row + i of its
+//                      cell. keep_row >= 0: row keep_row of chain, s2chain, sschain and prichain gets every chain.
+int launch_zs_propose(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* pop,
+                      const double* arch, const double* lower, const double* upper, const double* mu, const double* sig,
+                      const double* jitter, int64_t n_sel, int64_t n_pop, int64_t M_g, int64_t M_cap, int64_t ld,
+                      int64_t gen, bool jump, uint64_t seed, double gamma0, double CR, double p_snooker, double* trial,
+                      double* pri, double* ljac, uint8_t* move, uint8_t* active, void* stream);
+int launch_zs_decide(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* sigma2_0,
+                     const double* trial, const double* ss_t, const double* pri_t, const double* ljac, const uint8_t* move,
+                     const uint8_t* active, int64_t n_sel, int64_t n_pop, int64_t M_cap, int64_t ld, int64_t gen,
+                     uint64_t seed, bool updatesigma, int64_t keep_row, int64_t app_row, int64_t log_row, double* pop,
+                     double* arch, double* ss, double* pri, double* s2, int32_t* n_acc, int32_t* n_oob, int32_t* n_null,
+                     double* chain, double* s2chain, double* sschain, double* prichain, double* logr, uint8_t* acc_log,
+                     uint8_t* oob_log, double* ljac_log, uint8_t* snk_log, void* stream);
+
 }  // namespace tci

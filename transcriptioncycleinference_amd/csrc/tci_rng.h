@@ -1,7 +1,7 @@
 // tci_rng.h -- the counter-based generator of the sampler (tci_dram.hip) and of the mode search (tci_modesearch.hip):
 // Philox4x32-10 keyed by (seed), counter (chain, step, purpose, index). A stream is reproducible and independent of
 // launch geometry. Purposes 1-6 are the sampler's (tci_dram.hip), 7 and 8 the mode search's, 9-12 the DE-MC sampler's
-// (tci_demc.hip). Device code only.
+// (tci_demc.hip), 13-16 the DE-MC(zs) sampler's (tci_demczs.hip). Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

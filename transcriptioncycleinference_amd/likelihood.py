@@ -604,6 +604,38 @@ class Demc:
                                      U(self.trial_oob), self.logr.shape[0], 0, 0.0)
 
 
+@dataclasses.dataclass
+class DemcZs(Demc):
+    """A DE-MC(zs) run (``tci_demczs_outputs``; the definition is in ``include/tci.h``): :class:`Demc`'s fields, with
+    ``trial_oob`` 2 for a null snooker move, plus ``n_null`` (int32) ``[n_sel, n_pop]``, the logs ``ljac`` and
+    ``snooker`` (uint8) ``[log_rows, n_chains]``, and ``archive`` ``[n_sel, n_archive, ld]`` (None unless asked for):
+    ``z0`` followed by the chains' states at the append generations. ``m0``: the rows of ``z0``."""
+
+    n_null: Optional[np.ndarray] = None
+    ljac: Optional[np.ndarray] = None
+    snooker: Optional[np.ndarray] = None
+    archive: Optional[np.ndarray] = None
+    n_archive: int = 0
+    m0: int = 0
+
+    @classmethod
+    def empty_zs(cls, n: int, n_pop: int, ld: int, n_gen: int, thin: int, log_rows: int, m0: int, append_every: int,
+                 archive: bool) -> "DemcZs":
+        base = Demc.empty(n, n_pop, ld, n_gen, thin, log_rows)
+        G, B = base.logr.shape
+        M = int(m0) + n_pop * (int(n_gen) // max(int(append_every), 1))
+        return cls(**{f.name: getattr(base, f.name) for f in dataclasses.fields(Demc)},
+                   n_null=np.zeros((n, n_pop), np.int32), ljac=np.full((G, B), np.nan), snooker=np.zeros((G, B), np.uint8),
+                   archive=np.full((n, M, ld), np.nan) if archive else None, n_archive=M, m0=int(m0))
+
+    def to_c(self) -> "_lib.tci_demczs_outputs":
+        base = Demc.to_c(self)
+        P = lambda a: _lib.ptr(a, _lib._dp) if a is not None and a.size else None  # noqa: E731
+        return _lib.tci_demczs_outputs(*[getattr(base, f) for f, _ in _lib.tci_demc_outputs._fields_],
+                                       _lib.ptr(self.n_null, _lib._i32p), P(self.ljac),
+                                       _lib.ptr(self.snooker, _lib._u8p) if self.snooker.size else None, P(self.archive), 0)
+
+
 class Likelihood:
     """SS evaluator bound to one device and one dataset (the C ``tci_ctx``)."""
 
@@ -1144,6 +1176,72 @@ class Likelihood:
         else:
             self._check(self._lib.tci_demc_run(*args))
         dm.kernel_ms = float(out.kernel_ms)
+        if cr is not None:
+            cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
+        if ce is not None:
+            ce.n_rows, ce.kernel_ms = int(eout.n_rows), float(eout.kernel_ms)
+        dm.rhat, dm.ess = cr, ce
+        return dm
+
+    def demczs(self, pop0: np.ndarray, z0: np.ndarray, cell_id: Sequence[int], lower: np.ndarray, upper: np.ndarray,
+               prior_mu: np.ndarray, prior_sig: np.ndarray, jitter: np.ndarray, sigma2_0=1.0, n_gen: int = 1000,
+               thin: int = 1, jump_every: int = 10, CR: float = 0.2, gamma0: float = 0.0, updatesigma: bool = True,
+               seed: int = 0, keys=None, stats_from: int = 0, append_every: int = 10, p_snooker: float = 0.1,
+               rhat: bool = False, ess: bool = False, max_lag: int = 0, log_rows: int = 0, flags: int = 0, rank=False,
+               archive: bool = False) -> DemcZs:
+        """DE-MC(zs) (ter Braak & Vrugt 2008) on the device (``tci_demczs_run``; the definition is in ``include/tci.h``):
+        ``n_pop`` chains per cell whose proposals come from an archive of past states, with snooker moves. ``pop0``
+        ``[n_sel, n_pop, ld]``: the chains' starts; ``z0`` ``[n_sel, m0, ld]``: the starting archive of every cell,
+        ``m0 >= 3`` rows inside ``[lower, upper]``; ``append_every``: the chains' states join the archive after every
+        such generation; ``p_snooker``: the share of snooker moves; ``archive``: also return the final archive.
+        Everything else is :meth:`demc`'s. Returns a :class:`DemcZs`."""
+        pop0 = np.ascontiguousarray(pop0, np.float64)
+        z0 = np.ascontiguousarray(z0, np.float64)
+        if pop0.ndim != 3:
+            raise ValueError("pop0 must be [n_sel, n_pop, ld]")
+        n, n_pop, ld = pop0.shape
+        if z0.ndim != 3 or z0.shape[0] != n or z0.shape[2] != ld:
+            raise ValueError("z0 must be [n_sel, m0, ld]")
+        m0 = z0.shape[1]
+        cid = np.ascontiguousarray(np.atleast_1d(cell_id), np.int32)
+        if cid.shape != (n,):
+            raise ValueError("cell_id must have one entry per population")
+        for name, v in (("n_gen", n_gen), ("thin", thin), ("log_rows", log_rows)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 0:
+                raise ValueError(f"{name} must be an integer >= 0")
+        if isinstance(append_every, bool) or int(append_every) != append_every:
+            raise ValueError("append_every must be an integer")
+        f = lambda a: np.ascontiguousarray(np.asarray(a, np.float64).reshape(n, ld))  # noqa: E731
+        lo, up, mu, sig, jit = f(lower), f(upper), f(prior_mu), f(prior_sig), f(jitter)
+        s2v = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma2_0, np.float64), (n,)))
+        kv = None if keys is None else np.ascontiguousarray(keys, np.int64)
+        if kv is not None and kv.shape != (n,):
+            raise ValueError("keys must have one entry per population")
+        # an archive the library will refuse (its own message) is not allocated here
+        ok = int(append_every) >= 1 and m0 + n_pop * (int(n_gen) // max(int(append_every), 1)) < 2 ** 24
+        dm = DemcZs.empty_zs(n, n_pop, ld, int(n_gen), int(thin), int(log_rows), m0, int(append_every), archive and ok)
+        opt = _lib.tci_demczs_options(int(n_gen), int(thin), int(jump_every), int(stats_from), int(updatesigma), float(CR),
+                                      float(gamma0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(kv, _lib._i64p), int(flags),
+                                      int(append_every), float(p_snooker))
+        out = dm.to_c()
+        cr = ChainRhat.empty(n, ld) if rhat else None
+        ce = ChainEss.empty(n, ld, max_lag) if ess else None
+        ropt, rout = (cr.options(), cr.to_c()) if cr is not None else (None, None)
+        eopt, eout = (ce.options(), ce.to_c()) if ce is not None else (None, None)
+        R = lambda x: None if x is None else C.byref(x)  # noqa: E731
+        P = lambda a: _lib.ptr(a, _lib._dp)  # noqa: E731
+        ck = None
+        if rank is not None and rank is not False:
+            ck = ChainRank.empty(n, ld, max_lag=max_lag, **({} if rank is True else dict(rank)))
+        args = (self._h, C.byref(opt), P(pop0), P(z0), ld, _lib.ptr(cid, _lib._i32p), n, n_pop, m0, P(lo), P(up), P(mu),
+                P(sig), P(jit), P(s2v), C.byref(out), R(ropt), R(rout), R(eopt), R(eout))
+        if ck is not None:
+            kopt, kout = ck.options(), ck.to_c()
+            self._check(self._lib.tci_demczs_run_rank(*args, C.byref(kopt), C.byref(kout)))
+            dm.rank = ck.taken(kout)
+        else:
+            self._check(self._lib.tci_demczs_run(*args))
+        dm.kernel_ms, dm.n_archive = float(out.kernel_ms), int(out.n_archive)
         if cr is not None:
             cr.n_rows, cr.kernel_ms = int(rout.n_rows), float(rout.kernel_ms)
         if ce is not None:

@@ -29,7 +29,7 @@ import numpy as np
 from . import _lib
 from .data import Cells, draw_x0
 from .likelihood import (FITCHECK_POINTWISE, ChainCov, ChainDens, ChainEss, ChainLp, ChainQuant, ChainRank, ChainRhat, ChainStats,
-                         Demc, FitCheck, ModeSearch, rhat_groups)
+                         Demc, DemcZs, FitCheck, ModeSearch, rhat_groups)
 
 RESULT_FIELDS = ("mean_v", "sigma_v", "mean_ton", "sigma_ton", "mean_A", "sigma_A", "mean_tau", "sigma_tau",
                  "mean_MS2_basal", "sigma_MS2_basal", "mean_PP7_basal", "sigma_PP7_basal", "mean_R", "sigma_R",
@@ -101,6 +101,11 @@ PRESEARCH_KEYS = ("n_pop", "n_gen", "F", "CR")
 # MCMCdemc (fit(..., demc=dict(...))): the DE-MC population sampler's per-cell record
 DEMC_FIELDS = ("accept_rate", "n_oob", "rhat_max", "ess_min", "n_pop", "n_gen", "n_evals", "cell_index")
 DEMC_KEYS = ("n_pop", "n_gen", "CR", "gamma0", "jump_every", "jitter", "updatesigma")
+# MCMCdemczs (fit(..., demczs=dict(...))): the DE-MC(zs) sampler's per-cell record: MCMCdemc's fields plus the null
+# snooker moves per chain, the share of snooker moves (NaN without the log), the starting and the final archive rows
+DEMCZS_FIELDS = DEMC_FIELDS + ("n_null", "snooker_rate", "m0", "n_archive")
+DEMCZS_KEYS = DEMC_KEYS + ("m0", "append_every", "p_snooker")
+ZS_FIT_LOG_ROWS = 1024   # the generations a demczs fit logs: snooker_rate is the share of snooker moves among them
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
 # sit there: cells below 2^24, at most 2^8 replicates, and every key below 2^32.
@@ -467,6 +472,7 @@ class FitResult:
     MCMCcheck: Optional[List[Dict]] = None     # fitcheck(lk, fit_result): CHECK_FIELDS per fitted cell
     MCMCsearch: Optional[List[Dict]] = None    # fit(..., presearch=dict(...)): SEARCH_FIELDS per fitted cell
     MCMCdemc: Optional[List[Dict]] = None      # fit(..., demc=dict(...)): DEMC_FIELDS per fitted cell
+    MCMCdemczs: Optional[List[Dict]] = None    # fit(..., demczs=dict(...)): DEMCZS_FIELDS per fitted cell
     MCMCtemper: Optional[List[Dict]] = None    # fit(..., temper=R): TEMPER_FIELDS per fitted cell
     MCMCstack: Optional[List[Dict]] = None     # fit(..., stack=nsample): STACK_FIELDS per fitted cell
     MCMClp: Optional[List[Dict]] = None        # fit(..., logpost=True): LP_FIELDS (+ LP_GROUP_FIELDS) per fitted cell
@@ -589,7 +595,7 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
         max_lag: int = 0, covariance: bool = False, quantiles=None, density=None, replicates: int = 1,
         rhat: Optional[bool] = None, ess: bool = False, logpost: bool = False,
         stack: Optional[int] = None, temper=None, swap_every: int = 1, presearch: Optional[Mapping] = None,
-        demc: Optional[Mapping] = None, rank=False) -> FitResult:
+        demc: Optional[Mapping] = None, rank=False, demczs: Optional[Mapping] = None) -> FitResult:
     """``TranscriptionCycleMCMC`` for one dataset on the GPU: one DRAM chain per cell.
 
     ``lk``: a ``Likelihood`` holding the (truncated) cells. ``v0``: the previous fit of a
@@ -690,8 +696,31 @@ def fit(lk, n_steps: int = 20000, n_burn: int = 10000, ratePriorWidth: float = 5
     ``accept_rate``: the members' mean), and ``MCMCdemc`` holds one dict of ``DEMC_FIELDS`` per fitted cell, R-hat and
     the multi-chain ESS across the members reduced on the device. With ``presearch`` the population starts from the
     search's final one (its ``n_pop`` is the sampler's). It cannot be combined with ``temper`` or ``replicates``, which
-    are DRAM's, nor with the DRAM reductions. ``demc=None`` (the default) is today's fit bit for bit."""
+    are DRAM's, nor with the DRAM reductions. ``demc=None`` (the default) is today's fit bit for bit.
+
+    ``demczs``: a dict with keys among ``DEMCZS_KEYS`` (defaults: :func:`demczs`'s): the cells are sampled by the
+    DE-MC(zs) sampler (include/tci.h, ``tci_demczs_run``): ``n_pop`` chains per cell (default 4) that propose from an
+    archive of past states. Everything said of ``demc`` holds, the chains taking the members' place; ``MCMCdemczs`` holds
+    one dict of ``DEMCZS_FIELDS`` per fitted cell. With ``presearch`` the search runs ``m0`` members, its final
+    population is the archive and the chains start at its best members. ``snooker_rate`` is the share of snooker moves
+    among the first ``ZS_FIT_LOG_ROWS`` (1,024) generations, the ones the fit logs, not of the whole run. Rows kept while the archive is young are
+    burn-in: ``n_burn`` is the caller's to set. Exclusive with ``demc`` too. ``demczs=None`` (the default) is today's
+    fit bit for bit."""
     M = int(replicates)
+    if demczs is not None:
+        if demc is not None:
+            raise ValueError("demczs and demc are two samplers: give one")
+        if M != 1 or _temper_arg(temper)[1] > 1:
+            raise ValueError("demczs is a sampler of its own: it cannot be combined with temper or replicates (its "
+                             "chains are the cell's chains)")
+        want_rank = rank is not None and rank is not False
+        if want_rank and not isinstance(rank, (bool, Mapping)):
+            raise ValueError("rank must be True or a dict with keys among ('probs', 'tail')")
+        if diagnostics or covariance or quantiles is not None or density or logpost or stack is not None or rhat or ess:
+            raise ValueError("demczs does not take the DRAM reductions (diagnostics, covariance, quantiles, density, "
+                             "rhat, ess, logpost, stack): MCMCdemczs holds R-hat and ESS across the chains")
+        return _fit_demc(lk, demczs, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch,
+                         max_lag, rank if want_rank else False, zs=True)
     ps = _presearch_arg(presearch, M)
     betas, R = _temper_arg(temper)
     if demc is not None:
@@ -1023,14 +1052,16 @@ def demc_entry(res: Demc, k: int, n: int, cell_index: int) -> Dict:
 
 
 def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, cells, cell_offset, presearch, max_lag,
-              rank=False):
-    """:func:`fit` with the DE-MC sampler: every result field from the kept rows of all members pooled."""
-    kw = _demc_arg(demc_arg)
+              rank=False, zs=False):
+    """:func:`fit` with the DE-MC sampler, or with ``zs`` the DE-MC(zs) sampler: every result field from the kept rows of
+    all members (chains) pooled."""
+    name = "demczs" if zs else "demc"
+    kw = _demczs_arg(demc_arg) if zs else _demc_arg(demc_arg)
     if int(thin) < 1:
-        raise ValueError("a DE-MC fit is reduced from the kept rows: demc needs thin >= 1")
+        raise ValueError(f"a DE-MC fit is reduced from the kept rows: {name} needs thin >= 1")
     n_gen, n_pop = int(kw["n_gen"]), int(kw["n_pop"])
     if n_gen // int(thin) + 1 - -(-int(n_burn) // int(thin)) < 2:
-        raise ValueError("demc needs at least 2 kept generations at or past n_burn")
+        raise ValueError(f"{name} needs at least 2 kept generations at or past n_burn")
     cl: Cells = lk.cells
     off = int(cell_offset)
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
@@ -1040,16 +1071,20 @@ def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, ce
     ps = None
     searched = None
     if presearch is not None:
-        pk = _presearch_arg({**presearch, "n_pop": presearch.get("n_pop", n_pop)}, 1)
-        if int(pk.pop("n_pop")) != n_pop:
-            raise ValueError("presearch n_pop must be the sampler's n_pop")
-        ps = modesearch(lk, n_pop=n_pop, seed=seed, cells=keep, v0=v0, cell_offset=off, ratePriorWidth=ratePriorWidth,
+        n_search = n_pop      # the search's members: the population, or with zs the starting archive
+        if zs:
+            n_search = kw["m0"] = int(kw.get("m0") or demczs_m0(cl, keep))
+        pk = _presearch_arg({**presearch, "n_pop": presearch.get("n_pop", n_search)}, 1)
+        if int(pk.pop("n_pop")) != n_search:
+            raise ValueError("presearch n_pop must be the sampler's " + ("m0" if zs else "n_pop"))
+        ps = modesearch(lk, n_pop=n_search, seed=seed, cells=keep, v0=v0, cell_offset=off, ratePriorWidth=ratePriorWidth,
                         approved=approved, **pk)
         searched = [search_entry(ps[0], k, int(cl.lengths[c]), off + c + 1) for k, c in enumerate(keep)]
-    res, sp = demc(lk, thin=int(thin), n_burn=int(n_burn), seed=seed, cells=keep, v0=v0, presearch=ps, cell_offset=off,
-                   ratePriorWidth=ratePriorWidth, max_lag=max_lag, approved=approved, rank=rank, **kw)
+    res, sp = (demczs if zs else demc)(lk, thin=int(thin), n_burn=int(n_burn), seed=seed, cells=keep, v0=v0, presearch=ps,
+                                       cell_offset=off, ratePriorWidth=ratePriorWidth, max_lag=max_lag, approved=approved,
+                                       rank=rank, **({"log_rows": min(n_gen, ZS_FIT_LOG_ROWS)} if zs else {}), **kw)
     if sp.cells != keep:
-        raise RuntimeError(f"demc sampled cells {sp.cells}, the fit keeps {keep}")
+        raise RuntimeError(f"{name} sampled cells {sp.cells}, the fit keeps {keep}")
     K = len(keep)
     ld = res.pop.shape[2]
     sel = int(thin) * np.arange(res.chain.shape[0]) >= int(n_burn)
@@ -1083,13 +1118,102 @@ def _fit_demc(lk, demc_arg, n_burn, ratePriorWidth, seed, v0, approved, thin, ce
         ch["dR_chain"] = th[:, 7:].copy()
         ch["s2chain"] = sq.copy()
         chains.append(ch)
-        entries.append(demc_entry(res, k, n, off + c + 1))
+        entries.append((demczs_entry if zs else demc_entry)(res, k, n, off + c + 1))
         if res.rank is not None:   # the rank diagnostics across the members, beside rhat_max / ess_min
             rk = rank_entry(res.rank, k, n, off + c + 1, n_pop)
             entries[-1].update({f: rk[f] for f in RANK_FIELDS if f not in DEMC_FIELDS})
     return FitResult(cl.name, results, plots, chains, res.accept_rate.mean(axis=1), int(res.n_evals.sum()),
                      res.kernel_ms, np.array(keep, np.int64) + off, res.pop[:, 0].copy(), MCMCsearch=searched,
-                     MCMCdemc=entries)
+                     **{"MCMCdemczs" if zs else "MCMCdemc": entries})
+
+
+def _demczs_arg(arg):
+    """``fit``'s ``demczs`` as keyword arguments of :func:`demczs`."""
+    if not isinstance(arg, Mapping):
+        raise ValueError(f"demczs must be a dict with keys among {DEMCZS_KEYS}")
+    bad = sorted(set(arg) - set(DEMCZS_KEYS))
+    if bad:
+        raise ValueError(f"demczs has unknown keys {bad}: the keys are {DEMCZS_KEYS}")
+    d = dict(arg)
+    n_pop = d.setdefault("n_pop", 4)
+    if isinstance(n_pop, bool) or int(n_pop) != n_pop or not 1 <= int(n_pop) <= 4096:
+        raise ValueError("demczs n_pop must be an integer in [1, 4096]")
+    n_gen = d.setdefault("n_gen", 1000)
+    if isinstance(n_gen, bool) or int(n_gen) != n_gen or int(n_gen) < 1:
+        raise ValueError("demczs n_gen must be an integer >= 1")
+    m0 = d.get("m0")
+    if m0 is not None and (isinstance(m0, bool) or int(m0) != m0 or int(m0) < max(3, int(n_pop))):
+        raise ValueError("demczs m0 must be an integer >= max(3, n_pop): the chains start at the archive's first rows")
+    return d
+
+
+def demczs_m0(cl: Cells, ids: Sequence[int]) -> int:
+    """The default starting archive of :func:`demczs`: ``10 P`` rows, ``P = 7 + N`` of the longest of the cells ``ids``
+    (ter Braak & Vrugt's ``M0 = 10 d``)."""
+    return 10 * (7 + max((int(cl.lengths[int(c)]) for c in ids), default=0))
+
+
+def demczs(lk, n_pop: int = 4, m0: Optional[int] = None, n_gen: int = 1000, thin: int = 1, n_burn: int = 0, seed: int = 0,
+           cells: Optional[Sequence[int]] = None, v0=None, presearch=None, cell_offset: int = 0,
+           ratePriorWidth: float = 50.0, jitter=None, CR: float = 0.2, gamma0: float = 0.0, jump_every: int = 10,
+           updatesigma: bool = True, sigma2_0=1.0, append_every: int = 10, p_snooker: float = 0.1, rhat: bool = True,
+           ess: bool = True, max_lag: int = 0, log_rows: int = 0, approved=None, rank=False, archive: bool = False):
+    """A DE-MC(zs) run (``Likelihood.demczs``; include/tci.h, ``tci_demczs_run``) of the cells ``cells`` (default: all)
+    of ``lk``: ``n_pop`` chains per cell and a starting archive of ``m0`` rows (None: :func:`demczs_m0`, ``10 P`` of the
+    longest selected cell; ``m0 >= max(3, n_pop)``). The archive ``z0`` is :func:`search_population` with ``m0`` members
+    and the chains start at its first ``n_pop`` rows, so chain ``i`` starts at replicate ``i``'s x0. With ``presearch``
+    (a dict for :func:`modesearch`, run here with ``m0`` members and the same ``seed``, or the ``(ModeSearch,
+    SearchPlan)`` such a call returned) ``z0`` is the search's final population and the chains start at its best
+    members (:func:`search_order`). Keys, seeds, ``jitter``, ``n_burn``, ``rank`` and the reductions are :func:`demc`'s.
+    Returns ``(DemcZs, SearchPlan)``; row ``k`` of either is cell ``plan.cells[k]``, and ``plan.pop0`` is ``z0``."""
+    cl: Cells = lk.cells
+    ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
+    n_pop = int(n_pop)
+    if isinstance(presearch, tuple):
+        m0 = int(presearch[0].pop.shape[1]) if m0 is None else int(m0)
+    m0 = demczs_m0(cl, kept_cells(cl, ids, v0, int(cell_offset))) if m0 is None else int(m0)
+    if m0 < max(3, n_pop):
+        raise ValueError("m0 must be >= max(3, n_pop): the chains start at the archive's first rows")
+    if isinstance(presearch, tuple):
+        sr, sp = presearch
+        if sr.pop.shape[1] != m0:
+            raise ValueError("the mode search's n_pop is not the sampler's m0")
+    elif presearch is not None:
+        if not isinstance(presearch, Mapping) or set(presearch) - {"n_gen", "F", "CR"}:
+            raise ValueError("presearch must be a dict with keys among ('n_gen', 'F', 'CR') or a modesearch result")
+        sr, sp = modesearch(lk, n_pop=m0, seed=seed, cells=ids, v0=v0, cell_offset=cell_offset,
+                            ratePriorWidth=ratePriorWidth, approved=approved, **presearch)
+    else:
+        sr, sp = None, search_population(cl, ids, seed, m0, ratePriorWidth, v0, approved, cell_offset)
+    if not sp.cells:
+        return DemcZs.empty_zs(0, n_pop, sp.pop0.shape[2], int(n_gen), int(thin), 0, m0, max(int(append_every), 1), False), sp
+    if sr is None:
+        z0 = sp.pop0
+        pop0 = z0[:, :n_pop]
+    else:
+        z0 = sr.pop
+        pop0 = np.stack([z0[k, search_order(sr.f[k])[:n_pop]] for k in range(len(sp.cells))])
+    jit = jitter
+    if jit is None or np.ndim(jit) == 0:
+        base = demc_jitter(cl, sp.cells, ratePriorWidth, v0, approved, cell_offset)
+        jit = base if jit is None else float(jit) * base
+    res = lk.demczs(pop0, z0, np.array(sp.cells, np.int32), sp.lower, sp.upper, sp.prior_mu, sp.prior_sig, jit,
+                    sigma2_0=sigma2_0, n_gen=n_gen, thin=thin, jump_every=jump_every, CR=CR, gamma0=gamma0,
+                    updatesigma=updatesigma, seed=int(seed) * 1000003 + 20201028,
+                    keys=np.array(sp.cells, np.int64) + int(cell_offset), stats_from=n_burn, append_every=append_every,
+                    p_snooker=p_snooker, rhat=rhat, ess=ess, max_lag=max_lag, log_rows=log_rows, rank=rank, archive=archive)
+    return res, sp
+
+
+def demczs_entry(res: DemcZs, k: int, n: int, cell_index: int) -> Dict:
+    """One ``MCMCdemczs`` entry (``DEMCZS_FIELDS``) from selected cell ``k`` of ``res``: :func:`demc_entry`'s values plus
+    ``n_null`` per chain, ``snooker_rate`` (the share of snooker moves among the generations ``res`` logged, its first
+    ``log_rows``: not of the whole run when the log is shorter; NaN without a log), ``m0`` and ``n_archive``."""
+    n_pop = int(res.pop.shape[1])
+    snk = res.snooker[:, k * n_pop:(k + 1) * n_pop]
+    d = dict(demc_entry(res, k, n, cell_index), n_null=res.n_null[k].copy(),
+             snooker_rate=float(snk.mean()) if snk.size else float("nan"), m0=int(res.m0), n_archive=int(res.n_archive))
+    return {f: d[f] for f in DEMCZS_FIELDS}
 
 
 def search_order(f: np.ndarray) -> np.ndarray:
