@@ -103,6 +103,57 @@ def test_butterfly_sum_is_the_six_fold_numpy_fold():
     assert any(O.sum64(r) != np.add.reduce(r) or O.sum64(r) != sum(r.tolist()) for r in x)
 
 
+def test_butterfly_sum_at_the_lane_edges_and_the_longest_row():
+    """The shapes of tests/test_demczs_shapes_gpu.py: n = 9 (lanes 9 to 63 add nothing), 64 and 128 (every trip full), 65
+    and 129 (the last trip holds lane 0 alone) and 2055 (33 terms in lanes 0 to 6, 32 in the others). Terms of mixed sign
+    over 16 decades, so that the association order decides the low bits."""
+    rs = np.random.default_rng(4)
+    x = rs.normal(size=(6, 2056)) * 10.0 ** rs.integers(-8, 8, (6, 2056))
+    assert np.all((x > 0).any(axis=1) & (x < 0).any(axis=1))
+    differs = 0
+    for n in (9, 64, 65, 128, 129, 2055):
+        want = [O.sum64_loops(r[:n]) for r in x]
+        np.testing.assert_array_equal(O.sum64(x[:, :n]), want)
+        assert all(O.sum64(r[:n]) == w for r, w in zip(x, want))
+        differs += sum(w != sum(r[:n].tolist()) for r, w in zip(x, want))
+        # one term more or fewer in the last trip changes the sum: the count is not rounded to a trip
+        assert any(O.sum64(r[:n]) != O.sum64(r[:n - 1]) for r in x) and any(O.sum64(r[:n]) != O.sum64(r[:n + 1]) for r in x)
+    assert differs > 0      # the plain ascending sum is another order
+
+
+@pytest.mark.parametrize("M", [2 ** 16 + 5, 2 ** 24 - 1])
+def test_index_rule_at_archives_past_2_16_rows(M):
+    """m(w, n) = floor(w n / 2^32) in Python integers, where the product needs up to 56 bits, on the words 0, 2^32 - 1 and
+    some between: three distinct rows in range from scale_rule, and the same rows from index_draws' uint64 arithmetic on
+    the generator's words."""
+    words = (0, 1, 2 ** 16 - 1, 2 ** 16, 0x7FFFFFFF, 0x80000000, 0xFFFF0000, 2 ** 32 - 2, 2 ** 32 - 1)
+    m = lambda w, n: w * n // 2 ** 32   # noqa: E731
+
+    def rule(wx, wy, ww):
+        a, c, e = m(wx, M), m(wy, M - 1), m(ww, M - 2)
+        c += c >= a
+        e += e >= min(a, c)
+        e += e >= max(a, c)
+        return a, c, e
+
+    assert m(2 ** 32 - 1, M) == M - 1 and m(2 ** 32 - 1, M - 2) == M - 3 and m(0, M) == 0
+    assert m(2 ** 16, M) == M >> 16 and m(0x80000000, M) == M >> 1      # a 32-bit product would lose these
+    top = 0
+    for wx, wy, ww in itertools.product(words, repeat=3):
+        a, c, e = got = O.scale_rule(wx, wy, ww, M)
+        assert got == rule(wx, wy, ww) and len({a, c, e}) == 3 and 0 <= min(got) and max(got) < M
+        top = max(top, *got)
+    assert top == M - 1 and O.scale_rule(0, 0, 0, M) == (0, 1, 2)
+    assert O.scale_rule(2 ** 32 - 1, 2 ** 32 - 1, 2 ** 32 - 1, M) == (M - 1, M - 2, M - 3)
+    n_pop, P = 4096, 9
+    a, c, e, jr, _, _ = O.index_draws(7, 3, 5, n_pop, M, P, 0.5)
+    w = D.rng_vec(7, 3, 5, O.P_INDEX, np.arange(n_pop))
+    want = [rule(int(w[0][i]), int(w[1][i]), int(w[3][i])) for i in range(n_pop)]
+    np.testing.assert_array_equal(np.stack([a, c, e], axis=1), np.array(want, np.int64))
+    assert [int(v) for v in jr] == [m(int(v), P) for v in w[2]]
+    assert max(a.max(), c.max(), e.max()) >= M - M // 256 and a.dtype == np.int64   # 12,288 draws reach the top 1/256
+
+
 def test_the_parallel_move_at_once_is_demc_oracles_trial():
     rs = np.random.default_rng(3)
     P, ld, n = 120, 125, 6
