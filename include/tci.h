@@ -1328,6 +1328,66 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
                         tci_chainrhat_outputs* rout, const tci_chainess_options* eopt, tci_chainess_outputs* eout,
                         const tci_chainrank_options* kopt, tci_chainrank_outputs* kout);
 
+/* ---- DE-MC(zs): per-coordinate bounds census and oriented reflection ----
+ * tci_demczs_run_rank with two optional additions; everything not said here is tci_demczs_run's, bit for bit.
+ * Census (census = 1, in either mode). For every generation g >= 1, chain b and coordinate j < P that CROSSES,
+ *   n_cross[b][j] += 1; with t_j the RAW trial coordinate (before any reflection), oob_lo[b][j] += 1 if t_j < lower_j
+ *   and oob_hi[b][j] += 1 if t_j > upper_j. A NaN counts in neither (the row's n_oob still catches it). In a parallel
+ *   move the crossing coordinates are those of the crossover mask (all of them in a jump generation); in a snooker move
+ *   every j < P crosses. n_left[g - 1][b] is the proposal's count of such coordinates, -1 for a null move; a null move
+ *   touches no counter. Hence SUM_j (oob_lo + oob_hi)[b][j] = SUM_g n_left[g - 1][b] over the non-null moves when the
+ *   log holds every generation, and in reject mode with NaN-free inputs n_left > 0 iff trial_oob == 1.
+ * Reflect mode (mode = TCI_BOUNDS_REFLECT). Plain reflection of a leaving coordinate is NOT valid here: the difference
+ *   of two archive rows is symmetric under d -> -d only, not under negating some coordinates. The valid form remembers
+ *   its orientation. Unfold every coordinate onto a circle of circumference 2 w (the box and its mirror image), run the
+ *   unchanged proposal there and store the state as the box coordinate plus one orientation bit per coordinate: an
+ *   increment is applied with the sign of the bit and a reflection flips it. That is Metropolis on the unfolded torus
+ *   with a translation-invariant proposal, which needs the d -> -d symmetry alone, and its marginal on the box is the
+ *   target. Each chain carries orient[b][j] in {0, 1}, all 0 at the start (entries j >= P stay 0).
+ *   Parallel move, crossing j, with tci_demc_run's s = gamma * d and zz = jitter_j * f: s' = orient ? -s : s,
+ *     zz' = orient ? -zz : zz (negation is exact), y = x_j + s', t = y + zz', every other operation as in reject mode:
+ *     with every bit 0 the raw trial has reject mode's bits. Then at most one reflection: if t < lower, e = lower - t
+ *     and t' = lower + e; if t > upper, e = t - upper and t' = upper - e (a subtraction, then an addition or a
+ *     subtraction, as written). The trial's bit is orient ^ 1 for a reflected coordinate, orient otherwise. If t' is
+ *     NaN or still outside [lower, upper] (the overshoot exceeds the width) the proposal is rejected at the bounds as
+ *     in reject mode: a second reflection is needed exactly when the unfolded segment crosses two wall points, and the
+ *     reverse move crosses the same two, so the reject set is symmetric and the rule stays valid. n_refl[g - 1][b]
+ *     counts the coordinates a reflection was applied to, whether or not the proposal then stayed inside; n_reflected[b]
+ *     counts the evaluated proposals with n_refl > 0. An accepted trial's orientation row replaces the chain's.
+ *   Snooker move: reject mode's rule in both modes, orient unchanged (a valid move on x alone), n_refl = 0.
+ *   The archive, the kept rows, sschain, prichain, the reductions and the prior are in box coordinates, as always.
+ * Census outputs: n_cross, oob_lo, oob_hi, n_left. Reflection outputs: n_refl, n_reflected, orient. */
+#define TCI_BOUNDS_REJECT 0  /* tci_demczs_run's rule */
+#define TCI_BOUNDS_REFLECT 1
+typedef struct {
+  int32_t mode;   /* TCI_BOUNDS_REJECT (default) or TCI_BOUNDS_REFLECT */
+  int32_t census; /* 0 (default) or 1 */
+  int64_t flags;  /* reserved, must be 0 */
+} tci_bounds_options;
+
+/* Host buffers (any pointer may be NULL); log_rows is tci_demczs_outputs'. */
+typedef struct {
+  int32_t *n_cross, *oob_lo, *oob_hi; /* [n_chains][ld]; padding j >= P is -1 */
+  int32_t* n_left;      /* [log_rows][n_chains]: coordinates of the raw trial outside; -1 for a null move */
+  int32_t* n_refl;      /* [log_rows][n_chains]: coordinates reflected (0 in reject mode and for snooker moves) */
+  int32_t* n_reflected; /* [n_chains]: evaluated proposals with at least one reflection */
+  uint8_t* orient;      /* [n_chains][ld]: the final orientation bits */
+} tci_bounds_outputs;
+
+int tci_bounds_defaults(tci_bounds_options* opt);
+
+/* bopt and bout both NULL: exactly tci_demczs_run_rank. bopt NULL means the defaults. After tci_demczs_run_rank's
+ * checks and before any device work, TCI_EINVAL naming the field for mode outside {0, 1}, census outside {0, 1},
+ * flags != 0, a census output given with census = 0, a reflection output given in reject mode. With mode 0 and
+ * census 0 the call makes tci_demczs_run_rank's device allocations, launches and copies and nothing else. */
+int tci_demczs_run_bounds(tci_ctx* ctx, const tci_demczs_options* opt, const double* pop0, const double* z0, int64_t ld,
+                          const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower,
+                          const double* upper, const double* prior_mu, const double* prior_sig, const double* jitter,
+                          const double* sigma2_0, tci_demczs_outputs* out, const tci_chainrhat_options* ropt,
+                          tci_chainrhat_outputs* rout, const tci_chainess_options* eopt, tci_chainess_outputs* eout,
+                          const tci_chainrank_options* kopt, tci_chainrank_outputs* kout, const tci_bounds_options* bopt,
+                          tci_bounds_outputs* bout);
+
 const char* tci_version(void);
 
 #ifdef __cplusplus

@@ -77,6 +77,12 @@ function [MCMCresults, MCMCplot, MCMCchain, MCMCdiag, MCMClp, MCMCstack, MCMCtem
 %        take. Fills the eleventh output MCMCdemczs: MCMCdemc's fields plus n_null (1 x n_pop), snooker_rate (the
 %        share of snooker moves among the first min(n_gen, 1024) generations, the ones that are logged), m0 and
 %        n_archive. Not with 'demc'.)
+%     'bounds' ('reject'; with 'demczs': 'reflect' reflects a coordinate that leaves its box back into it, with an
+%        orientation bit per coordinate, instead of rejecting the proposal (tci_demczs_run_bounds, include/tci.h);
+%        MCMCdemczs gains reflect_rate, the evaluated proposals with a reflection over all proposals.)
+%     'census' (0; with 'demczs': 1 counts, per coordinate, how often it crossed and how often it left below or
+%        above its bound; MCMCdemczs gains n_cross, oob_lo, oob_hi (1 x 7+N, summed over the chains) and oob_share,
+%        (oob_lo + oob_hi) over the cell's bounds-rejected proposals (NaN with 'reflect').)
 %     'rank' (0; 1 fills the tenth output MCMCrank, one entry per fitted cell, with the rank diagnostics of Vehtari et
 %        al. (2021) over the kept rows at or past n_burn (tci_chainrank, include/tci.h; options.rank of
 %        tci_mex('dram') / tci_mex('demc'), reduced from the device chain): across the cell's DE-MC members with
@@ -118,6 +124,8 @@ p.addParameter('swap_every', 1);
 p.addParameter('presearch', []);
 p.addParameter('demc', []);
 p.addParameter('demczs', []);
+p.addParameter('bounds', 'reject');
+p.addParameter('census', 0);
 p.addParameter('rank', 0);
 p.parse(varargin{:});
 o = p.Results;
@@ -333,6 +341,11 @@ if ~isempty(dm)                                     % ---- the DE-MC fit: every 
             C0(:, (k-1)*n_pop + (1:n_pop)) = Z0(:, (k-1)*m0 + pick);
         end
         dopts.log_rows = min(dm(2), 1024);
+        if ~(ischar(o.bounds) && any(strcmp(o.bounds, {'reject', 'reflect'})))
+            error('tci:demczs', 'bounds must be ''reject'' or ''reflect''');
+        end
+        dopts.bounds = o.bounds;
+        dopts.census = double(o.census ~= 0);
         D = tci_mex('demczs', h, 1:nc, C0, Z0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, dopts);
     else
         D = tci_mex('demc', h, 1:nc, POP0, LB(:, 1:nc), UB(:, 1:nc), MU(:, 1:nc), SIG(:, 1:nc), JIT, sigma2_0, dopts);
@@ -371,6 +384,18 @@ if ~isempty(dm)                                     % ---- the DE-MC fit: every 
             dk.snooker_rate = mean(mean(D.snooker(mem, :)));
             dk.m0 = m0;
             dk.n_archive = D.n_archive;
+            if dopts.census
+                dk.n_cross = sum(D.n_cross(1:7+n, :, k), 2)';
+                dk.oob_lo = sum(D.oob_lo(1:7+n, :, k), 2)';
+                dk.oob_hi = sum(D.oob_hi(1:7+n, :, k), 2)';
+                dk.oob_share = nan(1, 7+n);
+                if strcmp(o.bounds, 'reject') && sum(D.n_oob(:, k)) > 0
+                    dk.oob_share = (dk.oob_lo + dk.oob_hi) / sum(D.n_oob(:, k));
+                end
+            end
+            if strcmp(o.bounds, 'reflect')
+                dk.reflect_rate = sum(D.n_reflected(:, k)) / (n_pop*dm(2));
+            end
             if isempty(MCMCdemczs), MCMCdemczs = dk; else, MCMCdemczs(k) = dk; end
         else
             if isempty(MCMCdemc), MCMCdemc = dk; else, MCMCdemc(k) = dk; end

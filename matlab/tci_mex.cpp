@@ -142,10 +142,12 @@
 //   out = tci_mex('demczs', h, cells, POP0, Z0, LB, UB, MU, SIG, JIT[, sigma2[, options]])
 //          the DE-MC(zs) sampler (ter Braak & Vrugt 2008; tci_demczs_run, the definition is in include/tci.h): POP0 is
 //          P x (n_pop * n), the chains' starts, and Z0 P x (m0 * n), the starting archive of every cell, both laid out as
-//          POP0 of 'demc'; everything else is 'demc''s, with the options append_every (10), p_snooker (0.1) and archive
-//          (false) beside its own. out: 'demc''s fields (trial_oob is 2 for a null move) plus n_null (n_pop x n), ljac
-//          and snooker (n_chains x min(log_rows, n_gen)), n_archive and, with options.archive, archive
-//          (P x n_archive x n).
+//          POP0 of 'demc'; everything else is 'demc''s, with the options append_every (10), p_snooker (0.1), archive
+//          (false), bounds ('reject' or 'reflect') and census (0 or 1; tci_demczs_run_bounds: with census the fields
+//          n_cross, oob_lo, oob_hi (P x n_pop x n) and n_left (n_chains x rows), with 'reflect' n_refl, n_reflected
+//          (n_pop x n) and orient (P x n_pop x n)) beside its own. out: 'demc''s fields (trial_oob is 2 for a null
+//          move) plus n_null (n_pop x n), ljac and snooker (n_chains x min(log_rows, n_gen)), n_archive and, with
+//          options.archive, archive (P x n_archive x n).
 //   options.presearch of 'dram': a population P x (n_pop * n) laid out as POP0 above, one per chain. The search runs
 //          first (options.presearch_gen generations, default 500, options.presearch_F, options.presearch_CR; seeded by
 //          options.seed and keyed by options.chain_keys) and chain c starts from the best final member of its
@@ -1926,7 +1928,7 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs0[], bool 
     o = prhs[10];
     static const char* known[] = {"n_gen", "thin", "jump_every", "stats_from", "updatesigma", "CR", "gamma0", "seed",
                                   "keys", "log_rows", "rhat", "ess", "max_lag", "rank"};
-    static const char* known_zs[] = {"append_every", "p_snooker", "archive"};
+    static const char* known_zs[] = {"append_every", "p_snooker", "archive", "bounds", "census"};
     for (int f = 0; f < mxGetNumberOfFields(o); ++f) {
       const char* fn = mxGetFieldNameByNumber(o, f);
       bool ok = false;
@@ -1945,6 +1947,17 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs0[], bool 
     zopt.p_snooker = opt_num(o, "p_snooker", zopt.p_snooker);
   }
   const bool want_archive = zs && opt_num(o, "archive", 0.0) != 0.0;
+  tci_bounds_options bopt;
+  tci_bounds_defaults(&bopt);
+  if (zs) {
+    const std::string bounds = opt_str(o, "bounds", "reject");
+    if (bounds != "reject" && bounds != "reflect") mexErrMsgIdAndTxt("tci:opts", "options.bounds must be 'reject' or 'reflect'");
+    bopt.mode = bounds == "reflect" ? TCI_BOUNDS_REFLECT : TCI_BOUNDS_REJECT;
+    const double census = opt_num(o, "census", 0.0);
+    if (census != 0.0 && census != 1.0) mexErrMsgIdAndTxt("tci:opts", "options.census must be 0 or 1");
+    bopt.census = (int32_t)census;
+  }
+  const bool reflect = bopt.mode == TCI_BOUNDS_REFLECT, census = bopt.census != 0;
   dopt.n_gen = opt_int(o, "n_gen", dopt.n_gen, 0);
   dopt.thin = opt_int(o, "thin", dopt.thin, 0);
   dopt.jump_every = opt_int(o, "jump_every", dopt.jump_every, 0);
@@ -1984,6 +1997,8 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs0[], bool 
                                      "n_oob", "n_evals", "accepted", "trial_oob", "n_keep", "kernel_ms"};
   if (zs) fields.insert(fields.end(), {"n_null", "ljac", "snooker", "n_archive"});
   if (want_archive) fields.push_back("archive");
+  if (census) fields.insert(fields.end(), {"n_cross", "oob_lo", "oob_hi", "n_left"});
+  if (reflect) fields.insert(fields.end(), {"n_refl", "n_reflected", "orient"});
   if (want_rhat) fields.insert(fields.end(), {"rhat", "s2_rhat", "rhat_max"});
   if (want_ess) fields.insert(fields.end(), {"ess", "s2_ess", "ess_min"});
   if (want_rank) fields.push_back("rank");
@@ -2061,12 +2076,58 @@ void cmd_demc(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs0[], bool 
       ar = mxCreateNumericArray(3, da, mxDOUBLE_CLASS, mxREAL);
       zout.archive = mxGetPr(ar);
     }
-    rc = tci_demczs_run_rank(ctx, &zopt, pop, z0, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, (int64_t)m0, in[0],
-                             in[1], in[2], in[3], in[4], s2v.data(), &zout, nullptr, want_rhat ? &rout : nullptr, &eopt,
-                             want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr);
+    // the census and the reflection (tci_demczs_run_bounds): int32 and uint8 on the library's side, doubles here
+    std::vector<int32_t> cens(census ? 3 * B * P : 0), nleft(census ? B * G + 1 : 0), nrefl(reflect ? B * G + 1 : 0),
+        nreflected(reflect ? B : 0);
+    std::vector<uint8_t> orient(reflect ? B * P : 0);
+    tci_bounds_outputs bout;
+    memset(&bout, 0, sizeof bout);
+    if (census) {
+      bout.n_cross = cens.data();
+      bout.oob_lo = cens.data() + B * P;
+      bout.oob_hi = cens.data() + 2 * B * P;
+      if (G) bout.n_left = nleft.data();
+    }
+    if (reflect) {
+      if (G) bout.n_refl = nrefl.data();
+      bout.n_reflected = nreflected.data();
+      bout.orient = orient.data();
+    }
+    if (census || reflect)
+      rc = tci_demczs_run_bounds(ctx, &zopt, pop, z0, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, (int64_t)m0, in[0],
+                                 in[1], in[2], in[3], in[4], s2v.data(), &zout, nullptr, want_rhat ? &rout : nullptr, &eopt,
+                                 want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr, &bopt, &bout);
+    else
+      rc = tci_demczs_run_rank(ctx, &zopt, pop, z0, (int64_t)P, cid.data(), (int64_t)n, (int64_t)n_pop, (int64_t)m0, in[0],
+                               in[1], in[2], in[3], in[4], s2v.data(), &zout, nullptr, want_rhat ? &rout : nullptr, &eopt,
+                               want_ess ? &eout : nullptr, &kopt, want_rank ? &ro.out : nullptr);
     out.n_keep = zout.n_keep;
     out.kernel_ms = zout.kernel_ms;
     if (rc == TCI_OK) {
+      const mwSize dq[3] = {P, n_pop, n};
+      auto cube = [&](const char* name, auto* v) {  // P x n_pop x n, as pop
+        mxArray* m = mxCreateNumericArray(3, dq, mxDOUBLE_CLASS, mxREAL);
+        for (size_t i = 0; i < B * P; ++i) mxGetPr(m)[i] = (double)v[i];
+        mxSetField(res, 0, name, m);
+      };
+      auto log_of = [&](const char* name, const std::vector<int32_t>& v) {  // n_chains x rows, as the other logs
+        mxArray* m = mxCreateDoubleMatrix(B, G, mxREAL);
+        for (size_t i = 0; i < B * G; ++i) mxGetPr(m)[i] = (double)v[i];
+        mxSetField(res, 0, name, m);
+      };
+      if (census) {
+        cube("n_cross", cens.data());
+        cube("oob_lo", cens.data() + B * P);
+        cube("oob_hi", cens.data() + 2 * B * P);
+        log_of("n_left", nleft);
+      }
+      if (reflect) {
+        log_of("n_refl", nrefl);
+        mxArray* nr = mxCreateDoubleMatrix(n_pop, n, mxREAL);
+        for (size_t b = 0; b < B; ++b) mxGetPr(nr)[b] = (double)nreflected[b];
+        mxSetField(res, 0, "n_reflected", nr);
+        cube("orient", orient.data());
+      }
       mxArray* nn = mxCreateDoubleMatrix(n_pop, n, mxREAL);
       for (size_t b = 0; b < B; ++b) mxGetPr(nn)[b] = (double)nnull[b];
       mxArray* ls = mxCreateDoubleMatrix(B, G, mxREAL);

@@ -44,8 +44,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 
-KERNELS = {"k_demc_propose<false>": "k_demc_propose", "k_zs_propose<false>": "k_zs_propose",
-           "k_demc_decide<false>": "k_demc_decide", "k_zs_decide<false>": "k_zs_decide"}
+KERNELS = {"k_demc_propose<false>": "k_demc_propose", "k_zs_propose<false, false": "k_zs_propose",
+           "k_demc_decide<false>": "k_demc_decide", "k_zs_decide<false, false": "k_zs_decide"}
 
 
 FAM = {"k_zs_propose": "k_zs_propose", "k_zs_decide": "k_zs_decide", "tci_cohort_kernel": "likelihood",

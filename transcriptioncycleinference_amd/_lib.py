@@ -212,6 +212,18 @@ class tci_demczs_outputs(C.Structure):
                                             ("n_archive", C.c_int64)]
 
 
+class tci_bounds_options(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("census", C.c_int32), ("flags", C.c_int64)]
+
+
+class tci_bounds_outputs(C.Structure):
+    _fields_ = [("n_cross", _i32p), ("oob_lo", _i32p), ("oob_hi", _i32p), ("n_left", _i32p), ("n_refl", _i32p),
+                ("n_reflected", _i32p), ("orient", _u8p)]
+
+
+TCI_BOUNDS_REJECT, TCI_BOUNDS_REFLECT = 0, 1
+
+
 class tci_fitcheck_options(C.Structure):
     _fields_ = [("scratch_bytes", C.c_int64), ("n_levels", C.c_int32), ("levels", C.c_double * 8)]
 
@@ -350,6 +362,13 @@ SIGNATURES = [
                                       C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
                                       C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
                                       C.POINTER(tci_chainrank_options), C.POINTER(tci_chainrank_outputs)]),
+    ("tci_bounds_defaults", C.c_int, [C.POINTER(tci_bounds_options)]),
+    ("tci_demczs_run_bounds", C.c_int, [C.c_void_p, C.POINTER(tci_demczs_options), _dp, _dp, C.c_int64, _i32p, C.c_int64,
+                                        C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(tci_demczs_outputs),
+                                        C.POINTER(tci_chainrhat_options), C.POINTER(tci_chainrhat_outputs),
+                                        C.POINTER(tci_chainess_options), C.POINTER(tci_chainess_outputs),
+                                        C.POINTER(tci_chainrank_options), C.POINTER(tci_chainrank_outputs),
+                                        C.POINTER(tci_bounds_options), C.POINTER(tci_bounds_outputs)]),
     ("tci_version", C.c_char_p, []),
 ]
 

@@ -21,14 +21,15 @@ SOURCES = [os.path.join(CSRC, "tci_kernels.hip"), os.path.join(CSRC, "tci_dram.h
            os.path.join(CSRC, "tci_fitcheck.hip"), os.path.join(CSRC, "tci_chainlp.hip"), os.path.join(CSRC, "tci_loocheck.hip"),
            os.path.join(CSRC, "tci_modesearch.hip"), os.path.join(CSRC, "tci_api_search.cpp"),
            os.path.join(CSRC, "tci_demc.hip"), os.path.join(CSRC, "tci_api_demc.cpp"),
-           os.path.join(CSRC, "tci_demczs.hip"), os.path.join(CSRC, "tci_api_demczs.cpp"),
+           os.path.join(CSRC, "tci_demczs.hip"), os.path.join(CSRC, "tci_demczs_bounds.hip"),
+           os.path.join(CSRC, "tci_api_demczs.cpp"),
            os.path.join(CSRC, "tci_chainrank.hip"),
            os.path.join(CSRC, "tci_api.cpp"), os.path.join(CSRC, "tci_api_chain.cpp"), os.path.join(CSRC, "tci_api_dram.cpp")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "tci.h"), os.path.join(CSRC, "tci_internal.h"), os.path.join(CSRC, "tci_diag.h"), os.path.join(CSRC, "tci_tile16.h"), os.path.join(CSRC, "tci_adapt_map.h"),
            os.path.join(CSRC, "tci_dram_internal.h"), os.path.join(CSRC, "tci_eval.h"), os.path.join(CSRC, "tci_csum.h"), os.path.join(CSRC, "tci_key.h"),
            os.path.join(CSRC, "tci_chainrhat_dev.h"), os.path.join(CSRC, "tci_api_internal.h"), os.path.join(CSRC, "tci_rng.h"),
            os.path.join(CSRC, "tci_prior.h"), os.path.join(CSRC, "tci_gamma.h"), os.path.join(CSRC, "tci_fp.h"),
-           os.path.join(CSRC, "tci_chain_dev.h")]
+           os.path.join(CSRC, "tci_chain_dev.h"), os.path.join(CSRC, "tci_demczs_kernels.h")]
 LIB = os.path.join(PKG_DIR, "libtci.so")
 ARCH = "gfx950"  # CDNA4 only: the kernels use gfx950 instructions (v_bitop3_b32, permlane16/32 swaps)
 # Options of single sources (each compiled to an object of its own, then linked with the rest). The likelihood

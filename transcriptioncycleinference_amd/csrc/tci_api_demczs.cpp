@@ -1,7 +1,9 @@
 // tci_api_demczs.cpp -- the C ABI of the DE-MC(zs) sampler (include/tci.h, tci_demczs_run): every check before any
 // device work, the uploads, generation 0, then per generation the proposal kernel, ONE batched likelihood launch on the
 // trial buffer under the active mask and the decision kernel (tci_demczs.hip), timed as one stretch, the group
-// reductions on the device chain, and the copies of what the caller asked for.
+// reductions on the device chain, and the copies of what the caller asked for. tci_demczs_run_bounds is the same run
+// (zs_run) with the census' counters and the orientation rows beside it; with both features off no buffer is
+// allocated, no kernel launched and no copy made beyond tci_demczs_run_rank's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,6 +19,7 @@ using namespace tci_api;
 namespace {
 
 const char* const kWho = "tci_demczs_run";
+const char* const kWhoBounds = "tci_demczs_run_bounds";
 
 std::string at(int64_t k, int64_t j) { return "cell " + std::to_string(k) + ", index " + std::to_string(j); }
 
@@ -36,12 +39,12 @@ int rows_check(tci_ctx* ctx, const std::string& who, const char* name, const cha
 }
 
 // Every check of a tci_demczs_run call, in the header's order. *keep_k0, *keep_rows: the kept rows the reductions use.
-int zs_check(tci_ctx* ctx, const tci_demczs_options& o, const double* pop0, const double* z0, int64_t ld,
+int zs_check(tci_ctx* ctx, const char* entry, const tci_demczs_options& o, const double* pop0, const double* z0, int64_t ld,
              const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower, const double* upper,
              const double* mu, const double* sig, const double* jitter, const double* s2, int64_t log_rows, bool reduce,
              const tci_chainrhat_options* ropt, const tci_chainess_options* eopt, bool ess,
              const tci_chainrank_options* kopt, tci_chainrank_options* k_opt, int64_t* keep_k0, int64_t* keep_rows) {
-  const std::string who = std::string(kWho) + ": ";
+  const std::string who = std::string(entry) + ": ";
   if (n_sel < 1) return fail(ctx, TCI_EINVAL, who + "n_sel must be >= 1");
   if (o.flags != 0) return fail(ctx, TCI_EINVAL, who + "flags is reserved and must be 0");
   if (o.n_gen < 0) return fail(ctx, TCI_EINVAL, who + "n_gen must be >= 0");
@@ -102,12 +105,38 @@ int zs_check(tci_ctx* ctx, const tci_demczs_options& o, const double* pop0, cons
     if (ess && eopt && eopt->max_lag < 0) return fail(ctx, TCI_EINVAL, who + "max_lag must be >= 0");
     if (ess && eopt && eopt->flags != 0) return fail(ctx, TCI_EINVAL, who + "flags is reserved and must be 0");
     if (k_opt) {
-      const int rc = chainrank_opts(ctx, kWho, kopt, k_opt);
+      const int rc = chainrank_opts(ctx, entry, kopt, k_opt);
       if (rc != TCI_OK) return rc;
     }
   }
   return TCI_OK;
 }
+
+// The checks of tci_demczs_run_bounds' own arguments, after zs_check and before any device work.
+int bounds_check(tci_ctx* ctx, const tci_bounds_options& bo, const tci_bounds_outputs* bout) {
+  const std::string who = std::string(kWhoBounds) + ": ";
+  if (bo.mode != TCI_BOUNDS_REJECT && bo.mode != TCI_BOUNDS_REFLECT)
+    return fail(ctx, TCI_EINVAL, who + "mode must be TCI_BOUNDS_REJECT (0) or TCI_BOUNDS_REFLECT (1)");
+  if (bo.census != 0 && bo.census != 1) return fail(ctx, TCI_EINVAL, who + "census must be 0 or 1");
+  if (bo.flags != 0) return fail(ctx, TCI_EINVAL, who + "flags is reserved and must be 0");
+  if (!bout) return TCI_OK;
+  if (!bo.census) {
+    const char* f = bout->n_cross ? "n_cross" : bout->oob_lo ? "oob_lo" : bout->oob_hi ? "oob_hi" : bout->n_left ? "n_left" : nullptr;
+    if (f) return fail(ctx, TCI_EINVAL, who + f + " is a census output and census is 0");
+  }
+  if (bo.mode != TCI_BOUNDS_REFLECT) {
+    const char* f = bout->n_refl ? "n_refl" : bout->n_reflected ? "n_reflected" : bout->orient ? "orient" : nullptr;
+    if (f) return fail(ctx, TCI_EINVAL, who + f + " is a reflection output and mode is TCI_BOUNDS_REJECT");
+  }
+  return TCI_OK;
+}
+
+int zs_run(tci_ctx* ctx, const tci_demczs_options* opt, const double* pop0, const double* z0, int64_t ld,
+           const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower, const double* upper,
+           const double* prior_mu, const double* prior_sig, const double* jitter, const double* sigma2_0,
+           tci_demczs_outputs* out, const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout,
+           const tci_chainess_options* eopt, tci_chainess_outputs* eout, const tci_chainrank_options* kopt,
+           tci_chainrank_outputs* kout, const tci_bounds_options* bopt, tci_bounds_outputs* bout);
 
 }  // namespace
 
@@ -141,7 +170,39 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
                         const double* sigma2_0, tci_demczs_outputs* out, const tci_chainrhat_options* ropt,
                         tci_chainrhat_outputs* rout, const tci_chainess_options* eopt, tci_chainess_outputs* eout,
                         const tci_chainrank_options* kopt, tci_chainrank_outputs* kout) {
+  return zs_run(ctx, opt, pop0, z0, ld, cell_id, n_sel, n_pop, m0, lower, upper, prior_mu, prior_sig, jitter, sigma2_0, out,
+                ropt, rout, eopt, eout, kopt, kout, nullptr, nullptr);
+}
+
+int tci_bounds_defaults(tci_bounds_options* o) {
+  if (!o) return TCI_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  return TCI_OK;
+}
+
+int tci_demczs_run_bounds(tci_ctx* ctx, const tci_demczs_options* opt, const double* pop0, const double* z0, int64_t ld,
+                          const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower,
+                          const double* upper, const double* prior_mu, const double* prior_sig, const double* jitter,
+                          const double* sigma2_0, tci_demczs_outputs* out, const tci_chainrhat_options* ropt,
+                          tci_chainrhat_outputs* rout, const tci_chainess_options* eopt, tci_chainess_outputs* eout,
+                          const tci_chainrank_options* kopt, tci_chainrank_outputs* kout, const tci_bounds_options* bopt,
+                          tci_bounds_outputs* bout) {
+  return zs_run(ctx, opt, pop0, z0, ld, cell_id, n_sel, n_pop, m0, lower, upper, prior_mu, prior_sig, jitter, sigma2_0, out,
+                ropt, rout, eopt, eout, kopt, kout, bopt, bout);
+}
+
+}  // extern "C"
+
+namespace {
+
+int zs_run(tci_ctx* ctx, const tci_demczs_options* opt, const double* pop0, const double* z0, int64_t ld,
+           const int32_t* cell_id, int64_t n_sel, int64_t n_pop, int64_t m0, const double* lower, const double* upper,
+           const double* prior_mu, const double* prior_sig, const double* jitter, const double* sigma2_0,
+           tci_demczs_outputs* out, const tci_chainrhat_options* ropt, tci_chainrhat_outputs* rout,
+           const tci_chainess_options* eopt, tci_chainess_outputs* eout, const tci_chainrank_options* kopt,
+           tci_chainrank_outputs* kout, const tci_bounds_options* bopt, tci_bounds_outputs* bout) {
   if (!ctx) return TCI_EINVAL;
+  const char* const kWho = bopt || bout ? kWhoBounds : ::kWho;  // the entry point the caller came through
   if (!pop0 || !z0 || !cell_id || !lower || !upper || !prior_mu || !prior_sig || !jitter || !sigma2_0 || !out)
     return fail(ctx, TCI_EINVAL, std::string(kWho) + ": null argument");
   tci_demczs_options o;
@@ -150,9 +211,18 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
   const bool reduce = rout || eout || kout;
   tci_chainrank_options k_opt{};
   int64_t keep_k0 = 0, keep_rows = 0;
-  int rc = zs_check(ctx, o, pop0, z0, ld, cell_id, n_sel, n_pop, m0, lower, upper, prior_mu, prior_sig, jitter, sigma2_0,
+  int rc = zs_check(ctx, kWho, o, pop0, z0, ld, cell_id, n_sel, n_pop, m0, lower, upper, prior_mu, prior_sig, jitter, sigma2_0,
                     out->log_rows, reduce, ropt, eopt, eout != nullptr, kopt, kout ? &k_opt : nullptr, &keep_k0, &keep_rows);
   if (rc != TCI_OK) return rc;
+  tci_bounds_options bo;
+  tci_bounds_defaults(&bo);
+  if (bopt) bo = *bopt;
+  rc = bounds_check(ctx, bo, bout);
+  if (rc != TCI_OK) return rc;
+  const bool reflect = bo.mode == TCI_BOUNDS_REFLECT, census = bo.census != 0;
+  const bool bounds = reflect || census;  // neither: the kernels and the buffers of tci_demczs_run_rank, nothing else
+  const tci_bounds_outputs none{};
+  const tci_bounds_outputs& bo_out = bout ? *bout : none;
 
   const size_t n = (size_t)n_sel, L = (size_t)ld, B = n * (size_t)n_pop;
   const int64_t M_cap = m0 + n_pop * (o.n_gen / o.append_every);
@@ -160,7 +230,7 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
   const size_t n_keep = o.thin > 0 ? (size_t)(o.n_gen / o.thin) + 1 : 0;
   const bool want_chain = out->chain || out->s2chain || out->sschain || out->prichain || reduce;
   const size_t K = want_chain ? n_keep : 0;  // kept rows the device holds
-  const bool want_log = out->logr || out->accepted || out->trial_oob || out->ljac || out->snooker;
+  const bool want_log = out->logr || out->accepted || out->trial_oob || out->ljac || out->snooker || bo_out.n_left || bo_out.n_refl;
   const size_t G = want_log ? (size_t)std::min<int64_t>(out->log_rows, o.n_gen) : 0;
   const double gamma0 = o.gamma0 > 0.0 ? o.gamma0 : 2.38;
 
@@ -170,7 +240,7 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
     return fail(ctx, TCI_ENOMEM,
                 std::string(kWho) + ": the chain, the archive or the logs (more than 2^64 bytes) do not fit the device");
 
-  std::vector<int32_t> row_cell, npar, nacc, noob, nnull;
+  std::vector<int32_t> row_cell, npar, nacc, noob, nnull, cens0;
   std::vector<int64_t> keys;
   RhatGroups groups;
   try {
@@ -180,6 +250,7 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
     noob.resize(B);
     nnull.resize(B);
     keys.resize(n);
+    if (census) cens0.resize(B * L);
   } catch (const std::bad_alloc&) {
     return fail(ctx, TCI_ENOMEM, std::string(kWho) + ": host allocation failed");
   }
@@ -188,6 +259,9 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
     npar[b] = 7 + ctx->meta[(size_t)row_cell[b]].n;
   }
   for (size_t k = 0; k < n; ++k) keys[k] = o.keys ? o.keys[k] : (int64_t)k;
+  if (census)  // the three counters start at 0, their padding at -1
+    for (size_t b = 0; b < B; ++b)
+      for (size_t j = 0; j < L; ++j) cens0[b * L + j] = j < (size_t)npar[b] ? 0 : -1;
   if (reduce) {
     std::vector<int32_t> group;
     try {
@@ -206,7 +280,9 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
       (K * B * (L + 3) + (n * Mc + 2 * B) * L + 6 * B + 5 * n * L + n + (out->logr ? GB : 0) + (out->ljac ? GB : 0)) *
           sizeof(double) +
       2 * B + (out->accepted ? GB : 0) + (out->trial_oob ? GB : 0) + (out->snooker ? GB : 0) +
-      (n + 5 * B) * sizeof(int32_t) + n * sizeof(int64_t);
+      (n + 5 * B) * sizeof(int32_t) + n * sizeof(int64_t) +
+      (bounds ? 3 * B + (census ? 3 * B * L : 0) + (bo_out.n_left ? GB : 0) + (bo_out.n_refl ? GB : 0) : 0) * sizeof(int32_t) +
+      (reflect ? 2 * B * L : 0);
   TCI_HIP(ctx, hipSetDevice(ctx->device));
   DevAllocs A;
   hipError_t e = hipSuccess;
@@ -232,6 +308,13 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
   int32_t* d_npar = ialloc(B);
   int32_t* d_cnt = ialloc(3 * B);  // n_acc, n_oob, n_null
   int64_t* d_keys = e == hipSuccess ? A.alloc<int64_t>(n, &e) : nullptr;
+  // tci_demczs_run_bounds' own buffers, each allocated only when its feature is on: with both off the call makes
+  // tci_demczs_run_rank's allocations and no other
+  int32_t* d_cens = census ? ialloc(3 * B * L) : nullptr;               // n_cross, oob_lo, oob_hi
+  int32_t* d_prop = bounds ? ialloc(3 * B) : nullptr;                   // n_left and n_refl of the trials, n_reflected
+  int32_t* d_leftlog = bo_out.n_left && G ? ialloc(G * B) : nullptr;
+  int32_t* d_refllog = bo_out.n_refl && G ? ialloc(G * B) : nullptr;
+  uint8_t* d_orient = reflect ? balloc(2 * B * L) : nullptr;            // of the chains, then of the trials
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return fail(ctx, TCI_ENOMEM, std::string(kWho) + ": the populations, the archive and the chain (" +
@@ -260,6 +343,28 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
   TCI_HIP(ctx, up(d_rowcell, row_cell.data(), B * sizeof(int32_t)));
   TCI_HIP(ctx, up(d_npar, npar.data(), B * sizeof(int32_t)));
   TCI_HIP(ctx, up(d_keys, keys.data(), n * sizeof(int64_t)));
+  tci::ZsBounds bx{};
+  tci::ZsDecideBounds dx{};
+  if (bounds) {
+    TCI_HIP(ctx, hipMemsetAsync(d_prop, 0, 3 * B * sizeof(int32_t), s));
+    bx.reflect = reflect;
+    dx.n_left_t = bx.n_left_t = d_prop;
+    dx.n_refl_t = bx.n_refl_t = d_prop + B;
+    dx.n_reflected = d_prop + 2 * B;
+    dx.n_left_log = d_leftlog;
+    dx.n_refl_log = d_refllog;
+  }
+  if (census) {
+    for (int c = 0; c < 3; ++c) TCI_HIP(ctx, up(d_cens + (size_t)c * B * L, cens0.data(), B * L * sizeof(int32_t)));
+    bx.n_cross = d_cens;
+    bx.oob_lo = d_cens + B * L;
+    bx.oob_hi = d_cens + 2 * B * L;
+  }
+  if (reflect) {
+    TCI_HIP(ctx, hipMemsetAsync(d_orient, 0, 2 * B * L, s));
+    bx.orient = dx.orient = d_orient;
+    dx.orient_t = bx.orient_t = d_orient + B * L;
+  }
 
   auto launch = [&]() -> int {
     // generation 0: the prior and the SS of the chains' starts, then s2, the counters and kept row 0
@@ -281,7 +386,7 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
       const int64_t app_row = g % o.append_every == 0 ? M_g : -1;
       rc = tci::launch_zs_propose(ctx->kp, d_cell, d_keys, d_pop, d_arch, d_lo, d_up, d_mu, d_sig, d_jit, n_sel, n_pop, M_g,
                                   M_cap, ld, g, jump, o.seed, gamma0, o.CR, o.p_snooker, d_trial, d_pri_t, d_lj, d_move,
-                                  d_active, (void*)s);
+                                  d_active, (void*)s, bounds ? &bx : nullptr);
       // one launch for every chain: a null or out-of-bounds row takes the kernel's inactive-row path
       if (rc == TCI_OK)
         rc = tci::launch(ctx->kp, ctx->rpl, tci::MODE_SS, d_trial, ld, d_rowcell, d_active, (int64_t)B, d_ss_t, nullptr, 0,
@@ -292,7 +397,7 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
                                    d_ss, d_pri, d_s2, d_nacc, d_noob, d_nnull, d_chain, d_s2c, d_ssc, d_pric,
                                    out->logr ? d_logr : nullptr, out->accepted ? d_acclog : nullptr,
                                    out->trial_oob ? d_ooblog : nullptr, out->ljac ? d_ljlog : nullptr,
-                                   out->snooker ? d_snklog : nullptr, (void*)s);
+                                   out->snooker ? d_snklog : nullptr, (void*)s, bounds ? &dx : nullptr);
     }
     return rc;
   };
@@ -315,7 +420,14 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
                      {G ? (void*)out->ljac : nullptr, d_ljlog, G * B * sizeof(double)},
                      {G ? (void*)out->accepted : nullptr, d_acclog, G * B},
                      {G ? (void*)out->trial_oob : nullptr, d_ooblog, G * B},
-                     {G ? (void*)out->snooker : nullptr, d_snklog, G * B}},
+                     {G ? (void*)out->snooker : nullptr, d_snklog, G * B},
+                     {bo_out.n_cross, bx.n_cross, B * L * sizeof(int32_t)},
+                     {bo_out.oob_lo, bx.oob_lo, B * L * sizeof(int32_t)},
+                     {bo_out.oob_hi, bx.oob_hi, B * L * sizeof(int32_t)},
+                     {G ? (void*)bo_out.n_left : nullptr, d_leftlog, G * B * sizeof(int32_t)},
+                     {G ? (void*)bo_out.n_refl : nullptr, d_refllog, G * B * sizeof(int32_t)},
+                     {bo_out.n_reflected, dx.n_reflected, B * sizeof(int32_t)},
+                     {bo_out.orient, d_orient, B * L}},
                     &ms);
   if (rc != TCI_OK) return rc;
   for (size_t b = 0; b < B; ++b) {
@@ -338,4 +450,4 @@ int tci_demczs_run_rank(tci_ctx* ctx, const tci_demczs_options* opt, const doubl
   return TCI_OK;
 }
 
-}  // extern "C"
+}  // namespace

@@ -295,17 +295,49 @@ int launch_demc_decide(const KParams& kp, const int32_t* cell_id, const int64_t*
 //                      chain; an accepted trial replaces its parent. log_row >= 0: the five logs (each may be null) get
 //                      that row. app_row >= 0: after the decisions chain i's row goes to archive row app_row + i of its
 //                      cell. keep_row >= 0: row keep_row of chain, s2chain, sschain and prichain gets every chain.
+// The bounds variants (tci_demczs_run_bounds): with bx given, generation gen >= 1 runs the kBounds instantiations of
+// k_zs_propose / k_zs_decide (tci_demczs_bounds.hip, a code object of its own), which take the struct as one more
+// kernel argument; with bx null the launches are the instantiations without the flag (tci_demczs.hip), whose arguments
+// are the ones listed here and nothing else. All pointers are device buffers laid out as the rows are.
+struct ZsBounds {
+  int reflect;                          // 1: TCI_BOUNDS_REFLECT
+  int32_t *n_cross, *oob_lo, *oob_hi;   // [n_sel * n_pop][ld], all three or none (census off)
+  const uint8_t* orient;                // [n_sel * n_pop][ld]: the chains' orientation bits; required with reflect
+  uint8_t* orient_t;                    // [n_sel * n_pop][ld]: the trials'; required with reflect
+  int32_t *n_left_t, *n_refl_t;         // [n_sel * n_pop], required: the two counts of this generation's proposals
+};
+struct ZsDecideBounds {
+  const int32_t *n_left_t, *n_refl_t;   // as k_zs_propose's kBounds instantiation wrote them
+  const uint8_t* orient_t;
+  uint8_t* orient;                      // null: no orientation rows (reject mode)
+  int32_t *n_left_log, *n_refl_log;     // [log_rows][n_sel * n_pop], each may be null
+  int32_t* n_reflected;                 // [n_sel * n_pop], required
+};
 int launch_zs_propose(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* pop,
                       const double* arch, const double* lower, const double* upper, const double* mu, const double* sig,
                       const double* jitter, int64_t n_sel, int64_t n_pop, int64_t M_g, int64_t M_cap, int64_t ld,
                       int64_t gen, bool jump, uint64_t seed, double gamma0, double CR, double p_snooker, double* trial,
-                      double* pri, double* ljac, uint8_t* move, uint8_t* active, void* stream);
+                      double* pri, double* ljac, uint8_t* move, uint8_t* active, void* stream, const ZsBounds* bx = nullptr);
 int launch_zs_decide(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* sigma2_0,
                      const double* trial, const double* ss_t, const double* pri_t, const double* ljac, const uint8_t* move,
                      const uint8_t* active, int64_t n_sel, int64_t n_pop, int64_t M_cap, int64_t ld, int64_t gen,
                      uint64_t seed, bool updatesigma, int64_t keep_row, int64_t app_row, int64_t log_row, double* pop,
                      double* arch, double* ss, double* pri, double* s2, int32_t* n_acc, int32_t* n_oob, int32_t* n_null,
                      double* chain, double* s2chain, double* sschain, double* prichain, double* logr, uint8_t* acc_log,
-                     uint8_t* oob_log, double* ljac_log, uint8_t* snk_log, void* stream);
+                     uint8_t* oob_log, double* ljac_log, uint8_t* snk_log, void* stream,
+                     const ZsDecideBounds* bx = nullptr);
+// The launches of the kBounds instantiations (tci_demczs_bounds.hip), which the two above hand a call with bx to.
+int launch_zs_propose_bounds(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* pop,
+                      const double* arch, const double* lower, const double* upper, const double* mu, const double* sig,
+                      const double* jitter, int64_t n_sel, int64_t n_pop, int64_t M_g, int64_t M_cap, int64_t ld,
+                      int64_t gen, bool jump, uint64_t seed, double gamma0, double CR, double p_snooker, double* trial,
+                      double* pri, double* ljac, uint8_t* move, uint8_t* active, void* stream, const ZsBounds& bx);
+int launch_zs_decide_bounds(const KParams& kp, const int32_t* cell_id, const int64_t* keys, const double* sigma2_0,
+                     const double* trial, const double* ss_t, const double* pri_t, const double* ljac, const uint8_t* move,
+                     const uint8_t* active, int64_t n_sel, int64_t n_pop, int64_t M_cap, int64_t ld, int64_t gen,
+                     uint64_t seed, bool updatesigma, int64_t keep_row, int64_t app_row, int64_t log_row, double* pop,
+                     double* arch, double* ss, double* pri, double* s2, int32_t* n_acc, int32_t* n_oob, int32_t* n_null,
+                     double* chain, double* s2chain, double* sschain, double* prichain, double* logr, uint8_t* acc_log,
+                     uint8_t* oob_log, double* ljac_log, uint8_t* snk_log, void* stream, const ZsDecideBounds& bx);
 
 }  // namespace tci

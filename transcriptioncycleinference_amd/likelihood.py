@@ -609,7 +609,11 @@ class DemcZs(Demc):
     """A DE-MC(zs) run (``tci_demczs_outputs``; the definition is in ``include/tci.h``): :class:`Demc`'s fields, with
     ``trial_oob`` 2 for a null snooker move, plus ``n_null`` (int32) ``[n_sel, n_pop]``, the logs ``ljac`` and
     ``snooker`` (uint8) ``[log_rows, n_chains]``, and ``archive`` ``[n_sel, n_archive, ld]`` (None unless asked for):
-    ``z0`` followed by the chains' states at the append generations. ``m0``: the rows of ``z0``."""
+    ``z0`` followed by the chains' states at the append generations. ``m0``: the rows of ``z0``.
+    ``bounds`` (``'reject'`` or ``'reflect'``) and ``census``: what the run was asked for (``tci_demczs_run_bounds``).
+    With ``census``: ``n_cross``, ``oob_lo`` and ``oob_hi`` (int32) ``[n_sel, n_pop, ld]``, -1 at ``j >= P``, and the log
+    ``n_left`` (int32) ``[log_rows, n_chains]``. With ``bounds='reflect'``: the log ``n_refl`` (int32), ``n_reflected``
+    (int32) ``[n_sel, n_pop]`` and ``orient`` (uint8) ``[n_sel, n_pop, ld]``. Each is None when its feature is off."""
 
     n_null: Optional[np.ndarray] = None
     ljac: Optional[np.ndarray] = None
@@ -617,6 +621,15 @@ class DemcZs(Demc):
     archive: Optional[np.ndarray] = None
     n_archive: int = 0
     m0: int = 0
+    bounds: str = "reject"
+    census: bool = False
+    n_cross: Optional[np.ndarray] = None
+    oob_lo: Optional[np.ndarray] = None
+    oob_hi: Optional[np.ndarray] = None
+    n_left: Optional[np.ndarray] = None
+    n_refl: Optional[np.ndarray] = None
+    n_reflected: Optional[np.ndarray] = None
+    orient: Optional[np.ndarray] = None
 
     @classmethod
     def empty_zs(cls, n: int, n_pop: int, ld: int, n_gen: int, thin: int, log_rows: int, m0: int, append_every: int,
@@ -634,6 +647,23 @@ class DemcZs(Demc):
         return _lib.tci_demczs_outputs(*[getattr(base, f) for f, _ in _lib.tci_demc_outputs._fields_],
                                        _lib.ptr(self.n_null, _lib._i32p), P(self.ljac),
                                        _lib.ptr(self.snooker, _lib._u8p) if self.snooker.size else None, P(self.archive), 0)
+
+    def with_bounds(self, bounds: str, census: bool) -> "_lib.tci_bounds_outputs":
+        """Allocate the outputs of the features that are on, and return them as ``tci_bounds_outputs``."""
+        n, n_pop, ld = self.pop.shape
+        G, B = self.logr.shape
+        self.bounds, self.census = bounds, bool(census)
+        full = lambda: np.full((n, n_pop, ld), -1, np.int32)  # noqa: E731
+        if census:
+            self.n_cross, self.oob_lo, self.oob_hi = full(), full(), full()
+            self.n_left = np.full((G, B), -1, np.int32)
+        if bounds == "reflect":
+            self.n_refl = np.zeros((G, B), np.int32)
+            self.n_reflected = np.zeros((n, n_pop), np.int32)
+            self.orient = np.zeros((n, n_pop, ld), np.uint8)
+        I = lambda a: _lib.ptr(a, _lib._i32p) if a is not None and a.size else None  # noqa: E731, E741
+        return _lib.tci_bounds_outputs(I(self.n_cross), I(self.oob_lo), I(self.oob_hi), I(self.n_left), I(self.n_refl),
+                                       I(self.n_reflected), _lib.ptr(self.orient, _lib._u8p))
 
 
 class Likelihood:
@@ -1188,13 +1218,20 @@ class Likelihood:
                thin: int = 1, jump_every: int = 10, CR: float = 0.2, gamma0: float = 0.0, updatesigma: bool = True,
                seed: int = 0, keys=None, stats_from: int = 0, append_every: int = 10, p_snooker: float = 0.1,
                rhat: bool = False, ess: bool = False, max_lag: int = 0, log_rows: int = 0, flags: int = 0, rank=False,
-               archive: bool = False) -> DemcZs:
+               archive: bool = False, bounds: str = "reject", census: bool = False) -> DemcZs:
         """DE-MC(zs) (ter Braak & Vrugt 2008) on the device (``tci_demczs_run``; the definition is in ``include/tci.h``):
         ``n_pop`` chains per cell whose proposals come from an archive of past states, with snooker moves. ``pop0``
         ``[n_sel, n_pop, ld]``: the chains' starts; ``z0`` ``[n_sel, m0, ld]``: the starting archive of every cell,
         ``m0 >= 3`` rows inside ``[lower, upper]``; ``append_every``: the chains' states join the archive after every
         such generation; ``p_snooker``: the share of snooker moves; ``archive``: also return the final archive.
-        Everything else is :meth:`demc`'s. Returns a :class:`DemcZs`."""
+        ``bounds``: ``'reject'`` (a proposal with a coordinate outside the box is rejected unevaluated) or ``'reflect'``
+        (the oriented reflection of ``tci_demczs_run_bounds``); ``census``: also count, per chain and coordinate, how
+        often the coordinate crossed and how often it left below or above its bound. With the defaults the call is
+        ``tci_demczs_run`` as before. Everything else is :meth:`demc`'s. Returns a :class:`DemcZs`."""
+        if bounds not in ("reject", "reflect"):
+            raise ValueError("bounds must be 'reject' or 'reflect'")
+        if not isinstance(census, (bool, np.bool_)):
+            raise ValueError("census must be True or False")
         pop0 = np.ascontiguousarray(pop0, np.float64)
         z0 = np.ascontiguousarray(z0, np.float64)
         if pop0.ndim != 3:
@@ -1235,7 +1272,15 @@ class Likelihood:
             ck = ChainRank.empty(n, ld, max_lag=max_lag, **({} if rank is True else dict(rank)))
         args = (self._h, C.byref(opt), P(pop0), P(z0), ld, _lib.ptr(cid, _lib._i32p), n, n_pop, m0, P(lo), P(up), P(mu),
                 P(sig), P(jit), P(s2v), C.byref(out), R(ropt), R(rout), R(eopt), R(eout))
-        if ck is not None:
+        if bounds != "reject" or census:
+            bopt = _lib.tci_bounds_options(_lib.TCI_BOUNDS_REFLECT if bounds == "reflect" else _lib.TCI_BOUNDS_REJECT,
+                                           int(census), 0)
+            bout = dm.with_bounds(bounds, census)
+            kopt, kout = (ck.options(), ck.to_c()) if ck is not None else (None, None)
+            self._check(self._lib.tci_demczs_run_bounds(*args, R(kopt), R(kout), C.byref(bopt), C.byref(bout)))
+            if ck is not None:
+                dm.rank = ck.taken(kout)
+        elif ck is not None:
             kopt, kout = ck.options(), ck.to_c()
             self._check(self._lib.tci_demczs_run_rank(*args, C.byref(kopt), C.byref(kout)))
             dm.rank = ck.taken(kout)

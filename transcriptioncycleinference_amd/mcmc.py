@@ -103,8 +103,12 @@ DEMC_FIELDS = ("accept_rate", "n_oob", "rhat_max", "ess_min", "n_pop", "n_gen", 
 DEMC_KEYS = ("n_pop", "n_gen", "CR", "gamma0", "jump_every", "jitter", "updatesigma")
 # MCMCdemczs (fit(..., demczs=dict(...))): the DE-MC(zs) sampler's per-cell record: MCMCdemc's fields plus the null
 # snooker moves per chain, the share of snooker moves (NaN without the log), the starting and the final archive rows
-DEMCZS_FIELDS = DEMC_FIELDS + ("n_null", "snooker_rate", "m0", "n_archive")
-DEMCZS_KEYS = DEMC_KEYS + ("m0", "append_every", "p_snooker")
+# With census (tci_demczs_run_bounds): n_cross, oob_lo, oob_hi [7 + N] summed over the cell's chains, and oob_share
+# [7 + N], the share of the bounds-rejected proposals in which coordinate j had left. With bounds='reflect':
+# reflect_rate, the share of all proposals that were evaluated after at least one reflection. None when the feature is off.
+DEMCZS_FIELDS = DEMC_FIELDS + ("n_null", "snooker_rate", "m0", "n_archive", "n_cross", "oob_lo", "oob_hi", "oob_share",
+                               "reflect_rate")
+DEMCZS_KEYS = DEMC_KEYS + ("m0", "append_every", "p_snooker", "bounds", "census")
 ZS_FIT_LOG_ROWS = 1024   # the generations a demczs fit logs: snooker_rate is the share of snooker moves among them
 # RNG stream key of replicate r of dataset-wide cell g: g + r * REPLICATE_KEY_STRIDE. The sampler's Philox counter
 # carries the low 32 bits of a chain's key and nothing else of it (include/tci.h, chain_keys), so the replicate has to
@@ -1144,6 +1148,10 @@ def _demczs_arg(arg):
     m0 = d.get("m0")
     if m0 is not None and (isinstance(m0, bool) or int(m0) != m0 or int(m0) < max(3, int(n_pop))):
         raise ValueError("demczs m0 must be an integer >= max(3, n_pop): the chains start at the archive's first rows")
+    if d.get("bounds", "reject") not in ("reject", "reflect"):
+        raise ValueError("demczs bounds must be 'reject' or 'reflect'")
+    if not isinstance(d.get("census", False), (bool, np.bool_)):
+        raise ValueError("demczs census must be True or False")
     return d
 
 
@@ -1157,14 +1165,16 @@ def demczs(lk, n_pop: int = 4, m0: Optional[int] = None, n_gen: int = 1000, thin
            cells: Optional[Sequence[int]] = None, v0=None, presearch=None, cell_offset: int = 0,
            ratePriorWidth: float = 50.0, jitter=None, CR: float = 0.2, gamma0: float = 0.0, jump_every: int = 10,
            updatesigma: bool = True, sigma2_0=1.0, append_every: int = 10, p_snooker: float = 0.1, rhat: bool = True,
-           ess: bool = True, max_lag: int = 0, log_rows: int = 0, approved=None, rank=False, archive: bool = False):
+           ess: bool = True, max_lag: int = 0, log_rows: int = 0, approved=None, rank=False, archive: bool = False,
+           bounds: str = "reject", census: bool = False):
     """A DE-MC(zs) run (``Likelihood.demczs``; include/tci.h, ``tci_demczs_run``) of the cells ``cells`` (default: all)
     of ``lk``: ``n_pop`` chains per cell and a starting archive of ``m0`` rows (None: :func:`demczs_m0`, ``10 P`` of the
     longest selected cell; ``m0 >= max(3, n_pop)``). The archive ``z0`` is :func:`search_population` with ``m0`` members
     and the chains start at its first ``n_pop`` rows, so chain ``i`` starts at replicate ``i``'s x0. With ``presearch``
     (a dict for :func:`modesearch`, run here with ``m0`` members and the same ``seed``, or the ``(ModeSearch,
     SearchPlan)`` such a call returned) ``z0`` is the search's final population and the chains start at its best
-    members (:func:`search_order`). Keys, seeds, ``jitter``, ``n_burn``, ``rank`` and the reductions are :func:`demc`'s.
+    members (:func:`search_order`). Keys, seeds, ``jitter``, ``n_burn``, ``rank`` and the reductions are :func:`demc`'s;
+    ``bounds`` and ``census`` are ``Likelihood.demczs``'s (``tci_demczs_run_bounds``).
     Returns ``(DemcZs, SearchPlan)``; row ``k`` of either is cell ``plan.cells[k]``, and ``plan.pop0`` is ``z0``."""
     cl: Cells = lk.cells
     ids = list(range(cl.n_cells)) if cells is None else [int(c) for c in cells]
@@ -1201,18 +1211,34 @@ def demczs(lk, n_pop: int = 4, m0: Optional[int] = None, n_gen: int = 1000, thin
                     sigma2_0=sigma2_0, n_gen=n_gen, thin=thin, jump_every=jump_every, CR=CR, gamma0=gamma0,
                     updatesigma=updatesigma, seed=int(seed) * 1000003 + 20201028,
                     keys=np.array(sp.cells, np.int64) + int(cell_offset), stats_from=n_burn, append_every=append_every,
-                    p_snooker=p_snooker, rhat=rhat, ess=ess, max_lag=max_lag, log_rows=log_rows, rank=rank, archive=archive)
+                    p_snooker=p_snooker, rhat=rhat, ess=ess, max_lag=max_lag, log_rows=log_rows, rank=rank, archive=archive,
+                    bounds=bounds, census=census)
     return res, sp
 
 
 def demczs_entry(res: DemcZs, k: int, n: int, cell_index: int) -> Dict:
     """One ``MCMCdemczs`` entry (``DEMCZS_FIELDS``) from selected cell ``k`` of ``res``: :func:`demc_entry`'s values plus
     ``n_null`` per chain, ``snooker_rate`` (the share of snooker moves among the generations ``res`` logged, its first
-    ``log_rows``: not of the whole run when the log is shorter; NaN without a log), ``m0`` and ``n_archive``."""
+    ``log_rows``: not of the whole run when the log is shorter; NaN without a log), ``m0`` and ``n_archive``. With the
+    census: ``n_cross``, ``oob_lo`` and ``oob_hi`` ``[7 + n]`` summed over the cell's chains and ``oob_share`` ``[7 + n]``,
+    ``(oob_lo + oob_hi)`` over the cell's bounds-rejected proposals. In reject mode that is the share of those proposals
+    in which coordinate ``j`` had left; in reflect mode a leaving coordinate is reflected and the counters do not say
+    which proposals were rejected, so it is NaN. With ``bounds='reflect'``: ``reflect_rate``, the evaluated proposals
+    with at least one reflection over all proposals. None when the feature is off."""
     n_pop = int(res.pop.shape[1])
     snk = res.snooker[:, k * n_pop:(k + 1) * n_pop]
     d = dict(demc_entry(res, k, n, cell_index), n_null=res.n_null[k].copy(),
-             snooker_rate=float(snk.mean()) if snk.size else float("nan"), m0=int(res.m0), n_archive=int(res.n_archive))
+             snooker_rate=float(snk.mean()) if snk.size else float("nan"), m0=int(res.m0), n_archive=int(res.n_archive),
+             n_cross=None, oob_lo=None, oob_hi=None, oob_share=None, reflect_rate=None)
+    P = 7 + int(n)
+    if res.census:
+        for f in ("n_cross", "oob_lo", "oob_hi"):
+            d[f] = getattr(res, f)[k, :, :P].astype(np.int64).sum(axis=0)
+        rejected = int(res.n_oob[k].sum())
+        left = (d["oob_lo"] + d["oob_hi"]).astype(np.float64)
+        d["oob_share"] = left / rejected if res.bounds == "reject" and rejected else np.full(P, np.nan)
+    if res.bounds == "reflect":
+        d["reflect_rate"] = float(res.n_reflected[k].sum()) / (n_pop * res.n_gen) if res.n_gen else float("nan")
     return {f: d[f] for f in DEMCZS_FIELDS}
 
 
